@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py -- node-embeddings/sec of the GraphSAGE 2-hop mean-aggregate forward on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds what else the bench measures or checks: the
+fp64-oracle parity gate and the bit-for-bit check of the timed path, the roofline / per-kernel timing passes, the side variants
+(caller's node order, pre-transformed table), BASELINE configs[3] beside the headline, and the CPU baseline.
+--dump-outputs DIR writes the embeddings the timed path computed in its last step to DIR/embeddings.npy (float32).
 
 One "step" = one 2-hop forward (sample both hops + frontier dedupe + layer 1 on the frontier +
 layer 2 on the seeds) over one batch of B seed nodes, through the C ABI (sage_forward2).
@@ -111,6 +116,12 @@ def parse():
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL, default) or gloo (rehearsing N > 1 on a 1-GPU box)")
     ap.add_argument("--share-device", action="store_true", help="rehearsal only: every rank uses cuda:0 (more than two ranks: the configs[3] "
                                                                   "variant is off unless --scale-variant on: 45 GB per rank)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline figure: parity gate and timed-path check, roofline / per-kernel passes, "
+                         "side variants, the configs[3] variant and the CPU baseline (--no-parity, --no-variant, --scale-variant and "
+                         "--cpu-seconds act within it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the embeddings the timed path computed in its last step (rank 0) to DIR/embeddings.npy, float32")
     args = ap.parse_args()
     given = {a.split("=")[0].lstrip("-").replace("-", "_") for a in sys.argv[1:] if a.startswith("--")}
     args.exec_given = "exec" in given or "SAGE_EXEC" in os.environ
@@ -248,13 +259,14 @@ def main():
             torch.cuda.synchronize()
 
     # ---- the headline: BASELINE configs[2] (or --config N) ----
-    head = run_workload(args, rank, world, dev, dist, fence, host, side_variants=not args.no_variant, with_cpu=args.cpu_seconds > 0)
+    head = run_workload(args, rank, world, dev, dist, fence, host, side_variants=args.full and not args.no_variant,
+                        with_cpu=args.full and args.cpu_seconds > 0, dump_dir=args.dump_outputs)
     variants = head.pop("variants", None) if head is not None else None
 
     # ---- BASELINE configs[3] (R-MAT 2^23 / 128 M edges: the workload BASELINE names for the 1/2/4/8 curve) beside it, at EVERY N since round 4
     #      (VERDICT r3 #2): the same function, hence the same K / W, fences, max-over-ranks, oracle gate, timed-path check, counted bytes and
     #      live kernel timing as the headline; never substituted for `value` ----
-    if args.scale_variant == "on" or (args.scale_variant == "auto" and args.config == 3):
+    if args.full and (args.scale_variant == "on" or (args.scale_variant == "auto" and args.config == 3)):
         import copy
         a4 = copy.copy(args)
         for key, val in PRESETS[4].items():
@@ -280,7 +292,7 @@ def main():
             "metric": "node-embeddings/sec (2-hop forward)", "value": head["value"], "unit": "embeddings/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": head["ms_per_step"],
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": dict(head["config"], variants=variants, host=host,
+            "config": dict(head["config"], variants=variants, host=host, full=args.full,
                            parallelism=f"seed-shard x{world}, replicated graph+features, no forward collective"),
             "parity_max_err_vs_fp64_oracle": head["parity_err"], "timed_path_check": head["timed_check"],
             "roofline": head["roofline"], "cpu_baseline": head["cpu_baseline"],
@@ -340,9 +352,10 @@ def mark(rank, msg):
     _PROGRESS["fh"].write(f"{time.perf_counter() - _PROGRESS['t0']:8.2f} {msg}\n")
 
 
-def run_workload(args, rank, world, dev, dist, fence, host, side_variants, with_cpu):
-    """One workload (args.config and the sizes its preset filled in) through the parity gate, the timed region, the timed-path check and
-    the kernel / byte accounting.  Every rank runs it; rank 0 returns the dict the JSON line is made of, the others None."""
+def run_workload(args, rank, world, dev, dist, fence, host, side_variants, with_cpu, dump_dir=None):
+    """One workload (args.config and the sizes its preset filled in) through the timed region and, with --full, the parity gate, the
+    timed-path check and the kernel / byte accounting.  Every rank runs it; rank 0 returns the dict the JSON line is made of, the others
+    None.  dump_dir: rank 0 writes the output of the last timed step there (dump_outputs)."""
     t_setup = time.perf_counter()
     from sage355.engine import RolePipeline, TwoHopEngine
     from sage355.graph import rmat_graph
@@ -395,18 +408,24 @@ def run_workload(args, rank, world, dev, dist, fence, host, side_variants, with_
     # the outer-hop kernel inside every timed forward; outputs are in the caller's seed order.
     relabel = "degree" if (args.engine_layout == "degree" and args.config != 2 and args.node_order != "degree") else None
     ekw = dict(concat=concat, agg_self_loop=args.self_loop, fused=not args.unfused, relabel=relabel)
-    base = TwoHopEngine(rowptr, col, table, w1, w2, k1, k2, max_batch=b, **ekw)
-    mark(rank, "engine built")
-    base_split = base.layout.layer1_split
+    exec_mode = args.exec
+    if args.config == 2 and args.exec == "pipe" and not args.exec_given:
+        exec_mode = "replay"        # 256-seed batches: 20 us of GPU work per batch, less than the host's enqueue per batch
+    # the single-forward engine: the timed path of the replay / direct modes; in the pipe modes only the gate and the accounting
+    # passes of --full use it
+    base = None
+    if args.full or exec_mode not in ("pipe", "pipegraph"):
+        base = TwoHopEngine(rowptr, col, table, w1, w2, k1, k2, max_batch=b, **ekw)
+        mark(rank, "engine built")
     nstreams = max(1, args.streams)
 
-    # ---- parity gate: one batch against the fp64 oracle on the GPU's own sampled sets.  The batch is the LAST one of the timed
-    #      region: after the timed region the output the role pipeline left for that very batch is compared with this one bit
+    # ---- parity gate (--full): one batch against the fp64 oracle on the GPU's own sampled sets.  The batch is the LAST one of the
+    #      timed region: after the timed region the output the role pipeline left for that very batch is compared with this one bit
     #      for bit (gate the path that is timed, at the size it is timed) ----
     parity_err = None
     gate_i = total_steps - 1
     gate_out = None
-    if not args.no_parity and rank == 0:
+    if args.full and not args.no_parity and rank == 0:
         from oracle import ref_sparse
         gate_out = base.forward(seeds_dev[gate_i], seed=sampler_seed[gate_i]).clone()
         o = gate_out.cpu()
@@ -428,10 +447,7 @@ def run_workload(args, rank, world, dev, dist, fence, host, side_variants, with_
     #  pipe   (default): RolePipeline -- stages S / G / D / L on role streams, `depth` batches in flight, one host call per batch
     #  replay          : hipGraph replay from a device batch queue, `streams` independent forwards in flight (round 1's mode)
     #  direct          : host-enqueued sage_forward2 calls
-    exec_mode = args.exec
     bpr = args.batches_per_replay if args.batches_per_replay > 0 else (10 if args.config == 2 else 1)
-    if args.config == 2 and args.exec == "pipe" and not args.exec_given:
-        exec_mode = "replay"        # 256-seed batches: 20 us of GPU work per batch, less than the host's enqueue per batch
     pipe = None
     engines, streams, outs = [], [], []
     pipe_graphs = None
@@ -469,6 +485,7 @@ def run_workload(args, rank, world, dev, dist, fence, host, side_variants, with_
             torch.cuda.synchronize()
 
     pipe_threaded = bool(pipe is not None and pipe.threads)
+    base_split = (base if base is not None else pipe.engines[0]).layout.layer1_split
 
     def run(step_range):
         if pipe_graphs is not None:
@@ -545,18 +562,22 @@ def run_workload(args, rank, world, dev, dist, fence, host, side_variants, with_
     value = world * b * args.steps / elapsed
     mark(rank, f"timed region done: {ms_per_step * 1e3:.1f} us per step")
 
-    # ---- the timed path's own output, checked AFTER the clock stopped: what the timed execution mode left for the gate batch
-    #      (the last timed step) against the oracle-gated single forward of the same (seeds, key), bit for bit ----
+    # ---- the timed path's own output for its last step (= the gate batch): the output slot the timed execution mode wrote ----
+    if pipe_graphs is not None:
+        got = pipe_out[(gate_i - args.warmup) % pipe_out.shape[0]]          # the timed graph numbers its batches from 0
+    elif pipe is not None:
+        got = pipe_out[gate_i % pipe_out.shape[0]]
+    elif exec_mode == "replay" and bpr > 1:
+        got = engines[(gate_i // bpr) % nstreams]._graph_out[gate_i % bpr]
+    else:
+        got = outs[gate_i % nstreams]
+    if dump_dir is not None and rank == 0:
+        dump_outputs(dump_dir, {"embeddings": got})
+
+    # ---- --full: that output checked AFTER the clock stopped against the oracle-gated single forward of the same (seeds, key),
+    #      bit for bit ----
     timed_check = None
     if gate_out is not None:
-        if pipe_graphs is not None:
-            got = pipe_out[(gate_i - args.warmup) % pipe_out.shape[0]]      # the timed graph numbers its batches from 0
-        elif pipe is not None:
-            got = pipe_out[gate_i % pipe_out.shape[0]]
-        elif exec_mode == "replay" and bpr > 1:
-            got = engines[(gate_i // bpr) % nstreams]._graph_out[gate_i % bpr]
-        else:
-            got = outs[gate_i % nstreams]
         same = bool(torch.equal(got, gate_out))
         timed_check = {"batch": gate_i, "bit_identical_to_oracle_gated_forward": same,
                        "what": "output slot the timed region wrote for its last step vs TwoHopEngine.forward(same seeds, same key), "
@@ -583,7 +604,7 @@ def run_workload(args, rank, world, dev, dist, fence, host, side_variants, with_
     #      a busy queue read 5-9 us longer.  The other stages' figures in stage_ms_alone are still marker intervals.
     #      The data-determined set sizes of every batch are counted by torch reductions after pass (b). ----
     roofline = None
-    if rank == 0:
+    if rank == 0 and args.full:
         he = HipEvents()
         split = bool(base.layout.layer1_split)      # layer 1 ran as column-sliced gather + dense contraction
         insitu_ms = None
@@ -843,6 +864,25 @@ def run_workload(args, rank, world, dev, dist, fence, host, side_variants, with_
     del table, rowptr, col, seeds_dev
     torch.cuda.empty_cache()
     return result
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dump_dir, arrays):
+    """--dump-outputs: each device array as DIR/<name>.npy in float32, so that two builds can be compared output for output.  All
+    arrays together stay within DUMP_LIMIT_BYTES: an array past its share keeps a fixed, seeded sample of its rows (sorted), whose
+    indices go to DIR/<name>_rows.npy (float64)."""
+    os.makedirs(dump_dir, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // (2 * max(1, len(arrays)))          # half of it: the row indices of a sample need room too
+    for name, t in arrays.items():
+        a = t.detach().to(torch.float32).cpu().numpy()
+        row_bytes = max(1, a[0].nbytes if a.shape[0] else 1)
+        if a.nbytes > share:
+            rows = np.sort(np.random.default_rng(0).choice(a.shape[0], max(1, share // row_bytes), replace=False))
+            a = a[rows]
+            np.save(os.path.join(dump_dir, name + "_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(dump_dir, name + ".npy"), np.ascontiguousarray(a))
 
 
 def cpu_port_baseline(graph, table, w1, w2, candidates, k1, k2, concat, budget_s):

@@ -78,3 +78,24 @@ def test_host_plan_turns_the_role_threads_on_only_where_every_rank_has_five_core
     assert bench.host_plan(types.SimpleNamespace(host_threads=0, roles="SGDL"), 1)["role_threads"] is False
     assert bench.host_plan(types.SimpleNamespace(host_threads=1, roles="SGDD"), 1)["role_threads"] is False      # three streams: no role threads
     assert 1 <= bench.usable_host_cores.__wrapped__() if hasattr(bench.usable_host_cores, "__wrapped__") else True
+
+
+def test_dump_outputs_writes_float32_and_samples_past_the_limit(tmp_path, monkeypatch):
+    """--dump-outputs: DIR/<name>.npy in float32; an array past its share of the 64 MB keeps a fixed, seeded, sorted sample of its
+    rows, whose indices are written beside it -- the same rows every run."""
+    import numpy as np
+    import torch
+    small = torch.arange(12, dtype=torch.float64).reshape(3, 4)
+    bench.dump_outputs(str(tmp_path / "a"), {"embeddings": small})
+    got = np.load(tmp_path / "a" / "embeddings.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small.numpy().astype(np.float32))
+    assert sorted(os.listdir(tmp_path / "a")) == ["embeddings.npy"]
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1 << 12)           # share = 2 KB = 32 rows of 16 floats
+    big = torch.randn(1000, 16, generator=torch.Generator().manual_seed(3))
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"embeddings": big})
+    emb, rows = np.load(tmp_path / "b" / "embeddings.npy"), np.load(tmp_path / "b" / "embeddings_rows.npy")
+    assert emb.shape == (32, 16) and rows.dtype == np.float64 and np.all(np.diff(rows) > 0)
+    assert np.array_equal(emb, big.numpy()[rows.astype(np.int64)])
+    assert emb.nbytes + rows.nbytes <= bench.DUMP_LIMIT_BYTES
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "embeddings_rows.npy"))

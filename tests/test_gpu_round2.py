@@ -291,7 +291,7 @@ def test_bench_two_ranks_say_how_the_pipeline_was_fed():
     where each rank of the node has five usable cores to itself -- and the line says which mode ran (config.host).  Two ranks share this
     box's one GPU (gloo), the headline workload, no side variants."""
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--share-device", "--dist-backend", "gloo", "--steps", "20", "--warmup", "5",
-           "--cpu-seconds", "0", "--preheat-seconds", "0.05", "--no-variant", "--scale-variant", "off"]
+           "--full", "--cpu-seconds", "0", "--preheat-seconds", "0.05", "--no-variant", "--scale-variant", "off"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])

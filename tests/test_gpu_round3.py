@@ -389,7 +389,7 @@ needs_two_gpus = pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs
 def test_bench_gpus_2_over_rccl_one_gpu_per_rank():
     """The N > 1 form as the driver runs it: `python bench.py --gpus 2`, backend nccl (= RCCL over xGMI), one GPU per rank, BASELINE
     configs[2] at full size with configs[3] (R-MAT 2^23, the workload BASELINE names for the scaling curve) as a variant."""
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--cpu-seconds", "0"]
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--cpu-seconds", "0"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=1500)
     assert res.returncode == 0, res.stderr[-3000:]
     line = json.loads([ln for ln in res.stdout.splitlines() if ln.startswith("{")][-1])
@@ -573,11 +573,11 @@ def test_role_pipeline_host_threads_are_bit_identical_over_a_long_run(window, co
 
 # ------------------------------------------------------------------------------------------ the bench line's contract
 def test_bench_line_as_the_driver_runs_it_keeps_the_contract():
-    """`python bench.py --gpus 1 --steps 20 --warmup 5` (the driver's command; the CPU baseline's budget cut to 3 s here): ONE JSON
-    line on stdout with the contract's keys, BASELINE's metric on configs[2], `roofline` and `cpu_baseline` objects whose figures are
-    consistent with each other, the timed path's output checked bit for bit, and the 1e-5 parity gate passed."""
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --full` (the CPU baseline's budget cut to 3 s here): ONE JSON line on stdout
+    with the contract's keys, BASELINE's metric on configs[2], `roofline` and `cpu_baseline` objects whose figures are consistent with
+    each other, the timed path's output checked bit for bit, and the 1e-5 parity gate passed."""
     r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"), "--gpus", "1",
-                        "--steps", "20", "--warmup", "5", "--cpu-seconds", "3"], capture_output=True, text=True, timeout=900)
+                        "--steps", "20", "--warmup", "5", "--full", "--cpu-seconds", "3"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, lines
@@ -613,6 +613,31 @@ def test_bench_line_as_the_driver_runs_it_keeps_the_contract():
     h = cfg["host"]
     assert h["ranks_on_node"] == 1 and h["cores_per_rank"] == h["host_cores_usable"] and h["role_threads"] == (h["cores_per_rank"] >= 5)
     assert ("host enqueue thread" in cfg["execution"]) == h["role_threads"]
+
+
+def test_bench_plain_line_times_only_the_headline_and_dumps_its_last_step(tmp_path):
+    """`python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR`: ONE JSON line with the contract's keys, `value` consistent
+    with `ms_per_step`, nothing that --full adds (no gate, no roofline, no CPU baseline, no variants), and DIR/embeddings.npy = the
+    [B, H2] float32 embeddings of the last timed step.  Two runs with the same arguments dump the same bits."""
+    dumps = []
+    for run in range(2):
+        out = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"), "--gpus", "1",
+                            "--steps", "20", "--warmup", "5", "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, lines
+        d = json.loads(lines[0])
+        assert d["metric"].startswith("node-embeddings/sec") and d["unit"] == "embeddings/s" and d["higher_is_better"] is True
+        assert (d["n_gpus"], d["steps"], d["warmup"], d["dtype"]) == (1, 20, 5, "f32")
+        assert abs(d["value"] - 4096 / (d["ms_per_step"] * 1e-3)) <= 1e-3 * d["value"]
+        assert d["config"]["full"] is False and d["config"]["variants"] is None
+        assert d["roofline"] is None and d["cpu_baseline"] is None and d["timed_path_check"] is None
+        assert sorted(os.listdir(out)) == ["embeddings.npy"]
+        emb = np.load(out / "embeddings.npy")
+        assert emb.dtype == np.float32 and emb.shape == (4096, 128) and np.isfinite(emb).all() and (emb != 0).any()
+        dumps.append(emb)
+    assert np.array_equal(dumps[0], dumps[1])
 
 
 # ------------------------------------------------------------------------------------------ inference on a pre-transformed table
