@@ -25,9 +25,17 @@ by a fingerprint over all set sizes and the contents of ~256 rows (adjacencies
 up to 200 000 keys), (c) on every call when ``SAGE_ADJ_STRICT=1``.  An in-place
 edit that keeps every probed size can therefore be served from the stale CSR
 for up to 63 forwards: call ``invalidate_adjacency(adj_lists)`` after editing an
-adjacency an Encoder has already seen.  The feature table is treated as frozen
-too (model.py:214-215): in-place writes that bump the tensor's version counter
-are picked up, ``.data`` writes need ``TwoHopEngine.refresh_table()``.
+adjacency an Encoder has already seen.
+
+Feature table and weight updates.  The forward may read private copies of
+``features.weight`` and of the ``weight`` Parameters (a device copy of a host
+tensor under ``cuda=False``; the two-hop engine's zero-padded copies and bf16
+weight planes).  Writes that move a tensor's version counter (``w[rows] = x``
+or ``w.add_(d)`` under ``torch.no_grad()``, an optimizer step) are picked up
+by the next forward.  Writes that do not (``w.data[...] = ...``, a collective)
+need one call on either Encoder of the pair before the next forward:
+``refresh_features()`` after writing ``features.weight``,
+``invalidate_weights()`` after writing a ``weight``.
 
 Sampling: the device sampler draws k distinct uniform neighbours per node
 (all of them when deg < k), the reference's rule (aggregators.py:42-46), from a
@@ -43,6 +51,7 @@ call as the reference does.
 """
 import collections
 import random
+import weakref
 
 import numpy as np
 import torch
@@ -207,6 +216,7 @@ class Encoder(nn.Module):
         self._engine = None
         self._engine_key = None
         self._dev_cache = {}
+        self._engine_readers = []              # weak references to the Encoders whose two-hop engine reads this one's table / weight
         print("feat dim:", self.feat_dim, "embed_dim:", self.embed_dim)   # encoders.py:38
 
     # ------------------------------------------------------------------ helpers
@@ -223,6 +233,44 @@ class Encoder(nn.Module):
             hit = (key, t.detach().to("cuda", torch.float32).contiguous())
             self._dev_cache[tag] = hit
         return hit[1]
+
+    def _pair(self):
+        """This Encoder and its base model, when that is an Encoder."""
+        base = getattr(self, "base_model", None)
+        return [self] + ([base] if isinstance(base, Encoder) else [])
+
+    def _engines(self):
+        """Every two-hop engine that reads this Encoder's or its base model's tensors."""
+        engines = []
+        for enc in self._pair():
+            for e in [enc] + [r() for r in enc._engine_readers]:
+                if e is not None and e._engine is not None and all(x is not e._engine for x in engines):
+                    engines.append(e._engine)
+        return engines
+
+    def refresh_features(self):
+        """`features.weight` was written in a way that does not move its version counter (`features.weight.data[...] = ...`, a
+        collective): bring every copy the forward reads up to date before the next forward -- the device copy of a host table
+        (cuda=False), rewritten in place, and the private copies of each two-hop engine over it (TwoHopEngine.refresh_table).
+        Either Encoder of the pair may be called."""
+        for enc in self._pair():
+            hit = enc._dev_cache.get("table")
+            if hit is not None and enc._is_table() and tuple(hit[1].shape) == tuple(enc.features.weight.shape):
+                hit[1].copy_(enc.features.weight.detach())
+        for eng in self._engines():
+            eng.refresh_table()
+
+    def invalidate_weights(self):
+        """A `weight` Parameter was written in a way that does not move its version counter (`.data`, a collective): the next forward
+        re-reads both layers' weights -- the device copies of host Parameters (cuda=False) and the two-hop engine's zero-padded
+        copies and bf16 planes (TwoHopEngine.invalidate_weights).  Either Encoder of the pair may be called."""
+        for enc in self._pair():
+            enc._dev_cache.pop("weight", None)
+            hit = enc._dev_cache.get("engine_w")
+            if hit is not None and hit[0] == "host":
+                hit[1] = None                      # the next _engine_weight copies the host Parameter into the same device buffer
+        for eng in self._engines():
+            eng.invalidate_weights()
 
     def _weight_dev(self):
         w = self.weight
@@ -311,6 +359,8 @@ class Encoder(nn.Module):
                                         agg_self_loop=self._agg_self_loop(), act1=base._act(), act2=self._act(),
                                         nan_empty=True, max_batch=max(len(nodes), 256), rowptr_outer=rp2, col_outer=c2)
             self._engine_key = key
+            if all(r() is not self for r in base._engine_readers):
+                base._engine_readers.append(weakref.ref(self))
         elif r1 or r2:
             self._engine.invalidate_weights()             # the buffers were rewritten in place: planes / padded copies are stale
         sampler_key = random.getrandbits(64)

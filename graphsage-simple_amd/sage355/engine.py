@@ -44,25 +44,36 @@ def pretransform_table(table, w1, rows_per_call=1 << 18):
     return y, eye                      # skipped and the column-sliced gather applies the activation and writes h1 itself
 
 
+class _Shared:
+    """What an engine and its siblings share about the caller's tensors: the caller's table behind a private copy (relabelled and / or
+    zero-padded; None when the engine reads the caller's table itself) with the version counter it was last copied at, the zero-padded
+    weight copies with the key they were made under, and the epoch that invalidate_weights() moves."""
+
+    def __init__(self, src):
+        self.src = src
+        self.version = src._version if src is not None else None
+        self.weights_epoch = 0
+        self.w1p = self.w2p = self.wpad_key = None
+
+
 class TwoHopEngine:
     def __init__(self, rowptr, col, table, w1, w2, k1, k2, concat=False, agg_self_loop=False, act1=ACT_RELU,
                  act2=ACT_RELU, nan_empty=True, fused=True, max_batch=4096, rowptr_outer=None, col_outer=None, relabel=None,
-                 prepare_weights=True, slice_major="auto", _shared_sliced=None):
+                 prepare_weights=True, slice_major="auto", _parent=None):
         """rowptr/col: CSR of enc1.adj_lists (inner hop); rowptr_outer/col_outer: CSR of
         enc2.adj_lists when it differs (injected pre-sampled sets), default the same.
         w1 [h1, d0 | 2*d0], w2 [h2, h1 | 2*h1]: the Encoders' `weight` Parameters
-        (referenced, not copied: an optimizer step is seen by the next forward)."""
+        (referenced, not copied: an optimizer step is seen by the next forward).
+        table: referenced too.  When the engine works on a private copy of it (relabel="degree", padded widths) the copy is
+        re-derived in place whenever the table's version counter moves; see refresh_table() for writes that do not move it."""
         _need_gpu()
-        self._ctor = dict(rowptr=rowptr, col=col, table=table, w1=w1, w2=w2, k1=k1, k2=k2, concat=concat, agg_self_loop=agg_self_loop,
-                          act1=act1, act2=act2, nan_empty=nan_empty, fused=fused, max_batch=max_batch, rowptr_outer=rowptr_outer,
-                          col_outer=col_outer, relabel=relabel, prepare_weights=prepare_weights, slice_major=slice_major)
         self.rowptr1 = _chk(rowptr, torch.int64, "rowptr", 1)
         self.col1 = _chk(col, torch.int32, "col", 1)
         self.rowptr2 = self.rowptr1 if rowptr_outer is None else _chk(rowptr_outer, torch.int64, "rowptr_outer", 1)
         self.col2 = self.col1 if col_outer is None else _chk(col_outer, torch.int32, "col_outer", 1)
         if self.rowptr2.shape[0] != self.rowptr1.shape[0]:
             raise native.SageError("inner and outer CSR must cover the same node ids")
-        self.table, self.table_ld = _row_major(table, "table")
+        self.table, self.table_ld = _row_major(table, "table")         # the caller's tensor itself (_row_major checks, never copies)
         # relabel="degree": work on a copy of graph and table renumbered by descending degree, so that the rows gathered
         # most often are neighbours in memory (config 3: gather 46 -> 40 us).  The outer-hop kernel translates the seeds
         # (model.seed_map), so the caller keeps its ids and outputs stay in the caller's seed order; ids in intermediates()
@@ -71,27 +82,32 @@ class TwoHopEngine:
         self.node_order = self._new_of_old = None
         if relabel not in (None, "degree"):
             raise native.SageError("relabel must be None or 'degree'")
-        if relabel == "degree":
+        if _parent is not None:              # a sibling: the parent's renumbering and private table copies, shared (sibling())
+            self.node_order, self._new_of_old = _parent.node_order, _parent._new_of_old
+            self.table, self.table_ld = _parent.table, _parent.table_ld
+        elif relabel == "degree":
             self._relabel_by_degree()
         self.num_nodes = self.rowptr1.shape[0] - 1
         if self.table.shape[0] < self.num_nodes:
             raise native.SageError(f"table has {self.table.shape[0]} rows for {self.num_nodes} nodes")
         self.w1, self.w2 = w1, w2
-        self.d0 = self.table.shape[1]
+        self.d0 = table.shape[1]
         self.h1, self.h2 = w1.shape[0], w2.shape[0]
         mult = 2 if concat else 1
         if tuple(w1.shape) != (self.h1, mult * self.d0) or tuple(w2.shape) != (self.h2, mult * self.h1):
             raise native.SageError(f"weight shapes {tuple(w1.shape)}, {tuple(w2.shape)} do not fit d0={self.d0}, concat={concat}")
         # The 16-B-per-lane kernels want row widths that are multiples of 4 floats.  Cora's 1433 raw features and the
         # reference's default 50-wide layer 1 (model.py:543) are not: the engine then works on zero-padded copies
-        # (table once -- it is frozen, model.py:214-215 -- and the weights whenever their version counter moves).
+        # (table and weights re-derived in place whenever the caller's version counters move, _sync_table / _weights).
         # Zero weight rows / columns make the pad inert: relu(0) = 0, and sigmoid's 0.5 meets a zero column of W2.
         self.d0p, self.h1p = -(-self.d0 // 4) * 4, -(-self.h1 // 4) * 4
         self._padded = (self.d0p != self.d0) or (self.h1p != self.h1)
-        if self.d0p != self.d0 or self.table_ld % 4 != 0 or self.table.data_ptr() % 16 != 0:
+        if _parent is None and (self.d0p != self.d0 or self.table_ld % 4 != 0 or self.table.data_ptr() % 16 != 0):
             padded = torch.zeros((self.table.shape[0], self.d0p), dtype=torch.float32, device=self.table.device)
             padded[:, :self.d0] = self.table
             self.table, self.table_ld = padded, self.d0p
+        # siblings share one _Shared: a refresh through any engine of a pipe reaches every one of them
+        self._shared = _parent._shared if _parent is not None else _Shared(table if self.table is not table else None)
         # Slice-major second copy of the table for the column-sliced layer-1 gather: float[d0 / W][N][W] (W = 32 floats = 128-byte
         # slices by default), so that the XCD that owns a slice reads ONE contiguous array -- consecutive hub rows' slices share DRAM
         # pages and L2 sets -- instead of 128 bytes out of every KiB.  With it the 128-byte slices that round 2 measured SLOWER on the
@@ -103,12 +119,10 @@ class TwoHopEngine:
         # one stays for whole-row consumers (the concat encoder's own rows, the backward, read-back).
         # slice_major: "auto" / True / False; SAGE_TABLE_SLICED=0 disables, SAGE_TABLE_SLICE_FLOATS = 32 / 64 / 128 picks W.
         import os
-        self._table_sliced = _shared_sliced
+        self._table_sliced = _parent._table_sliced if _parent is not None else None
         self._table_sliced_version = self.table._version
         _sl = os.environ.get("SAGE_TABLE_SLICED", "1")              # 0: never, 1: "auto" as above, 2: "auto" includes the concat encoder (A/B)
         self._want_sliced = slice_major is True or (slice_major == "auto" and (_sl == "2" or (not concat and _sl != "0")))
-        self._wpad_key = None
-        self._w1p = self._w2p = None
         self._w1prep = self._w1prep_key = None
         self.prepare_weights = bool(prepare_weights)
         self.k1, self.k2 = int(k1), int(k2)
@@ -158,16 +172,13 @@ class TwoHopEngine:
 
     def sibling(self):
         """Another engine over the SAME device graph / table / weights (shared, not copied) with a workspace of its own:
-        what every additional mini-batch in flight needs."""
-        if self._padded:                      # zero-padded copies of table / weights (small graphs): just build another
-            return TwoHopEngine(**self._ctor)
-        e = TwoHopEngine(self.rowptr1, self.col1, self.table, self.w1, self.w2, self.k1, self.k2, concat=self.concat,
-                         agg_self_loop=self.agg_self_loop, act1=self.act1, act2=self.act2, nan_empty=self.nan_empty, fused=self.fused,
-                         max_batch=self.max_batch, rowptr_outer=self.rowptr2, col_outer=self.col2, relabel=None,
-                         prepare_weights=self.prepare_weights, slice_major=self._table_sliced is not None, _shared_sliced=self._table_sliced)
-        e.node_order, e._new_of_old = self.node_order, self._new_of_old
-        e._model_key = None
-        return e
+        what every additional mini-batch in flight needs.  The private copies (renumbered / zero-padded table, slice-major copy,
+        zero-padded weights) are shared too, so a refresh through any one engine reaches all of them."""
+        src = self._shared.src if self._shared.src is not None else self.table
+        return TwoHopEngine(self.rowptr1, self.col1, src, self.w1, self.w2, self.k1, self.k2, concat=self.concat,
+                            agg_self_loop=self.agg_self_loop, act1=self.act1, act2=self.act2, nan_empty=self.nan_empty, fused=self.fused,
+                            max_batch=self.max_batch, rowptr_outer=self.rowptr2, col_outer=self.col2, relabel=None,
+                            prepare_weights=self.prepare_weights, slice_major=self._table_sliced is not None, _parent=self)
 
     def _seeds_in(self, seeds):
         """Seeds cross the boundary in the CALLER's ids; with relabel="degree" the outer-hop kernel translates them
@@ -178,28 +189,33 @@ class TwoHopEngine:
         """The weight tensors the kernels read: the caller's own, or zero-padded copies kept in step with them."""
         if not self._padded:
             return self.w1, self.w2
-        key = (self.w1.data_ptr(), self.w1._version, self.w2.data_ptr(), self.w2._version)
-        if key != self._wpad_key:
+        s = self._shared
+        key = (self.w1.data_ptr(), self.w1._version, self.w2.data_ptr(), self.w2._version, s.weights_epoch)
+        if key != s.wpad_key:
             m = 2 if self.concat else 1
-            if self._w1p is None:
-                self._w1p = torch.zeros((self.h1p, m * self.d0p), dtype=torch.float32, device=self.device)
-                self._w2p = torch.zeros((self.h2, m * self.h1p), dtype=torch.float32, device=self.device)
-            with torch.no_grad():
+            if s.w1p is None:
+                s.w1p = torch.zeros((self.h1p, m * self.d0p), dtype=torch.float32, device=self.device)
+                s.w2p = torch.zeros((self.h2, m * self.h1p), dtype=torch.float32, device=self.device)
+            with torch.no_grad():                # in place: the pointers a pipe or a captured graph holds stay valid
                 for c in range(m):
-                    self._w1p[:self.h1, c * self.d0p: c * self.d0p + self.d0] = self.w1[:, c * self.d0: (c + 1) * self.d0]
-                    self._w2p[:, c * self.h1p: c * self.h1p + self.h1] = self.w2[:, c * self.h1: (c + 1) * self.h1]
-            self._wpad_key = key
-        return self._w1p, self._w2p
+                    s.w1p[:self.h1, c * self.d0p: c * self.d0p + self.d0] = self.w1[:, c * self.d0: (c + 1) * self.d0]
+                    s.w2p[:, c * self.h1p: c * self.h1p + self.h1] = self.w2[:, c * self.h1: (c + 1) * self.h1]
+            s.wpad_key = key
+        return s.w1p, s.w2p
 
     def invalidate_weights(self):
-        """Forget every cached form of the weights (zero-padded copies, bf16 planes, the C model struct): the next forward
-        rebuilds them from the tensors as they are NOW.  The caches are keyed on (data_ptr, tensor._version), which does not move
-        when the weights are written through `.data`, by a collective, or by a replayed hipGraph."""
-        self._w1prep_key = self._wpad_key = self._model_key = None
+        """The weights were written in a way that does not move their version counters (`.data`, a collective, a replayed hipGraph):
+        forget every cached form of them (zero-padded copies, bf16 planes, the C model struct), for this engine and its siblings; the
+        next forward rebuilds them, in place, from the tensors as they are NOW.  In-place writes that move the version counters
+        (an optimizer step, `w.add_(...)` under no_grad) need no call: the next forward notices them.  Between replays of a captured
+        graph use refresh_weights() instead."""
+        self._shared.weights_epoch += 1
+        self._w1prep_key = self._model_key = None
 
     def refresh_weights(self):
-        """Re-read the caller's weights into the padded copies (only needed between replays of a captured graph when
-        the widths are padded; `forward` does it by itself)."""
+        """Re-read the caller's weights NOW, whatever wrote them, into the zero-padded copies and the bf16 planes, in place: the call to
+        make before replaying a captured graph after any weight update (a replay does not look at version counters)."""
+        self.invalidate_weights()
         self._model(queued=self._queue is not None)
 
     def _prepare_w1(self, w1):
@@ -209,7 +225,7 @@ class TwoHopEngine:
         need = L.sage_prepared_weight_bytes(self.d0p, self.h1p, int(self.concat))
         if need == 0 or not self.prepare_weights:
             return None
-        key = (w1.data_ptr(), w1._version)
+        key = (w1.data_ptr(), w1._version, self._shared.weights_epoch)
         if self._w1prep is None or self._w1prep.numel() != need:
             self._w1prep = torch.empty(need, dtype=torch.uint8, device=self.device)
             self._w1prep_key = None
@@ -224,6 +240,8 @@ class TwoHopEngine:
         column-sliced gather with 256-byte slices of whole 64-float pieces."""
         import os
         w = int(os.environ.get("SAGE_TABLE_SLICE_FLOATS", "32"))         # floats per slice: 32 (128 B, default) / 64 / 128
+        if getattr(self, "_slice_floats", None) != w:
+            self._model_key = None           # the model struct carries the slice width (a sibling's first one was built before it was known)
         self._slice_floats = w
         ok = (self._want_sliced and bool(self.layout.layer1_split) and w in (32, 64, 128) and self.d0p % w == 0 and self.d0p >= 2 * w
               and self.table_ld == self.d0p and self.table.shape[0] == self.num_nodes)
@@ -242,15 +260,31 @@ class TwoHopEngine:
                 self._model_key = None
             self._table_sliced_version = self.table._version
 
+    def _sync_table(self, force=False):
+        """Re-derive the private table copy (renumbered and / or zero-padded) from the caller's table, IN PLACE (role pipelines and
+        captured graphs hold its pointer), when the caller's version counter has moved since the last copy, or always (force).
+        An integer compare when nothing changed; a no-op for an engine that reads the caller's table itself."""
+        s = self._shared
+        if s.src is None or (not force and s.src._version == s.version):
+            return
+        with torch.no_grad():
+            rows = s.src if self.node_order is None else s.src[self.node_order]
+            self.table[:, :self.d0].copy_(rows)          # the pad columns are never written: they stay zero
+        s.version = s.src._version
+
     def refresh_table(self):
-        """The table was written in a way that does not move its version counter (`.data`, a collective, a replayed hipGraph): bring the
-        engine's slice-major copy up to date, in place (pointers held by role pipelines stay valid).  The table is otherwise treated
-        as frozen (model.py:214-215)."""
+        """The table was written in a way that does not move its version counter (`.data`, a collective, a replayed hipGraph): re-read
+        it into the engine's private copies -- the renumbered / zero-padded copy and the slice-major one -- in place, on the current
+        stream (pointers held by role pipelines and captured graphs stay valid), for this engine and its siblings.  In-place writes
+        that move the version counter (`table[rows] = x`) need no call before a forward; before a REPLAY of a captured graph call this
+        after any table write."""
+        self._sync_table(force=True)
         self._table_sliced_version = None
         if self.layout.total_bytes:
             self._slice_table()
 
     def _model(self, queued=False):
+        self._sync_table()
         if self.layout.total_bytes:          # the layout is known (after the first _reserve)
             self._slice_table()
         w1, w2 = self._weights()
@@ -590,27 +624,37 @@ class RolePipeline:
             raise native.SageError("RolePipeline: an earlier submit failed half-way; synchronise, drop this pipe and create a new one")
 
     def _weights_key(self):
+        """The CALLER's tensors' version counters (not those of the engine's private copies, which only move once they are rebuilt) and
+        the weights epoch: integers, no side effects -- nothing is rewritten before the pipe has been joined."""
         e0 = self.engines[0]
-        w1, w2 = e0._weights()
-        return (w1.data_ptr(), w2.data_ptr(), w1._version, w2._version, e0.table._version)
+        s = e0._shared
+        table = s.src if s.src is not None else e0.table
+        return (e0.w1.data_ptr(), e0.w2.data_ptr(), e0.w1._version, e0.w2._version, table._version, s.weights_epoch)
 
     def _sync_weights(self):
-        """Weights or table written in place since the last submit (version counters): re-prepare the weight planes / refresh the
-        slice-major table copy on the CURRENT stream -- the stream such a write was made on -- and make the role streams wait for it."""
+        """Weights or table written in place since the last submit (version counters): re-prepare the weight planes / re-derive the
+        private table copies on the CURRENT stream -- the stream such a write was made on -- and make the role streams wait for it."""
         key = self._weights_key()
         if key != self._wkey:
-            self.join()                           # batches still in the pipe read the planes / the copy that are about to be rewritten
-            m = self.engines[0]._model()          # re-prepares the weight planes, refreshes the slice-major copy in place: current stream
+            self.join()                           # batches still in the pipe read the planes / the copies that are about to be rewritten
+            m = self.engines[0]._model()          # re-pads / re-prepares the weights, re-derives the table copies in place: current stream
             native.check(native.lib().sage_pipe_update_weights(self._h, m.w1, m.w2, m.w1_prepared), "pipe_update_weights")
             self.fork()                           # the role streams wait for that
             self._wkey = key
 
     def refresh_table(self):
-        """The table was written without moving its version counter (`.data`, a collective): refresh the engine's slice-major copy in
-        place and order the role streams behind it (and behind whatever wrote the table on the current stream)."""
+        """The table was written without moving its version counter (`.data`, a collective): re-read it into the engines' private
+        copies in place and order the role streams behind that (and behind whatever wrote the table on the current stream).  Also the
+        call to make before replaying a graph from capture() after any table write."""
         self.join()
         self.engines[0].refresh_table()
         self.fork()
+
+    def refresh_weights(self):
+        """The weights were written without moving their version counters (`.data`, a collective), or a graph from capture() is to be
+        replayed after any weight update: re-pad / re-prepare them now, in place, with the role streams ordered behind that."""
+        self.engines[0].invalidate_weights()      # moves the weights epoch, which is part of the key
+        self._sync_weights()
 
     def __del__(self):
         h = getattr(self, "_h", None)

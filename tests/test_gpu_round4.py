@@ -7,31 +7,10 @@ from oracle import ref_sparse, sampler_ref
 from sage355 import native, ops
 from sage355.engine import RolePipeline, TwoHopEngine
 from test_gpu_forward import build_modules
-from util import assert_close_rowmax, full_table, load_golden, sets_from_padded
+from util import assert_close_rowmax, full_table, load_golden, sets_from_padded, torch_two_hop
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-
-
-def _torch_two_hop(table, w1, w2, g):
-    """The reference's expression (aggregators.py:54-74, encoders.py:49-62) on the fixture's injected sets, differentiable, fp64."""
-    gcn = bool(g["gcn"])
-    l1 = torch.from_numpy(g["layer1_nodes"])
-    pos = {int(v): i for i, v in enumerate(g["layer1_nodes"])}
-
-    def mean_rows(src, nbr, cnt, index_of):
-        rows = []
-        for r in range(nbr.shape[0]):
-            ids = [index_of(int(x)) for x in nbr[r, :int(cnt[r])]]
-            rows.append(src[ids].mean(0))
-        return torch.stack(rows)
-
-    agg1 = mean_rows(table, g["nbr1"], g["cnt1"], lambda x: x)
-    x1 = agg1 if gcn else torch.cat([table[l1], agg1], 1)
-    h1 = torch.relu(x1 @ w1.t())
-    agg2 = mean_rows(h1, g["nbr2"], g["cnt2"], lambda x: pos[x])
-    x2 = agg2 if gcn else torch.cat([h1[[pos[int(s)] for s in g["seeds"]]], agg2], 1)
-    return torch.relu(x2 @ w2.t())                     # [B, H2]
 
 
 @pytest.mark.parametrize("table_on_device", [True, False])
@@ -58,7 +37,7 @@ def test_trainable_feature_table_gets_its_gradient(name, table_on_device):
     t64 = full_table(g).double().requires_grad_()
     w1 = torch.from_numpy(g["w1"]).double().requires_grad_()
     w2 = torch.from_numpy(g["w2"]).double().requires_grad_()
-    (_torch_two_hop(t64, w1, w2, g) * cot.double().t()).sum().backward()
+    (torch_two_hop(t64, w1, w2, g) * cot.double().t()).sum().backward()
     tg = enc1.features.weight.grad
     assert tg is not None and tg.is_cuda == table_on_device and float(tg.abs().max()) > 0
     for got, want, what in ((tg, t64.grad, "grad_table"), (enc1.weight.grad, w1.grad, "grad_w1"), (enc2.weight.grad, w2.grad, "grad_w2")):

@@ -66,6 +66,48 @@ def sets_from_padded(nodes, nbr, cnt):
     return {int(n): set(int(x) for x in nbr[r, :int(cnt[r])]) for r, n in enumerate(nodes)}
 
 
+def torch_two_hop(table, w1, w2, g):
+    """The reference's expression (aggregators.py:54-74, encoders.py:49-62) on the fixture's injected sets, differentiable, fp64."""
+    gcn = bool(g["gcn"])
+    l1 = torch.from_numpy(g["layer1_nodes"])
+    pos = {int(v): i for i, v in enumerate(g["layer1_nodes"])}
+
+    def mean_rows(src, nbr, cnt, index_of):
+        rows = []
+        for r in range(nbr.shape[0]):
+            ids = [index_of(int(x)) for x in nbr[r, :int(cnt[r])]]
+            rows.append(src[ids].mean(0))
+        return torch.stack(rows)
+
+    agg1 = mean_rows(table, g["nbr1"], g["cnt1"], lambda x: x)
+    x1 = agg1 if gcn else torch.cat([table[l1], agg1], 1)
+    h1 = torch.relu(x1 @ w1.t())
+    agg2 = mean_rows(h1, g["nbr2"], g["cnt2"], lambda x: pos[x])
+    x2 = agg2 if gcn else torch.cat([h1[[pos[int(s)] for s in g["seeds"]]], agg2], 1)
+    return torch.relu(x2 @ w2.t())                     # [B, H2]
+
+
+def oracle_on_engine_sets(eng, table, w1, w2, seeds):
+    """The fp64 oracle (ref_sparse.two_hop_forward) on the sets of `eng`'s LAST forward, read back from its workspace.  table / w1 / w2:
+    the caller's tensors, seeds: the caller's ids.  A relabelled engine's sets hold INTERNAL ids: the table is taken in internal order
+    (table[node_order]) and the seeds are mapped to internal ids; the rows stay in the caller's seed order.  -> [B, H2] float64."""
+    from oracle import ref_sparse
+    it = eng.intermediates()
+    first = it["first_frontier_row"]
+    s1, nbr1, cnt1 = it["s1_nodes"].cpu().numpy(), it["nbr1"].cpu().numpy(), it["cnt1"].cpu().numpy()
+    nbr2, cnt2 = it["nbr2"].cpu().numpy(), it["cnt2"].cpu().numpy()
+    t = table.detach().cpu()
+    seeds = np.asarray(seeds, dtype=np.int64)
+    if eng.node_order is not None:
+        t = t[eng.node_order.cpu()]
+        seeds = eng._new_of_old.cpu().numpy().astype(np.int64)[seeds]
+    if eng.concat:
+        assert np.array_equal(s1[:first], seeds)
+    return ref_sparse.two_hop_forward(t, w1.detach().cpu(), w2.detach().cpu(), seeds, nbr2, cnt2, s1[first:], nbr1[first:], cnt1[first:],
+                                      gcn=not eng.concat, agg_gcn=eng.agg_self_loop, seed_nbr1=nbr1[:first] if eng.concat else None,
+                                      seed_cnt1=cnt1[:first] if eng.concat else None)
+
+
 def assert_close_rowmax(actual, expected, rtol=RTOL, rows_dim=0, what=""):
     """|a-b| <= rtol * max|expected row|; NaNs must coincide."""
     a = torch.as_tensor(np.asarray(actual), dtype=torch.float64)
