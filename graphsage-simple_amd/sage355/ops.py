@@ -201,3 +201,49 @@ def layer_forward(table, nbr, cnt, weight, act=ACT_RELU, concat=False, self_inde
                                          native.stream_handle())
     native.check(rc, "layer_forward")
     return out
+
+
+def csr_mean_workspace_bytes(n, max_edges, dim):
+    """Bytes of the workspace sage_csr_mean needs (host arithmetic; 0 = shape out of range)."""
+    return int(native.lib().sage_csr_mean_workspace_bytes(int(n), int(max_edges), int(dim)))
+
+
+def csr_mean(rowptr, col, table, nodes=None, self_loop=False, any_nonempty=None, out=None, max_edges=None, workspace=None):
+    """aggregators.py:47-48 (num_sample=None) + 52-74 from the CSR: [n, dim] mean over every neighbour of each node
+    (row r is node nodes[r], or node r without `nodes`).  max_edges: upper bound on the edges of the selected rows, default
+    len(col) (exact for distinct rows; a smaller bound only costs speed).  workspace: a uint8 device tensor to reuse."""
+    _need_gpu()
+    _chk(rowptr, torch.int64, "rowptr", 1)
+    _chk(col, torch.int32, "col", 1)
+    table, ld = _row_major(table, "table")
+    num_nodes = rowptr.shape[0] - 1
+    if num_nodes < 0:
+        raise native.SageError("csr_mean: rowptr is empty")
+    if table.shape[0] < max(num_nodes, 1):
+        raise native.SageError(f"csr_mean: table has {table.shape[0]} rows for {num_nodes} nodes")
+    if nodes is not None:
+        _chk(nodes, torch.int32, "nodes", 1)
+    n = num_nodes if nodes is None else nodes.shape[0]
+    dim = table.shape[1]
+    if out is None:
+        out = torch.empty((n, dim), dtype=torch.float32, device=table.device)
+    out, ldo = _row_major(out, "out")
+    if out.shape[0] < n or out.shape[1] != dim:
+        raise native.SageError(f"csr_mean: out is {tuple(out.shape)}, expected ({n}, {dim})")
+    if any_nonempty is not None:
+        _chk(any_nonempty, torch.int32, "any_nonempty")
+    if n == 0:
+        return out
+    if col.numel() == 0:                                  # an empty tensor may have no storage address: the kernels read none of it
+        col = torch.zeros(1, dtype=torch.int32, device=table.device)
+    max_edges = col.numel() if max_edges is None else int(max_edges)
+    need = csr_mean_workspace_bytes(n, max_edges, dim)
+    if need == 0:
+        raise native.SageError(f"csr_mean: n = {n}, max_edges = {max_edges}, dim = {dim} out of range")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=table.device)
+    rc = native.lib().sage_csr_mean(native.ptr(rowptr), native.ptr(col), num_nodes, native.ptr(nodes), n, max_edges,
+                                    native.ptr(table), table.shape[0], ld, dim, 1 if self_loop else 0, native.ptr(any_nonempty),
+                                    native.ptr(out), ldo, native.ptr(workspace), workspace.numel(), native.stream_handle())
+    native.check(rc, "csr_mean")
+    return out

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SAGE_ABI_VERSION 6
+#define SAGE_ABI_VERSION 7
 
 #define SAGE_OK            0
 #define SAGE_EINVAL       -1   /* bad argument (NULL, size, alignment, range) */
@@ -134,6 +134,32 @@ int sage_gather_mean(const float* table, int64_t table_rows, int64_t ld, int32_t
                      const int32_t* slot_rows, const int32_t* self_row,
                      const int32_t* any_nonempty,
                      float* out, int64_t ldo, sage_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * sage_csr_mean (ABI 7) -- aggregators.py:47-48 with num_sample=None (every
+ * neighbour, no sampling), then aggregators.py:52-74, straight from the CSR:
+ *     out[r, :] = mean of table[u, :] over u in col[rowptr[v] .. rowptr[v+1]),
+ *     v = nodes ? nodes[r] : r
+ * self_loop: v's own row joins the mean unless v is already in its row (the
+ * set-union rule of sage_gather_mean's self_row; rows need not be sorted).
+ * An empty row without a self term is NaN if *any_nonempty != 0, else zeros
+ * (zeros when any_nonempty is NULL).  Any dim >= 1, ld >= dim, ldo >= dim.
+ * max_edges bounds the edges of the selected rows (rowptr[num_nodes] does for
+ * distinct rows); it sizes the workspace.  A bound that is too small still
+ * gives the right result, more slowly.  Node ids outside [0, num_nodes) are
+ * empty rows; neighbour ids are clamped into the table.
+ * Load balance: rows longer than SAGE_CSR_MEAN_CHUNK edges are cut into chunks
+ * of that many, summed by separate waves and added in chunk order.  No float
+ * atomics: a row's bits depend only on its CSR entries, the table, self_loop
+ * and the flag, so csr_mean(nodes = S) == csr_mean(all)[S] bit for bit.
+ * ------------------------------------------------------------------------- */
+#define SAGE_CSR_MEAN_CHUNK 512
+size_t sage_csr_mean_workspace_bytes(int32_t n, int64_t max_edges, int32_t dim);
+int sage_csr_mean(const int64_t* rowptr, const int32_t* col, int64_t num_nodes,
+                  const int32_t* nodes /* nullable: row r is node r */, int32_t n, int64_t max_edges,
+                  const float* table, int64_t table_rows, int64_t ld, int32_t dim,
+                  int32_t self_loop, const int32_t* any_nonempty /* nullable */,
+                  float* out, int64_t ldo, void* workspace, size_t workspace_bytes, sage_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * sage_linear_act -- encoders.py:49-62 without materialising the concat:
