@@ -180,8 +180,12 @@ int sage_linear_act(const float* self_tab, int64_t ld_self, const int32_t* self_
  * sage_layer_forward -- one Encoder.forward (encoders.py:47-62) in ONE launch:
  * gather-mean rows are staged through an LDS tile and contracted with W by
  * fp32 MFMA without the [n, dim] round trip through HBM.  Arguments as the two
- * calls above.  SAGE_EUNSUPPORTED if (dim, out_dim) has no fused kernel; the
- * caller then uses the two-launch form.
+ * calls above.  Rows at or past min(*n_dev, n) are not written, nor are the
+ * columns [out_dim, ldo) of out.  Neighbour ids (after slot_rows) and the
+ * concat self_index are clamped into the table.  SAGE_EUNSUPPORTED if
+ * (dim, out_dim) has no fused kernel, if table or weight is not 16-byte
+ * aligned, or if ld or ldw is not a multiple of 4; nothing is launched and
+ * the caller then uses the two-launch form.
  * ------------------------------------------------------------------------- */
 int sage_layer_forward(const float* table, int64_t table_rows, int64_t ld, int32_t dim,
                        const int32_t* nbr, const int32_t* cnt, int32_t k,

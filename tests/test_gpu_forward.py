@@ -145,11 +145,14 @@ def test_strict_path_consumes_python_random_like_the_reference():
 
 
 # ---------------------------------------------------------------- device-sampled sets vs the fp64 oracle
-def check_engine_against_oracle(graph, table, w1, w2, seeds, k1, k2, concat, self_loop, fused, seed=1234):
+def check_engine_against_oracle(graph, table, w1, w2, seeds, k1, k2, concat, self_loop, fused, seed=1234, inspect=None):
+    """inspect(eng), if given, runs after the forward (e.g. to assert which kernel the sizes select)."""
     rowptr, col = torch.from_numpy(graph.rowptr).to(DEV), torch.from_numpy(graph.col).to(DEV)
     eng = TwoHopEngine(rowptr, col, table.to(DEV), w1.to(DEV), w2.to(DEV), k1, k2, concat=concat, agg_self_loop=self_loop,
                        fused=fused, max_batch=len(seeds))
     out = eng.forward(torch.from_numpy(seeds.astype(np.int32)).to(DEV), seed=seed).cpu()
+    if inspect is not None:
+        inspect(eng)
     it = eng.intermediates()
     s1 = it["s1_nodes"].cpu().numpy()
     nbr2, cnt2 = it["nbr2"].cpu().numpy(), it["cnt2"].cpu().numpy()
@@ -230,6 +233,53 @@ def test_two_hop_odd_batches_and_fanouts(b, k1, k2, concat):
     w2 = torch.randn(32, m * 64, generator=gen) / np.sqrt(m * 64)
     seeds = np.random.default_rng(b).choice(np.nonzero(graph.degrees() > 0)[0], b, replace=False)
     check_engine_against_oracle(graph, table, w1, w2, seeds, k1, k2, concat, False, True, seed=5)
+
+
+@pytest.mark.parametrize("concat", [False, True])
+@pytest.mark.parametrize("h1", [64, 100, 200])
+def test_two_hop_layer2_on_a_batch_of_8192_or_more(h1, concat):
+    """Layer 2 runs the one-launch layer on `batch` rows, so only a batch of 8192 or more reaches its large-n kernels:
+    layer_fused_kernel<64 | 128, 64, 4, ...> for h1 = 64 and 100 (100: the padding columns of the KP 128 tile) and
+    <256, 32, 4, ...> for h1 = 200, the only width that runs layer 2 at KP 256.  The gcn encoder adds the self-row union."""
+    graph = rmat_graph(14, 300_000, seed=2)
+    gen = torch.Generator().manual_seed(h1)
+    m = 2 if concat else 1
+    table = torch.randn(graph.num_nodes, 64, generator=gen)
+    w1 = torch.randn(h1, m * 64, generator=gen) / np.sqrt(m * 64)
+    w2 = torch.randn(40, m * h1, generator=gen) / np.sqrt(m * h1)
+    seeds = np.random.default_rng(h1).choice(np.nonzero(graph.degrees() > 0)[0], 8200, replace=False)
+
+    def inspect(eng):
+        it = eng.intermediates()
+        assert it["cnt2"].shape[0] == 8200 >= 8192 and it["h1"].shape[1] == h1 and eng.h1p == h1
+        assert eng._model().fused == 1 and ops.layer_forward_supported(eng.h1p, 40, concat)
+
+    check_engine_against_oracle(graph, table, w1, w2, seeds, 4, 5, concat, not concat, True, seed=h1 + 3, inspect=inspect)
+
+
+@pytest.mark.parametrize("concat", [False, True])
+@pytest.mark.parametrize("d0", [32, 60])
+def test_two_hop_narrow_layer1_takes_the_large_fused_kernel(d0, concat):
+    """Layer 1 below SAGE_SPLIT_MIN_DIM (64) stays one launch, and its kernel is chosen by the workspace's frontier bound
+    max_s1 = B * k2 + B (sage_forward2_layout), not by the live frontier: 512 seeds at fanout 20 bound it at 10752, so
+    layer_fused_kernel<64, 64, 4, true, concat> runs with n_dev (the live frontier) cutting into its row tiles."""
+    graph = rmat_graph(14, 300_000, seed=2)
+    gen = torch.Generator().manual_seed(d0)
+    m = 2 if concat else 1
+    table = torch.randn(graph.num_nodes, d0, generator=gen)
+    w1 = torch.randn(64, m * d0, generator=gen) / np.sqrt(m * d0)
+    w2 = torch.randn(32, m * 64, generator=gen) / np.sqrt(m * 64)
+    seeds = np.random.default_rng(d0).choice(np.nonzero(graph.degrees() > 0)[0], 512, replace=False)
+
+    def inspect(eng):
+        from sage355 import native
+        L = native.WsLayout()
+        native.check(native.lib().sage_forward2_layout(eng._model(), 512, L), "forward2_layout")
+        assert L.max_s1 == 512 * 20 + 512 >= 8192 and L.layer1_split == 0
+        assert eng.d0p == d0 < 64 and ops.layer_forward_supported(d0, 64, concat)
+        assert 0 < eng.intermediates()["n_s1"] < L.max_s1
+
+    check_engine_against_oracle(graph, table, w1, w2, seeds, 10, 20, concat, False, True, seed=d0 + 1, inspect=inspect)
 
 
 @pytest.mark.parametrize("concat,self_loop", [(False, False), (True, False), (False, True)])
