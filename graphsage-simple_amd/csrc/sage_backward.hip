@@ -357,7 +357,7 @@ __global__ __launch_bounds__(256) void gather_mean_bwd_kernel(const float* __res
             } else {
                 id = s;
             }
-            if (id < 0 || id >= table_rows) continue;
+            id = min(max(id, 0), table_rows - 1);            // the forward's clamp: the adjoint of what it computed
             for (int col = lane; col < dim; col += kWave)
                 atomicAdd(&gtab[(int64_t)id * ld + col], gagg[(int64_t)r * ldg + col] * inv);
         }
@@ -496,7 +496,7 @@ __global__ __launch_bounds__(512) void bwd_dw_edges_kernel(const EdgeArgs a) {
                 const int idx = tid + 512 * u;
                 const bool nok = n0b + 4 * (idx & 63) < K1;
                 f32x4 xv = xq[u];
-                if (!nok) xv = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (!nok || term_w[trip * EK_KT + (idx >> 6)] == 0.f) xv = f32x4{0.f, 0.f, 0.f, 0.f};   // padded terms: 0 x NaN
                 *reinterpret_cast<f32x4*>(&xs[buf][idx >> 6][4 * (idx & 63)]) = xv;
             }
         };

@@ -5,8 +5,9 @@
 // eager one to 1e-4 only.
 //
 // Inverted index per call, all on the device, no host synchronisation, everything in the caller's workspace:
-//   1. expand   every (r, j) slot -> key = the table row it points at (or the sentinel `table_rows`: padding, ids out of range,
-//               rows past the live count), value = r; 1 / c_r per row, with the forward's set-union rule for the self row
+//   1. expand   every (r, j) slot -> key = the table row it points at, clamped into the table as the forward does (or the
+//               sentinel `table_rows`: padding, rows past the live count), value = r; 1 / c_r per row, with the forward's
+//               set-union rule for the self row
 //   2. sort     hipcub::DeviceRadixSort::SortPairs on the key bits that matter -- a stable sort, so equal keys keep the slot
 //               order (r ascending, then j)
 //   3. heads    start[t] / end[t] of every key's run in the sorted list
@@ -93,12 +94,12 @@ __global__ __launch_bounds__(256) void det_expand_kernel(const int32_t* __restri
             }
             if (extra && __any(j < c && id == s)) extra = false;     // aggregators.py:50-51: set union (the forward's rule)
             if (j < k) {
-                kr[j] = (j < c && id >= 0 && id < table_rows) ? id : table_rows;
+                kr[j] = j < c ? min(max(id, 0), table_rows - 1) : table_rows;      // clamped into the table, as the forward
                 vr[j] = r;
             }
         }
         if (lane == 0) {
-            kr[k] = (extra && s < table_rows) ? s : table_rows;      // wave-uniform `extra`: every lane saw every ballot
+            kr[k] = extra ? min(s, table_rows - 1) : table_rows;     // wave-uniform `extra`: every lane saw every ballot
             vr[k] = r;
             const int ceff = c + (extra ? 1 : 0);
             inv_c[r] = ceff > 0 ? 1.0f / (float)ceff : 0.f;

@@ -203,13 +203,19 @@ int sage_layer_forward_supported(int32_t dim, int32_t out_dim, int32_t concat);
  * mm / relu / cat / div).
  *
  * sage_linear_act_backward: dZ = grad_out * act'(out);
- *   grad_weight[out_dim, ds+dim] += dZ^T . [self | agg]   (ACCUMULATES: caller zeroes)
+ *   grad_weight[out_dim, ds+dim] += dZ^T . [self | agg]   (ACCUMULATES: caller zeroes; nullable)
  *   grad_x[n, ds+dim]             = dZ . W                 (written; nullable)
+ *   Columns [ds+dim, ldgw) of grad_weight and [ds+dim, ldgx) of grad_x are
+ *   not written.
  * sage_gather_mean_backward: grad_table[row(nbr[r,j]), :] += grad_agg[r, :] / c
  *   (fp32 atomics, caller zeroes grad_table; same slot_rows / self_row rules
- *   as the forward).
+ *   as the forward: neighbour ids (after slot_rows) and the self row are
+ *   clamped into [0, table_rows) exactly as the forward clamps them, the
+ *   set-union test compares the self row before clamping, so c is the
+ *   forward's and the result is the adjoint of sage_gather_mean).
  * ------------------------------------------------------------------------- */
-/* n_dev (nullable): the live row count on the device, min(*n_dev, n) rows take part (rows past it are neither read nor written). */
+/* n_dev (nullable): the live row count on the device, min(*n_dev, n) rows take part (rows past it are neither read nor written:
+ * they add nothing to grad_weight or grad_table, and their rows of grad_x keep what the caller left there). */
 int sage_linear_act_backward(const float* self_tab, int64_t ld_self, const int32_t* self_index,
                              const float* agg, int64_t ld_agg, int32_t dim,
                              const float* weight, int64_t ldw, int32_t out_dim, int32_t act,
@@ -233,8 +239,9 @@ int sage_gather_mean_backward(const float* grad_agg, int64_t ldg, int32_t dim,
  *    straight from HBM in MFMA register order); anything else the generic tile kernel, also through partials.
  *  - sage_gather_mean_backward_ws: an inverted index (expand -> stable radix sort by table row -> run heads) built per call in
  *    the workspace; every table row's terms are then summed in ascending (r, j) order and the row is STORED (zeros where
- *    nobody points): rows [0, min(*table_rows_dev, table_rows)) of grad_table are written, the caller zeroes nothing.
- *    Needs dim % 4 == 0, ld % 4 == 0, 16-byte aligned arrays.
+ *    nobody points): rows [0, min(*table_rows_dev, table_rows)) of grad_table are written, the caller zeroes nothing; rows past
+ *    them and columns [dim, ld) are not.  Ids are clamped as in the legacy form.  Needs dim % 4 == 0, ld % 4 == 0, 16-byte aligned
+ *    arrays; otherwise, and for a short workspace, nothing is launched.
  * The *_workspace_bytes queries are host-side arithmetic (0 = shape out of range / query failed); workspaces 256-byte aligned. */
 size_t sage_linear_act_backward_workspace_bytes(int32_t n, int32_t dim, int32_t has_self, int32_t out_dim);
 int sage_linear_act_backward_ws(const float* self_tab, int64_t ld_self, const int32_t* self_index,
@@ -261,7 +268,9 @@ int sage_row_order(const int32_t* nodes, int32_t n, const int32_t* n_dev, int32_
  * this form no grad_h1 is scattered and the terms come in (seed, slot) order, which does not depend on the frontier's arbitrary row
  * order: bitwise reproducible without an inverted index or a canonical row order (csrc/sage_backward.hip).  grad_x2 is what
  * sage_linear_act_backward(_ws) returned for layer 2; row2 / cnt2 / self_row2 / h1 / agg1 / s1_nodes are the forward's
- * intermediates (sage_ws_layout_t).  Widths and leading dimensions multiples of 4, arrays 16-byte aligned. */
+ * intermediates (sage_ws_layout_t).  Widths and leading dimensions multiples of 4, arrays 16-byte aligned; otherwise, and for a
+ * short workspace, nothing is launched.  Rows of h1 / agg1 / the table that no term references contribute nothing
+ * (a NaN there stays out of grad_w1); columns past d0 (concat: 2*d0) of grad_w1 are not written. */
 size_t sage_two_hop_grad_w1_workspace_bytes(int32_t batch, int32_t k2, int32_t d0, int32_t concat, int32_t h1);
 int sage_two_hop_grad_w1(const float* grad_x2, int64_t ldgx,
                          const int32_t* row2, const int32_t* cnt2, int32_t k2, const int32_t* self_row2, int32_t batch,
