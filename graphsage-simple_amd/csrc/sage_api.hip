@@ -28,6 +28,11 @@ static int env_int(const char* name, int dflt, int lo, int hi) {
     return (int)(x < lo ? lo : x > hi ? hi : x);
 }
 
+// Which form layer 1 takes when both exist (the same-box A/B that decides it)
+#ifndef SAGE_LAYER1_FUSED_DEFAULT
+#define SAGE_LAYER1_FUSED_DEFAULT 1
+#endif
+
 const sage_tunables_t& sage_tunables() {
     static const sage_tunables_t t = [] {
         sage_tunables_t x;
@@ -50,6 +55,8 @@ const sage_tunables_t& sage_tunables() {
         x.tile16_grid = env_int("SAGE_T16_GRID", 2 * kNumCU, 64, 1024);
         x.sample_fused = env_int("SAGE_SAMPLE_FUSED", 0, 0, 1);
         x.tile16_waves = env_int("SAGE_T16_WAVES", 8, 8, 16) >= 16 ? 16 : 8;
+        x.layer1_fused = env_int("SAGE_LAYER1_FUSED", SAGE_LAYER1_FUSED_DEFAULT, 0, 1);
+        x.layer1_phase_per_cu = env_int("SAGE_L1P_PER_CU", 3, 1, 3);
         return x;
     }();
     return t;

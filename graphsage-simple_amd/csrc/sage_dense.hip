@@ -11,6 +11,7 @@
 //     to MFMA 4q+t; LDS rows padded by one ds_read_b128 width.
 #include <atomic>
 #include "sage_internal.h"
+#include "sage_split_bf16.h"
 
 namespace {
 
@@ -218,33 +219,13 @@ extern "C" int sage_debug_dense_select(int launch) {
 #define STAMP_DECL
 #define STAMP(i) do { } while (0)
 #endif
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using bf16x4 = __attribute__((ext_vector_type(4))) __bf16;
+using sage_split_detail::bf16x8;
+using sage_split_detail::bf16x4;
+using sage_split_detail::huge4;
+using sage_split_detail::split3;
+using sage_split_detail::lds_barrier;
+using sage_split_detail::mfma_bf16x3_step;
 using f32x8 = __attribute__((ext_vector_type(8))) float;
-
-// |x| >= 2^127, +-Inf or NaN (exponent field 254 or 255): the three-term split is not exact there -- RNE to bf16 can
-// round the first term up to Inf, and Inf - Inf poisons the remainders -- so a tile (or a weight slice) that holds such a
-// value is recomputed by exact_row_dot below, a plain fp32 fma chain with torch.mm's Inf / NaN behaviour.
-__device__ inline bool huge4(const f32x4 x) {
-    bool h = false;
-#pragma unroll
-    for (int e = 0; e < 4; ++e) h |= (__float_as_uint(x[e]) & 0x7F800000u) >= 0x7F000000u;
-    return h;
-}
-
-__device__ inline void split3(const f32x4 x, bf16x4& hi, bf16x4& mid, bf16x4& lo) {
-    hi = __builtin_convertvector(x, bf16x4);
-    const f32x4 r1 = x - __builtin_convertvector(hi, f32x4);
-    mid = __builtin_convertvector(r1, bf16x4);
-    const f32x4 r2 = r1 - __builtin_convertvector(mid, f32x4);
-    lo = __builtin_convertvector(r2, bf16x4);
-}
-
-// Block barrier for data exchanged through LDS only.  __syncthreads() carries a workgroup-scope fence, and on gfx9 a release
-// fence is `s_waitcnt vmcnt(0)`: it DRAINS every global load in flight -- the W slice (24 KiB per wave) requested in the
-// prologue, the next tile's rows requested before the MFMA loop -- at each of the two barriers per tile.  Here only the LDS
-// queue is waited for; the compiler still waits for a load where its value is used.
-__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 // out[g][col] before the activation as an fp32 fma chain over k (the [self | agg] order of encoders.py:54): the slow, exact
 // form for tiles that hold |x| >= 2^127 / Inf / NaN (never taken on ordinary data: one LDS word per tile decides)
@@ -516,12 +497,7 @@ __global__ __launch_bounds__(512) void dense_bf16x3_kernel(const DenseArgs a) {
                             const bf16x8 ah = *reinterpret_cast<const bf16x8*>(abase + 16 * st);
                             const bf16x8 am = *reinterpret_cast<const bf16x8*>(abase + PL + 16 * st);
                             const bf16x8 al = *reinterpret_cast<const bf16x8*>(abase + 2 * PL + 16 * st);
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(al, bw[st][0], acc[t], 0, 0, 0);
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bw[st][2], acc[t], 0, 0, 0);
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bw[st][1], acc[t], 0, 0, 0);
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(am, bw[st][0], acc[t], 0, 0, 0);
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bw[st][1], acc[t], 0, 0, 0);
-                            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(ah, bw[st][0], acc[t], 0, 0, 0);
+                            acc[t] = mfma_bf16x3_step(ah, am, al, bw[st], acc[t]);
                         }
                     }
                     STAMP(stamp_i); ++stamp_i;

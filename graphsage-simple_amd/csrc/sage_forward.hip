@@ -82,6 +82,26 @@ namespace {
         }                                                                                  \
     } while (0)
 
+// Which launches layer 1 is made of (a function of the model and the layout only, so every call on a workspace -- and the role pipeline,
+// which must know whether its D stage launches anything -- agrees)
+struct layer1_form_t {
+    bool split1;          // wide + large layer 1: column-sliced gather (cross-XCD L2 partitioning) into agg1, then a dense contraction
+    bool gather_only1;    // serving on a pre-transformed table (sage_model_t.w1_is_identity): the split layer's gather applies act1 and writes h1
+    bool phase1;          // the split layer 1 as ONE phase-sliced launch (sage_layer1_phase.hip; bit-identical h1): gcn encoder, slice-major table of
+                          // 32-float slices, prepared W1, and nobody needs the means (sage_model_t.keep_means: the backward reads agg1)
+};
+layer1_form_t layer1_form(const sage_model_t* m, const sage_ws_layout_t& L, const float* agg1, const float* h1) {
+    layer1_form_t f;
+    f.split1 = m->fused && L.layer1_split && sage_aligned(m->table, 16) && sage_aligned(m->w1, 16) &&
+               sage_gather_is_sliced(m->d0, m->table_ld, m->d0, m->table, agg1, L.max_s1, m->k1);
+    f.gather_only1 = f.split1 && m->w1_is_identity != 0 && !m->concat && m->d0 == m->h1 &&
+                     sage_gather_is_sliced(m->d0, m->table_ld, m->h1, m->table, h1, L.max_s1, m->k1);
+    f.phase1 = f.split1 && !f.gather_only1 && !m->concat && !m->keep_means && sage_tunables().layer1_fused != 0 &&
+               m->table_sliced != nullptr && m->table_slice_floats == 32 && sage_aligned(m->table_sliced, 16) &&
+               m->w1_prepared != nullptr && sage_layer1_phase_supported(m->d0, m->h1, m->k1);
+    return f;
+}
+
 int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes, const int32_t* seeds, int32_t batch,
                   uint64_t seed, float* out, int64_t ldo, sage_stream_t stream, void* const* ev, int stages = SAGE_STAGE_ALL,
                   int cursor_off = 0, bool key_in_ws = false, void* tail_event = nullptr) {
@@ -150,10 +170,10 @@ int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes
     const int32_t* nan2 = m->nan_empty ? (self_loop ? any2 : s1_count) : nullptr;
     const bool fuse1 = m->fused && sage_layer_fused_supported(m->d0, m->h1, m->concat) && m->table_ld % 4 == 0 &&
                        sage_aligned(m->table, 16) && sage_aligned(m->w1, 16);
-    // wide + large layer 1: column-sliced gather (cross-XCD L2 partitioning) into agg1, then a dense contraction;
+    // wide + large layer 1: column-sliced gather into agg1, then a dense contraction (or both in one phase-sliced launch);
     // otherwise the one-launch fused layer; otherwise the generic two-launch form
-    const bool split1 = m->fused && L.layer1_split && sage_aligned(m->table, 16) && sage_aligned(m->w1, 16) &&
-                        sage_gather_is_sliced(m->d0, m->table_ld, m->d0, m->table, agg1, L.max_s1, m->k1);
+    const layer1_form_t form1 = layer1_form(m, L, agg1, h1);
+    const bool split1 = form1.split1, gather_only1 = form1.gather_only1, phase1 = form1.phase1;
     uint64_t* key_slot = key_in_ws ? (uint64_t*)(counters + 16) : nullptr;    // in the 256-B slot of the counters, past the 16 ints in use
     // Layer 2 as a one-launch layer resolves hash slots itself, so both hops can be sampled by ONE launch (sage_sample.hip:
     // sample_fused_kernel).  The choice depends on the model only, so every call on a workspace agrees on who resolves the slots.
@@ -200,9 +220,6 @@ int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes
     if (int rc = settle(SAGE_STAGE_SAMPLE_INNER)) return rc;
     SAGE_EV(3);
     }
-    // serving on a pre-transformed table (sage_model_t.w1_is_identity): the split layer's gather applies act1 and writes h1; no contraction
-    const bool gather_only1 = split1 && m->w1_is_identity != 0 && !m->concat && m->d0 == m->h1 &&
-                              sage_gather_is_sliced(m->d0, m->table_ld, m->h1, m->table, h1, L.max_s1, m->k1);
     // 3. layer 1 on S1: the HBM-bound gather ...
     if (stages & SAGE_STAGE_GATHER1) {
     // (sage_forward2_profiled: events 4 / 5 are the gather launch's own start / stop events when it takes a column-sliced form)
@@ -217,6 +234,11 @@ int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes
         if (int rc = sage_launch_gather_mean(sm ? m->table_sliced : m->table, m->num_nodes, sm ? sw : m->table_ld, m->d0, nbr1, cnt1, m->k1, L.max_s1,
                                              s1_count, nullptr, self_loop ? s1_nodes : nullptr, nan1, h1, m->h1, first_row, st,
                                              sm ? m->num_nodes * (int64_t)sw : 0, m->act1))
+            return rc;
+    } else if (phase1) {
+        if (int rc = sage_launch_layer1_phase(m->table_sliced, m->num_nodes, m->d0, nbr1, cnt1, m->k1, L.max_s1, s1_count,
+                                              self_loop ? s1_nodes : nullptr, nan1, m->w1, ldw1, m->w1_prepared, m->h1, m->act1, h1, m->h1,
+                                              first_row, st))
             return rc;
     } else if (split1) {
         // optional slice-major copy of the table ([d0 / 64][num_nodes][64]): every XCD pair reads ONE contiguous array
@@ -233,8 +255,8 @@ int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes
     // ... and its contraction (one launch with the gather unless the layer is split); then layer 2
     if (stages & SAGE_STAGE_CONTRACT1) {
     SAGE_EV(6);
-    if (gather_only1) {
-        // nothing: the gather wrote h1
+    if (gather_only1 || phase1) {
+        // nothing: the gather stage wrote h1
     } else if (split1) {
         arm(SAGE_STAGE_CONTRACT1);
         if (int rc = sage_launch_layer_dense(agg1, m->d0, m->d0, L.max_s1, s1_count, m->concat, m->table, m->table_ld, m->num_nodes,
@@ -292,6 +314,15 @@ int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes
 extern "C" int sage_forward2(const sage_model_t* m, void* workspace, size_t workspace_bytes, const int32_t* seeds, int32_t batch,
                              uint64_t seed, float* out, int64_t ldo, sage_stream_t stream) {
     return forward2_impl(m, workspace, workspace_bytes, seeds, batch, seed, out, ldo, stream, nullptr);
+}
+
+// SAGE_STAGE_CONTRACT1 launches nothing for this model (the gather stage writes h1): the role pipeline then skips stage D's hand-off
+bool sage_forward2_contract1_is_empty(const sage_model_t* m, int32_t batch) {
+    sage_ws_layout_t L;
+    if (check_model(m) != SAGE_OK || sage_forward2_layout(m, m->ws_batch ? m->ws_batch : batch, &L) != SAGE_OK) return false;
+    const float* aligned = reinterpret_cast<const float*>(uintptr_t{256});      // workspace arrays are 256-byte aligned (forward2_impl requires it)
+    const layer1_form_t f = layer1_form(m, L, aligned, aligned);
+    return f.gather_only1 || f.phase1;
 }
 
 // A subset of the forward's launches with the seeds and the sampler key taken from the call (sage_pipe.hip: one call per role stream)

@@ -227,6 +227,54 @@ __device__ __forceinline__ void gather_sliced_block_pipelined(
 // registers and stores them: no cross-lane traffic at all, ~10x fewer instructions per unit, and TRIP neighbours of every
 // row (64/SL x TRIP KiB per wave) in flight at once, so a few waves per CU cover the fabric's latency.
 // Summation order: neighbours in list order, one fp32 add per neighbour (as the reference's mask.mm row sum does per column).
+// One (destination row, slice) unit of the rows form below: the sum of the row's neighbour slices in list order (+ the self row
+// unless it is among them) and its mean, for the lane that owns 4 of the slice's columns.  Shared with the phase-sliced layer 1
+// (sage_layer1_phase.hip), which keeps the mean on the chip; `myn` = the row's k neighbour ids (global memory or LDS).
+// No branch and no wait inside a trip: every id load and every row load is unconditional -- slots past the
+// list's end re-read the list's LAST row (an L1 hit, nothing leaves the CU) and get weight 0 -- so all TRIP
+// rows of all 64/SL destinations are in flight together.  (A predicated form compiled to one exec branch and one
+// s_waitcnt vmcnt(0) PER LOAD: 54 us at 4 blocks per CU.)
+using gather_v4 = __attribute__((ext_vector_type(4))) float;
+template <int TRIP, bool SLOT>
+__device__ __forceinline__ gather_v4 gather_rows_unit_sum(const float* __restrict__ tcol, const int64_t ld, const int32_t* __restrict__ myn,
+                                                          const int c, const int k, const int s, const int last_row,
+                                                          const int32_t* __restrict__ slot_rows, bool& extra) {
+    using V = gather_v4;
+    V acc = {0.f, 0.f, 0.f, 0.f};
+    for (int j0 = 0; j0 < k; j0 += TRIP) {                      // wave-uniform bounds; one trip when k <= TRIP
+        int id[TRIP];
+#pragma unroll
+        for (int u = 0; u < TRIP; ++u) id[u] = myn[min(min(j0 + u, c - 1), k - 1) < 0 ? 0 : min(min(j0 + u, c - 1), k - 1)];
+        V t[TRIP];
+#pragma unroll
+        for (int u = 0; u < TRIP; ++u) {
+            int x = id[u];
+            if (SLOT) x = slot_rows[max(x, 0)];
+            extra = extra && !(j0 + u < c && x == s);           // aggregators.py:50-51: set union
+            x = min(max(x, 0), last_row);
+            t[u] = *reinterpret_cast<const V*>(tcol + (int64_t)x * ld);
+        }
+#pragma unroll
+        for (int u = 0; u < TRIP; ++u) {
+            // select, not multiply: a slot past the end may hold Inf / NaN of a row that is not in the set
+            acc[0] += (j0 + u < c) ? t[u][0] : 0.f; acc[1] += (j0 + u < c) ? t[u][1] : 0.f;
+            acc[2] += (j0 + u < c) ? t[u][2] : 0.f; acc[3] += (j0 + u < c) ? t[u][3] : 0.f;
+        }
+    }
+    if (extra) {
+        const V sv = *reinterpret_cast<const V*>(tcol + (int64_t)min(s, last_row) * ld);
+        acc += sv;
+    }
+    return acc;
+}
+// the mean of a unit, with the empty-set rule (NaN inside a batch that has non-empty sets, zeros otherwise)
+__device__ __forceinline__ gather_v4 gather_rows_unit_mean(const gather_v4 acc, const int c, const bool extra, const bool nan_rule) {
+    const int ceff = c + (extra ? 1 : 0);
+    if (ceff > 0) return acc * (1.0f / (float)ceff);
+    const float fill = nan_rule ? __builtin_nanf("") : 0.f;
+    return gather_v4{fill, fill, fill, fill};
+}
+
 template <int SL, int TRIP, bool SLOT>
 __device__ __forceinline__ void gather_sliced_block_rows(
     const float* __restrict__ table, int table_rows, int64_t ld, int dim,
@@ -260,42 +308,9 @@ __device__ __forceinline__ void gather_sliced_block_rows(
         }
         bool extra = s >= 0;
         const int32_t* __restrict__ myn = nbr + (int64_t)rq * k;
-        V acc = {0.f, 0.f, 0.f, 0.f};
-        // No branch and no wait inside a trip: every id load and every row load is unconditional -- slots past the
-        // list's end re-read the list's LAST row (an L1 hit, nothing leaves the CU) and get weight 0 -- so all TRIP
-        // rows of all 64/SL destinations are in flight together.  (A predicated form compiled to one exec branch and one
-        // s_waitcnt vmcnt(0) PER LOAD: 54 us at 4 blocks per CU.)
-        for (int j0 = 0; j0 < k; j0 += TRIP) {                      // wave-uniform bounds; one trip when k <= TRIP
-            int id[TRIP];
-#pragma unroll
-            for (int u = 0; u < TRIP; ++u) id[u] = myn[min(min(j0 + u, c - 1), k - 1) < 0 ? 0 : min(min(j0 + u, c - 1), k - 1)];
-            V t[TRIP];
-#pragma unroll
-            for (int u = 0; u < TRIP; ++u) {
-                int x = id[u];
-                if (SLOT) x = slot_rows[max(x, 0)];
-                extra = extra && !(j0 + u < c && x == s);           // aggregators.py:50-51: set union
-                x = min(max(x, 0), last_row);
-                t[u] = *reinterpret_cast<const V*>(tcol + (int64_t)x * ld);
-            }
-#pragma unroll
-            for (int u = 0; u < TRIP; ++u) {
-                const float w = (j0 + u < c) ? 1.f : 0.f;
-                // select, not multiply: a slot past the end may hold Inf / NaN of a row that is not in the set
-                acc[0] += (j0 + u < c) ? t[u][0] : 0.f; acc[1] += (j0 + u < c) ? t[u][1] : 0.f;
-                acc[2] += (j0 + u < c) ? t[u][2] : 0.f; acc[3] += (j0 + u < c) ? t[u][3] : 0.f;
-                (void)w;
-            }
-        }
-        if (extra) {
-            const V sv = *reinterpret_cast<const V*>(tcol + (int64_t)min(s, last_row) * ld);
-            acc += sv;
-        }
+        const V acc = gather_rows_unit_sum<TRIP, SLOT>(tcol, ld, myn, c, k, s, last_row, slot_rows, extra);
         if (valid && ok) {
-            const int ceff = c + (extra ? 1 : 0);
-            V res;
-            if (ceff > 0) res = acc * (1.0f / (float)ceff);
-            else { const float fill = nan_rule ? __builtin_nanf("") : 0.f; res = V{fill, fill, fill, fill}; }
+            V res = gather_rows_unit_mean(acc, c, extra, nan_rule);
             if (act != SAGE_ACT_NONE) { res[0] = sage_activate(res[0], act); res[1] = sage_activate(res[1], act); res[2] = sage_activate(res[2], act); res[3] = sage_activate(res[3], act); }
             sage_store_stream<SAGE_AGG_STORE>(reinterpret_cast<V*>(out + (int64_t)r * ldo + c0), res);
         }

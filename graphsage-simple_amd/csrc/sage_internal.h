@@ -61,6 +61,14 @@ int sage_launch_layer_dense(const float* agg, int64_t ld_agg, int32_t dim, int32
                             const float* weight, int64_t ldw, int32_t out_dim, int32_t act, float* out, int64_t ldo, int32_t n_off,
                             sage_finish_t fin, const void* weight_prepared, hipStream_t st);
 
+// Phase-sliced layer 1 (sage_layer1_phase.hip): gather + contraction of the gcn encoder's layer 1 in one launch on the slice-major table
+// of 32-float slices, bit-identical to sage_launch_gather_mean + sage_launch_layer_dense.  SAGE_EUNSUPPORTED when the shape has no kernel.
+bool sage_layer1_phase_supported(int32_t d0, int32_t h1, int32_t k);
+int sage_launch_layer1_phase(const float* table_sliced, int64_t table_rows, int32_t d0, const int32_t* nbr, const int32_t* cnt, int32_t k,
+                             int32_t n, const int32_t* n_dev, const int32_t* self_row, const int32_t* any_nonempty, const float* weight,
+                             int64_t ldw, const void* weight_prepared, int32_t out_dim, int32_t act, float* out, int64_t ldo, int32_t n_off,
+                             hipStream_t st);
+
 // Measurement hook (sage_gather.hip): set by the thread that is about to launch the layer-1 gather, cleared right after.
 struct sage_ext_launch_t { void* start; void* stop; };
 extern thread_local const sage_ext_launch_t* sage_ext_launch;
@@ -96,6 +104,8 @@ extern thread_local void* sage_tail_event;
 int sage_forward2_launch_stages(const sage_model_t* m, void* workspace, size_t workspace_bytes, const int32_t* seeds, int32_t batch,
                                 uint64_t seed, float* out, int64_t ldo, int32_t stages, hipStream_t stream, void* tail_event = nullptr);
 
+bool sage_forward2_contract1_is_empty(const sage_model_t* m, int32_t batch);
+
 // Launch-shape tunables, read ONCE from the environment (A/B runs on one box without rebuilding; defaults are the
 // measured optima recorded in DESIGN.md).  Every value is clamped to a safe range.
 struct sage_tunables_t {
@@ -114,6 +124,9 @@ struct sage_tunables_t {
                                   //                      (measured: 24.3 us fused vs 10.3 + 11.4: the inner hop of a block's own winners is
                                   //                      three dependent rounds on 128-256 blocks instead of one round on 1500; pipeline 66.8 vs 66.2 us)
     int tile16_waves;             // SAGE_T16_WAVES       layer-2 tile16 kernel: 16 (1024-thread blocks) or 8 (512-thread blocks, default: 1.5 us per forward in the pipeline)
+    int layer1_fused;             // SAGE_LAYER1_FUSED    1: layer 1 as ONE phase-sliced launch where its conditions hold and nobody needs the means
+                                  //                      (sage_layer1_phase.hip); 0: always gather + contraction.  Default: see sage_api.hip
+    int layer1_phase_per_cu;      // SAGE_L1P_PER_CU      phase-sliced layer 1: persistent 256-thread blocks per CU (1..3), default 3
 };
 // n_words 32-bit words := v, as a kernel (hipMemsetAsync misbehaves inside replayed hipGraphs on ROCm 7.2: sage_api.hip)
 int sage_fill_u32(void* p, uint32_t v, size_t n_words, hipStream_t st);

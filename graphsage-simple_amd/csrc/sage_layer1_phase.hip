@@ -1,0 +1,245 @@
+// Layer 1 of the gcn encoder in ONE launch on the slice-major table, phase-sliced:
+//     h1[r] = act1( mean_j table[nbr1[r, j]] . W1^T )
+// without the [|S1|, D0] means ever leaving the chip (the split form writes them with the column-sliced gather and reads them back in
+// the contraction: two launches, 24 MB out and 24 MB in at BASELINE config 3).
+//
+// What the split form's gather owes its speed to is that an XCD's private L2 holds ONE 128-byte slice of the hot rows.  The one-launch
+// layers of sage_fused.hip gather whole rows and lose that.  Here the slicing is kept in TIME instead of in space:
+//   * a block owns TILES of 32 destination rows (tile t goes to block t mod grid; the grid is a multiple of 8, blocks are dealt round
+//     robin over the 8 XCDs, so XCD x owns the tiles of class x: an eighth of the rows whatever the device-side row count is);
+//   * it walks the D0 / 32 slices of the table in PHASES.  In a phase it gathers slice p of its 32 rows exactly as the rows form of the
+//     sliced gather does (sage_gather_body.h: lane group of 8 lanes x 16 B per (row, slice), every neighbour in flight, sum in list
+//     order), so at any time an XCD's L2 is asked for one slice of an eighth of the rows;
+//   * the 32 x 32 slice means go to LDS as the three bf16 planes of the exact split (sage_split_bf16.h) and are contracted with the
+//     phase's 32 columns of the prepared W1 planes (sage_prepare_weights' register order, 24 KiB per phase, L2-resident) by six
+//     v_mfma_f32_32x32x16_bf16 per 16 k.  The accumulators of the tile (32 rows x H1, wave w = columns [32 w, 32 w + 32)) stay in
+//     registers over all phases: K is split in time, there are no partial sums in memory.
+// Bits.  Every phase order and every accumulator is that of the split form: slices in ascending order for every block (NOT rotated by
+// XCD: a row's bits must not depend on the tile, block or XCD it lands on, and fp32 accumulation is order dependent), K half 0 (the
+// first half of the slices) and K half 1 in two accumulators of the same wave that meet as half 0 + half 1, the MFMA order of
+// dense_bf16x3_kernel inside a step, the gather's sums in list order.  The result equals gather + contraction BIT FOR BIT
+// (tests/test_gpu_layer1_fused.py), so the two forms can be mixed freely (training keeps the means, serving does not).
+// Rows that hold |x| >= 2^127 / Inf / NaN in their means (the empty-set NaN rule included), or every row when W1 holds one, are
+// recomputed by the exact fp32 fma chain of the contraction's cold path, from the table.
+// Latency: 3 blocks of 4 waves per CU take turns -- while one contracts and stages, the others have their 16 x 1 KiB per wave in flight.
+#include <hip/hip_ext.h>
+
+#include "sage_gather_body.h"
+#include "sage_split_bf16.h"
+
+namespace {
+
+using namespace sage_split_detail;
+using sage_gather_detail::gather_rows_unit_mean;
+using sage_gather_detail::gather_rows_unit_sum;
+using sage_gather_detail::gather_v4;
+
+struct PhaseArgs {
+    const float* table; int table_rows; int64_t slice_stride;     // slice-major: float[D0 / 32][table_rows][32]
+    const int32_t* nbr; const int32_t* cnt; int k;
+    int n; const int32_t* n_dev; int n_off;
+    const int32_t* self_row; const int32_t* any_nonempty;
+    const float* W; int64_t ldw; const uint4* wsplit; int out_dim; int act;
+    float* out; int64_t ldo;
+};
+
+constexpr int kTileRows = 32;         // destination rows per tile = per MFMA
+constexpr int kSliceFloats = 32;      // 128-byte slices: 8 lanes x 16 B
+constexpr int kMaxK = SAGE_MAX_FANOUT;
+
+// the mean of column kk of row `lr` of the tile, as the vector path computes it (same terms, same order)
+__device__ inline float exact_mean(const PhaseArgs& a, const int32_t* ids, int c, int s, bool extra, bool nan_rule, int kk) {
+    const int last_row = a.table_rows - 1;
+    const float* col = a.table + (int64_t)(kk / kSliceFloats) * a.slice_stride + (kk % kSliceFloats);
+    float sum = 0.f;
+    for (int j = 0; j < c; ++j) sum += col[(int64_t)min(max(ids[j], 0), last_row) * kSliceFloats];
+    if (extra) sum += col[(int64_t)min(s, last_row) * kSliceFloats];
+    const int ceff = c + (extra ? 1 : 0);
+    if (ceff > 0) return sum * (1.0f / (float)ceff);
+    return nan_rule ? __builtin_nanf("") : 0.f;
+}
+
+template <int NSLICE>
+__global__ __launch_bounds__(256, 3) void layer1_phase_kernel(const PhaseArgs a) {
+    constexpr int M = kTileRows, SL = 8, TRIP = 16;
+    constexpr int LDB = kSliceFloats + 8;                 // bf16 elements per LDS row of a plane (+16 B)
+    constexpr int PL = M * LDB;
+    constexpr int PLD = 128 + 4;                          // floats per row of the output tile
+    constexpr int STEPS = NSLICE;                         // 16-k steps per K half of the prepared planes (KP = 32 NSLICE)
+    __shared__ __attribute__((aligned(16))) __bf16 planes[2 * 3 * PL];
+    __shared__ __attribute__((aligned(16))) float outp[M * PLD];
+    __shared__ int32_t ids[M * kMaxK];
+    __shared__ int32_t cnts[M], selfs[M];
+    __shared__ int rowflag[M];                            // the row's means hold a huge value (this tile)
+    __shared__ int tileflag;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    int nn = a.n;
+    if (a.n_dev) nn = min(*a.n_dev + a.n_off, a.n);
+    const int ntiles = (nn + M - 1) / M;
+    const bool nan_rule = a.any_nonempty ? (*a.any_nonempty != 0) : false;
+    const int last_row = a.table_rows - 1;
+    const int grp = lane / SL, gl = lane % SL;
+    const int lr = wave * (kWave / SL) + grp;             // the tile row whose slices this lane group gathers
+    const int i32 = lane & 31, h = lane >> 5;
+    const int n0 = wave * 32;
+    const bool mfma_wave = n0 < a.out_dim;
+    const int k = a.k;
+    const bool w_huge = a.wsplit[(size_t)8 * STEPS * 3 * 64].x != 0;     // the trailer sage_prepare_weights leaves behind the planes
+
+    for (int tile = (int)blockIdx.x; tile < ntiles; tile += (int)gridDim.x) {
+        __syncthreads();                                  // the previous tile's ids / flags / output tile have been read
+        for (int i = tid; i < M * k; i += 256) {
+            const int rq = min(tile * M + i / k, nn - 1); // rows past the end shadow the last row (nothing of theirs is stored)
+            ids[i] = a.nbr[(int64_t)rq * k + i % k];
+        }
+        if (tid < M) {
+            const int rq = min(tile * M + tid, nn - 1);
+            cnts[tid] = min(a.cnt[rq], k);
+            selfs[tid] = a.self_row ? a.self_row[rq] : -1;
+            rowflag[tid] = 0;
+        }
+        if (tid == 0) tileflag = w_huge ? 1 : 0;
+        __syncthreads();
+        const bool valid = tile * M + lr < nn;
+        const int c = cnts[lr], s = selfs[lr];
+        const int32_t* myn = ids + lr * k;
+
+        f32x16 acc[2];                                    // K half 0 / K half 1, as the two wave groups of dense_bf16x3_kernel
+#pragma unroll
+        for (int e = 0; e < 16; ++e) { acc[0][e] = 0.f; acc[1][e] = 0.f; }
+#pragma unroll
+        for (int kg = 0; kg < 2; ++kg) {
+#pragma unroll 1
+            for (int q = 0; q < NSLICE / 2; ++q) {
+                const int p = kg * (NSLICE / 2) + q;      // the phase = the slice
+                const float* tcol = a.table + (int64_t)p * a.slice_stride + gl * 4;
+                bool extra = s >= 0;
+                const gather_v4 sum = gather_rows_unit_sum<TRIP, false>(tcol, kSliceFloats, myn, c, k, s, last_row, nullptr, extra);
+                // this phase's W1 planes: [K half][column group = wave][step][plane][lane] x 16 B; requested once the
+                // rows have arrived (their 24 registers beside the 64 of the rows in flight spill), in flight while the means are staged
+                bf16x8 bw[2][3];
+                {
+                    const uint4* wp = a.wsplit + ((size_t)(kg * 4 + __builtin_amdgcn_readfirstlane(wave)) * STEPS + 2 * q) * 3 * 64;
+#pragma unroll
+                    for (int j = 0; j < 2; ++j)
+#pragma unroll
+                        for (int pl = 0; pl < 3; ++pl) bw[j][pl] = __builtin_bit_cast(bf16x8, wp[(j * 3 + pl) * 64 + lane]);
+                }
+                gather_v4 res = gather_rows_unit_mean(sum, c, extra, nan_rule);
+                if (!valid) res = gather_v4{0.f, 0.f, 0.f, 0.f};
+                if (huge4(res)) { rowflag[lr] = 1; tileflag = 1; }       // same value from every writer
+                __bf16* buf = planes + (p & 1) * 3 * PL;
+                {
+                    bf16x4 hi, mid, lo;
+                    split3(res, hi, mid, lo);
+                    __bf16* dst = buf + lr * LDB + gl * 4;
+                    *reinterpret_cast<bf16x4*>(dst) = hi;
+                    *reinterpret_cast<bf16x4*>(dst + PL) = mid;
+                    *reinterpret_cast<bf16x4*>(dst + 2 * PL) = lo;
+                }
+                // one barrier per phase: the planes are double-buffered, and a wave reaches the next phase's barrier only after its
+                // MFMAs of this one
+                lds_barrier();
+                if (mfma_wave) {
+                    const __bf16* abase = buf + i32 * LDB + 8 * h;
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const bf16x8 ah = *reinterpret_cast<const bf16x8*>(abase + 16 * j);
+                        const bf16x8 am = *reinterpret_cast<const bf16x8*>(abase + PL + 16 * j);
+                        const bf16x8 al = *reinterpret_cast<const bf16x8*>(abase + 2 * PL + 16 * j);
+                        acc[kg] = mfma_bf16x3_step(ah, am, al, bw[j], acc[kg]);
+                    }
+                }
+            }
+        }
+        // epilogue: half 0 + half 1 -> [row][column] tile in LDS -> activation -> whole 512-B rows, streaming stores
+        if (mfma_wave) {
+            float* mine = outp + n0 + i32;
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) mine[((reg & 3) + 8 * (reg >> 2) + 4 * h) * PLD] = acc[0][reg] + acc[1][reg];
+        }
+        lds_barrier();
+        const bool any_bad = tileflag != 0;
+#pragma unroll
+        for (int it = 0; it < M * 32 / 256; ++it) {
+            const int idx = it * 256 + tid;
+            const int row = idx >> 5, col = (idx & 31) * 4;
+            const int g = tile * M + row;
+            if (g < nn && col < a.out_dim && !(any_bad && (w_huge || rowflag[row] != 0))) {      // out_dim % 32 == 0 (host-checked)
+                const f32x4 pv = *reinterpret_cast<const f32x4*>(outp + row * PLD + col);
+                f32x4 v;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] = sage_activate(pv[e], a.act);
+                sage_store_stream<SAGE_H1_STORE>(reinterpret_cast<f32x4*>(a.out + (int64_t)g * a.ldo + col), v);
+            }
+        }
+        // rows with a huge value (all rows when W1 holds one): the exact fp32 fma chain over k, torch.mm's Inf / NaN behaviour.
+        // Block-uniform; never taken on ordinary data.
+        if (any_bad) {
+            const int d0 = NSLICE * kSliceFloats;
+            for (int idx = tid; idx < M * a.out_dim; idx += 256) {
+                const int row = idx / a.out_dim, col = idx % a.out_dim;
+                const int g = tile * M + row;
+                if (g >= nn || !(w_huge || rowflag[row] != 0)) continue;
+                const int32_t* rid = ids + row * k;
+                const int rc = cnts[row], rs = selfs[row];
+                bool rextra = rs >= 0;
+                for (int j = 0; j < rc; ++j) rextra = rextra && rid[j] != rs;
+                const float* wrow = a.W + (int64_t)col * a.ldw;
+                float dot = 0.f;
+                for (int kk = 0; kk < d0; ++kk) dot = fmaf(exact_mean(a, rid, rc, rs, rextra, nan_rule, kk), wrow[kk], dot);
+                a.out[(int64_t)g * a.ldo + col] = sage_activate(dot, a.act);
+            }
+        }
+    }
+}
+
+template <int NSLICE>
+int launch_phase(const PhaseArgs& a, hipStream_t st) {
+    // persistent blocks, 3 per CU, a multiple of 8 so that a tile's class (tile mod 8) is its XCD
+    const int per_cu = sage_tunables().layer1_phase_per_cu;
+    const int grid = min((sage_cdiv(a.n, kTileRows) + 7) / 8 * 8, kNumCU * per_cu);
+    if (const sage_ext_launch_t* x = sage_ext_launch)     // measurement hook: the launch's own start / stop events (sage_gather.hip)
+        hipExtLaunchKernelGGL((layer1_phase_kernel<NSLICE>), dim3(grid), dim3(256), 0, st, (hipEvent_t)x->start, (hipEvent_t)x->stop, 0u, a);
+    else
+        SAGE_LAUNCH_TAIL((layer1_phase_kernel<NSLICE>), dim3(grid), dim3(256), 0, st, a);
+    SAGE_CHECK_LAUNCH("layer1_phase_kernel");
+    return SAGE_OK;
+}
+
+}  // namespace
+
+bool sage_layer1_phase_supported(int32_t d0, int32_t h1, int32_t k) {
+    return (d0 == 64 || d0 == 128 || d0 == 256) && h1 >= 32 && h1 <= 128 && h1 % 32 == 0 && k >= 1 && k <= kMaxK;
+}
+
+int sage_launch_layer1_phase(const float* table_sliced, int64_t table_rows, int32_t d0, const int32_t* nbr, const int32_t* cnt, int32_t k,
+                             int32_t n, const int32_t* n_dev, const int32_t* self_row, const int32_t* any_nonempty, const float* weight,
+                             int64_t ldw, const void* weight_prepared, int32_t out_dim, int32_t act, float* out, int64_t ldo, int32_t n_off,
+                             hipStream_t st) {
+    if (!sage_layer1_phase_supported(d0, out_dim, k) || !weight_prepared || !sage_aligned(table_sliced, 16) || !sage_aligned(out, 16) ||
+        !sage_aligned(weight_prepared, 16) || ldo % 4 != 0 || ldo < out_dim || ldw < d0) {
+        sage_set_error("layer1_fused: unsupported shape d0=%d h1=%d k=%d (or unaligned arrays / no prepared weights)", d0, out_dim, k);
+        return SAGE_EUNSUPPORTED;
+    }
+    if (n == 0) return SAGE_OK;
+    const PhaseArgs a{table_sliced, (int)table_rows, table_rows * (int64_t)kSliceFloats, nbr, cnt, k, n, n_dev, n_off, self_row, any_nonempty,
+                      weight, ldw, (const uint4*)weight_prepared, out_dim, act, out, ldo};
+    if (d0 == 64) return launch_phase<2>(a, st);
+    if (d0 == 128) return launch_phase<4>(a, st);
+    return launch_phase<8>(a, st);
+}
+
+extern "C" int sage_layer1_fused_supported(int32_t d0, int32_t h1, int32_t k) { return sage_layer1_phase_supported(d0, h1, k) ? 1 : 0; }
+
+extern "C" int sage_layer1_fused(const float* table_sliced, int64_t table_rows, int32_t d0, const int32_t* nbr, const int32_t* cnt,
+                                 int32_t k, int32_t n, const int32_t* n_dev, const int32_t* self_row, const int32_t* any_nonempty,
+                                 const float* weight, int64_t ldw, const void* weight_prepared, int32_t out_dim, int32_t act, float* out,
+                                 int64_t ldo, sage_stream_t stream) {
+    SAGE_REQUIRE(table_sliced && nbr && cnt && weight && weight_prepared && out, "layer1_fused: NULL array");
+    SAGE_REQUIRE(n >= 0 && table_rows >= 1 && table_rows < (1ll << 31), "layer1_fused: n = %d, table_rows = %lld", n, (long long)table_rows);
+    SAGE_REQUIRE(act >= 0 && act <= SAGE_ACT_NONE, "layer1_fused: bad activation");
+    return sage_launch_layer1_phase(table_sliced, table_rows, d0, nbr, cnt, k, n, n_dev, self_row, any_nonempty, weight, ldw, weight_prepared,
+                                    out_dim, act, out, ldo, 0, (hipStream_t)stream);
+}

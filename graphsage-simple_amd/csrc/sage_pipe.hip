@@ -81,6 +81,7 @@ struct sage_pipe {
     hipStream_t st[4];                                  // S, G, D, L
     hipEvent_t ev[4][SAGE_PIPE_MAX_DEPTH];              // [role][slot]: role's work on the slot's batch is enqueued
     hipEvent_t ev_fork;
+    bool d_empty;                                       // stage D launches nothing for this model (sage_forward2_contract1_is_empty)
     uint64_t submitted;
     int64_t express_count;                              // batches that took the express lane (submitting thread only)
     // host enqueue threads
@@ -175,6 +176,7 @@ extern "C" int sage_pipe_create(const sage_model_t* m, int32_t batch, int32_t de
     sage_pipe* p = new (std::nothrow) sage_pipe();
     SAGE_REQUIRE(p, "pipe_create: out of host memory");
     p->model = *m;
+    p->d_empty = sage_forward2_contract1_is_empty(m, batch);
     p->batch = batch;
     p->depth = depth;
     p->ws_bytes = workspace_bytes;
@@ -230,6 +232,7 @@ extern "C" int sage_pipe_update_weights(sage_pipe_t* p, const float* w1, const f
     p->model.w1 = w1;
     p->model.w2 = w2;
     p->model.w1_prepared = w1_prepared;
+    p->d_empty = sage_forward2_contract1_is_empty(&p->model, p->batch);      // the one-launch layer 1 needs the prepared planes
     return SAGE_OK;
 }
 
@@ -245,6 +248,13 @@ static int role_enqueue(sage_pipe* p, int r, const pipe_desc& d, unsigned long l
     // capturing (hipExtLaunchKernel is not a capturable launch), and SAGE_PIPE_TAIL=0 keeps the separate record (A/B)
     static const bool tail_on = [] { const char* v = getenv("SAGE_PIPE_TAIL"); return !(v && *v == '0'); }();
     auto tail = [&](int role, bool needed) -> void* { return (tail_on && cap == 0 && needed) ? (void*)p->ev[role][slot] : nullptr; };
+    // Stage D launches nothing when the gather stage writes h1 itself (the phase-sliced layer 1, the pre-transformed table): its wait and its
+    // record are then skipped and L takes the hand-off from G directly -- one stream-to-stream hand-off less per batch.  (The role threads
+    // still pass the batch from G's thread to D's to L's on the host, so L's wait is issued after G's record.)  SAGE_PIPE_EMPTY_D=1 keeps the
+    // empty hand-off (A/B).
+    static const bool keep_empty_d = [] { const char* v = getenv("SAGE_PIPE_EMPTY_D"); return v && *v == '1'; }();
+    const bool d_empty = !keep_empty_d && p->d_empty;
+    const int g_consumer = d_empty ? RL : RD;             // who takes G's hand-off
     if (d.express) {
         // the pipeline was idle at submit: no release to wait for, nothing to hand over; roles S, G, D have no calls to make
         if (r != RL) return SAGE_OK;
@@ -293,15 +303,16 @@ static int role_enqueue(sage_pipe* p, int r, const pipe_desc& d, unsigned long l
             const sage_ext_launch_t x{d.gev[0], d.gev[1]};
             if (d.gev[0] && d.gev[1]) sage_ext_launch = &x;
             const int rc = sage_forward2_launch_stages(m, ws, p->ws_bytes, d.seeds, p->batch, d.key, nullptr, 0, SAGE_STAGE_GATHER1, p->st[RG],
-                                                       tail(RG, p->st[RD] != p->st[RG]));
+                                                       tail(RG, p->st[g_consumer] != p->st[RG]));
             sage_ext_launch = nullptr;
             if (rc) return rc;
-            if (tail(RG, p->st[RD] != p->st[RG])) return SAGE_OK;
+            if (tail(RG, p->st[g_consumer] != p->st[RG])) return SAGE_OK;
         }
 #endif
-        return record(p, RG, slot, p->st[RD] != p->st[RG]);
+        return record(p, RG, slot, p->st[g_consumer] != p->st[RG]);
     case RD:
         // D: the contraction (or the whole fused layer 1)
+        if (d_empty) return SAGE_OK;
         if (int rc = wait_on(p, RD, RG, slot, cap != 0)) return rc;
 #ifndef SAGE_PIPE_SKIP_D
         if (int rc = sage_forward2_launch_stages(m, ws, p->ws_bytes, d.seeds, p->batch, d.key, nullptr, 0, SAGE_STAGE_CONTRACT1, p->st[RD],
@@ -312,7 +323,7 @@ static int role_enqueue(sage_pipe* p, int r, const pipe_desc& d, unsigned long l
         return record(p, RD, slot, p->st[RL] != p->st[RD]);
     default:
         // L: layer 2; afterwards the workspace is clean again
-        if (int rc = wait_on(p, RL, RD, slot, cap != 0)) return rc;
+        if (int rc = wait_on(p, RL, d_empty ? RG : RD, slot, cap != 0)) return rc;
 #ifndef SAGE_PIPE_SKIP_L
         if (int rc = sage_forward2_launch_stages(m, ws, p->ws_bytes, d.seeds, p->batch, d.key, d.out, d.ldo, SAGE_STAGE_LAYER2, p->st[RL],
                                                  tail(RL, p->st[RS] != p->st[RL])))

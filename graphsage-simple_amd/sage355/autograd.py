@@ -84,6 +84,7 @@ class _TwoHop(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, w1, w2, engine, ids, key):
+        engine.keep_means = True             # backward_weights reads the layer-1 means this forward leaves in the workspace
         out = engine.forward(ids, seed=key)
         ctx.engine, ctx.ids, ctx.key, ctx.generation = engine, ids, key, engine.generation
         ctx.devices = (w1.device, w2.device)

@@ -140,6 +140,8 @@ class TwoHopEngine:
         self._cursor = None
         self._graph = None
         self._last_batch = 0
+        self.keep_means = False              # True: every forward leaves the layer-1 means in the workspace (training: backward_weights reads them)
+        self._kept_means = False             # ... and whether the LAST forward did
         self.generation = 0                  # forwards run so far: a backward checks that the workspace still holds ITS forward
         self._bwd = None                     # scratch of backward_weights (allocated on first use)
         self._reserve(max_batch)
@@ -283,7 +285,18 @@ class TwoHopEngine:
         if self.layout.total_bytes:
             self._slice_table()
 
-    def _model(self, queued=False):
+    def _wants_means(self):
+        """Does this forward have to leave the layer-1 means in the workspace (sage_model_t.keep_means)?  Yes for an engine that trains
+        (keep_means: EngineTrainer, autograd._TwoHop -- backward_weights reads them) and for any forward made under grad mode on weights
+        that require a gradient; otherwise the library may run the split layer 1 as one launch that never writes them (same h1 bits)."""
+        return bool(self.keep_means or (torch.is_grad_enabled() and (self.w1.requires_grad or self.w2.requires_grad)))
+
+    def _model(self, queued=False, keep_means=False):
+        m = self._model_cached(queued)
+        m.keep_means = int(bool(keep_means))
+        return m
+
+    def _model_cached(self, queued=False):
         self._sync_table()
         if self.layout.total_bytes:          # the layout is known (after the first _reserve)
             self._slice_table()
@@ -343,7 +356,8 @@ class TwoHopEngine:
     def forward_queued(self, out):
         """One forward on the batch at the queue cursor (advances it).  Capturable."""
         L = native.lib()
-        rc = L.sage_forward2(self._model(queued=True), self.workspace.data_ptr(), self.workspace.numel(), None,
+        self._kept_means = self._wants_means()
+        rc = L.sage_forward2(self._model(queued=True, keep_means=self._kept_means), self.workspace.data_ptr(), self.workspace.numel(), None,
                              self._queue_batch, 0, out.data_ptr(), out.stride(0), torch.cuda.current_stream().cuda_stream)
         if rc != 0:
             native.check(rc, "forward2 (queued)")
@@ -415,7 +429,8 @@ class TwoHopEngine:
         elif out.shape != (b, self.h2) or out.dtype != torch.float32 or not out.is_cuda or out.stride(1) != 1:
             raise native.SageError("forward: `out` must be a [B, h2] fp32 device tensor with unit inner stride")
         L = native.lib()
-        args = (self._model(), self.workspace.data_ptr(), self.workspace.numel(), seeds.data_ptr(), b,
+        self._kept_means = self._wants_means()
+        args = (self._model(keep_means=self._kept_means), self.workspace.data_ptr(), self.workspace.numel(), seeds.data_ptr(), b,
                 int(seed) & 0xFFFFFFFFFFFFFFFF, out.data_ptr(), out.stride(0), torch.cuda.current_stream().cuda_stream)
         rc = L.sage_forward2(*args) if stage_events is None else L.sage_forward2_profiled(*args, stage_events)
         if rc != 0:
@@ -488,7 +503,7 @@ class TwoHopEngine:
             #      frontier's arbitrarily placed rows is needed, and the bits do not depend on the layout.  agg1 from the workspace
             #      (split layer) or recomputed on the live rows
             self_row1 = s1_nodes if self.agg_self_loop else None
-            if L.layer1_split:
+            if L.layer1_split and self._kept_means:
                 # the split layer (sliced gather + contraction) left the means of this very forward in the workspace: no second gather
                 agg1 = self._view(L.agg1, L.max_s1 * d0p, torch.float32).view(L.max_s1, d0p)
             else:
@@ -531,6 +546,9 @@ class TwoHopEngine:
             "nbr1": self._view(L.nbr1, L.max_s1 * self.k1, torch.int32).view(L.max_s1, self.k1)[:n1],
             "cnt1": self._view(L.cnt1, L.max_s1, torch.int32)[:n1],
             "h1": self._view(L.h1, L.max_s1 * self.h1p, torch.float32).view(L.max_s1, self.h1p)[:n1, :self.h1],
+            # the layer-1 means: only a split layer 1 writes them, and only when the forward was asked to keep them (keep_means)
+            "agg1": (self._view(L.agg1, L.max_s1 * self.d0p, torch.float32).view(L.max_s1, self.d0p)[:n1, :self.d0]
+                     if (L.layer1_split and self._kept_means) else None),
         }
 
 

@@ -15,7 +15,7 @@ CSRC_DIR = os.path.join(os.path.dirname(_HERE), "csrc")
 ACT_RELU, ACT_SIGMOID, ACT_NONE = 0, 1, 2
 TAG_INNER, TAG_OUTER, TAG_INNER_SELF = 1, 2, 3
 MAX_FANOUT = 64
-ABI_VERSION = 7
+ABI_VERSION = 8
 CSR_MEAN_CHUNK = 512                                          # SAGE_CSR_MEAN_CHUNK
 EINVAL, EUNSUPPORTED, ELAUNCH, ENOSPACE = -1, -2, -3, -4      # include/sage355.h
 
@@ -33,6 +33,7 @@ SYMBOLS = [
     "sage_pipe_create", "sage_pipe_destroy", "sage_pipe_update_weights", "sage_pipe_submit", "sage_pipe_submit_profiled", "sage_pipe_submit_many",
     "sage_pipe_join", "sage_pipe_fork", "sage_pipe_reset", "sage_pipe_set_threads", "sage_pipe_flush",
     "sage_pipe_express_count", "sage_csr_mean_workspace_bytes", "sage_csr_mean",
+    "sage_layer1_fused", "sage_layer1_fused_supported",
 ]
 PIPE_MAX_DEPTH = 8
 
@@ -53,7 +54,7 @@ class Model(Structure):
                 ("k1", c_int32), ("k2", c_int32), ("concat", c_int32), ("agg_self_loop", c_int32),
                 ("act1", c_int32), ("act2", c_int32), ("nan_empty", c_int32), ("fused", c_int32), ("ws_batch", c_int32),
                 ("queue", c_void_p), ("queue_len", c_int32), ("queue_cursor", c_void_p), ("w1_prepared", c_void_p), ("seed_map", c_void_p),
-                ("table_sliced", c_void_p), ("table_slice_floats", c_int32), ("w1_is_identity", c_int32)]
+                ("table_sliced", c_void_p), ("table_slice_floats", c_int32), ("w1_is_identity", c_int32), ("keep_means", c_int32)]
 
 
 class Batch(Structure):      # sage_batch_t, lives in device memory (16 bytes)
@@ -144,6 +145,8 @@ def lib():
     L.sage_pipe_express_count.argtypes = [P]
     L.sage_csr_mean_workspace_bytes.argtypes = [I32, I64, I32]
     L.sage_csr_mean.argtypes = [P, P, I64, P, I32, I64, P, I64, I64, I32, I32, P, P, I64, P, c_size_t, P]
+    L.sage_layer1_fused_supported.argtypes = [I32, I32, I32]
+    L.sage_layer1_fused.argtypes = [P, I64, I32, P, P, I32, I32, P, P, P, P, I64, P, I32, I32, P, I64, P]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name == "sage_prepared_weight_bytes" or name.endswith("_workspace_bytes"):

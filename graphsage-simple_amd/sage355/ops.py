@@ -203,6 +203,57 @@ def layer_forward(table, nbr, cnt, weight, act=ACT_RELU, concat=False, self_inde
     return out
 
 
+def slice_major(table, slice_floats=32):
+    """[N, D] -> the slice-major copy float[D / W][N][W] (sage_model_t.table_sliced)."""
+    n, d = table.shape
+    if d % slice_floats:
+        raise native.SageError(f"slice_major: {d} columns are not whole slices of {slice_floats}")
+    return table.view(n, d // slice_floats, slice_floats).permute(1, 0, 2).contiguous()
+
+
+def prepare_weights(weight, concat=False):
+    """W [out_dim, dim | 2 dim] -> its bf16 planes in the contraction kernels' register order (sage_prepare_weights)."""
+    _need_gpu()
+    weight, ldw = _row_major(weight, "weight")
+    out_dim, dim = weight.shape[0], weight.shape[1] // (2 if concat else 1)
+    need = native.lib().sage_prepared_weight_bytes(dim, out_dim, int(bool(concat)))
+    if need == 0:
+        raise native.SageError(f"prepare_weights: no prepared form for dim={dim} out_dim={out_dim}")
+    prep = torch.empty(need, dtype=torch.uint8, device=weight.device)
+    native.check(native.lib().sage_prepare_weights(native.ptr(weight), ldw, dim, out_dim, int(bool(concat)), native.ptr(prep), need,
+                                                   native.stream_handle()), "prepare_weights")
+    return prep
+
+
+def layer1_fused_supported(dim, out_dim, k):
+    return bool(native.lib().sage_layer1_fused_supported(int(dim), int(out_dim), int(k)))
+
+
+def layer1_fused(table_sliced, nbr, cnt, weight, act=ACT_RELU, self_row=None, any_nonempty=None, n_dev=None, out=None, prepared=None):
+    """The gcn encoder's layer 1 in one phase-sliced launch on a slice-major table float[D / 32][N][32] (sage_layer1_fused)."""
+    _need_gpu()
+    if not (table_sliced.dim() == 3 and table_sliced.shape[2] == 32 and table_sliced.is_contiguous() and table_sliced.dtype == torch.float32):
+        raise native.SageError("layer1_fused: table_sliced must be a contiguous fp32 [D / 32, N, 32] tensor")
+    weight, ldw = _row_major(weight, "weight")
+    _chk(nbr, torch.int32, "nbr", 2)
+    _chk(cnt, torch.int32, "cnt", 1)
+    n, k = nbr.shape
+    dim, rows = table_sliced.shape[0] * 32, table_sliced.shape[1]
+    out_dim = weight.shape[0]
+    if weight.shape[1] != dim:
+        raise native.SageError(f"layer1_fused: weight is {tuple(weight.shape)}, table is {dim} wide")
+    if prepared is None:
+        prepared = prepare_weights(weight)
+    if out is None:
+        out = torch.empty((n, out_dim), dtype=torch.float32, device=table_sliced.device)
+    out, ldo = _row_major(out, "out")
+    rc = native.lib().sage_layer1_fused(native.ptr(table_sliced), rows, dim, native.ptr(nbr), native.ptr(cnt), k, n, native.ptr(n_dev),
+                                        native.ptr(self_row), native.ptr(any_nonempty), native.ptr(weight), ldw, native.ptr(prepared),
+                                        out_dim, int(act), native.ptr(out), ldo, native.stream_handle())
+    native.check(rc, "layer1_fused")
+    return out
+
+
 def csr_mean_workspace_bytes(n, max_edges, dim):
     """Bytes of the workspace sage_csr_mean needs (host arithmetic; 0 = shape out of range)."""
     return int(native.lib().sage_csr_mean_workspace_bytes(int(n), int(max_edges), int(dim)))

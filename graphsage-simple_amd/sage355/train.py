@@ -176,6 +176,7 @@ class EngineTrainer:
         dist.broadcast_params(self.parameters())
         self.engine = TwoHopEngine(rowptr, col, table, self.w1, self.w2, num_sample1, num_sample2, concat=self.concat,
                                    agg_self_loop=agg_self_loop, max_batch=max_batch, relabel=relabel)
+        self.engine.keep_means = True        # the backward reads the layer-1 means of the forward from the workspace
         self.engine.invalidate_weights()
         self._native, self._ops = native, ops
         self._out_q = None

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SAGE_ABI_VERSION 7
+#define SAGE_ABI_VERSION 8
 
 #define SAGE_OK            0
 #define SAGE_EINVAL       -1   /* bad argument (NULL, size, alignment, range) */
@@ -198,6 +198,24 @@ int sage_layer_forward(const float* table, int64_t table_rows, int64_t ld, int32
 int sage_layer_forward_supported(int32_t dim, int32_t out_dim, int32_t concat);
 
 /* ---------------------------------------------------------------------------
+ * sage_layer1_fused (ABI 8) -- sage_gather_mean + the gcn encoder's W.x + act on a SLICE-MAJOR table of 32-float slices
+ * (float[d0 / 32][table_rows][32], sage_model_t.table_sliced) in ONE launch that keeps the means on the chip: a block walks the
+ * slices of its 32 rows in phases, gathers a slice as the column-sliced gather does and contracts it with that slice of the
+ * prepared W (sage_prepare_weights(weight, ldw, d0, out_dim, 0, ...); required) while the fp32 accumulators stay in registers.
+ *     out[r, :] = act( W . mean_j table[nbr[r*k+j], :] ),  rows r < min(*n_dev, n)
+ * Same self_row / any_nonempty rules as sage_gather_mean (no slot_rows); the bits are those of sage_gather_mean on that table
+ * followed by the contraction, whatever n and wherever the row sits.  d0 in {64, 128, 256}, out_dim in {32, 64, 96, 128},
+ * k <= SAGE_MAX_FANOUT, ldo % 4 == 0, 16-byte aligned arrays; otherwise SAGE_EUNSUPPORTED and nothing is launched.
+ * ------------------------------------------------------------------------- */
+int sage_layer1_fused_supported(int32_t d0, int32_t out_dim, int32_t k);
+int sage_layer1_fused(const float* table_sliced, int64_t table_rows, int32_t d0,
+                      const int32_t* nbr, const int32_t* cnt, int32_t k,
+                      int32_t n, const int32_t* n_dev,
+                      const int32_t* self_row, const int32_t* any_nonempty,
+                      const float* weight, int64_t ldw, const void* weight_prepared, int32_t out_dim, int32_t act,
+                      float* out, int64_t ldo, sage_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * Backward of the two operators (autograd of encoders.py:58-62 and
  * aggregators.py:60-74; the reference gets these from torch autograd through
  * mm / relu / cat / div).
@@ -348,6 +366,10 @@ typedef struct {
      * else the flag is ignored (the contraction with an identity W1 returns its operand exactly, so the result is the same bit for bit).
      * w1 must still point at a real identity matrix. */
     int32_t        w1_is_identity;
+    /* (ABI 8) the caller needs the layer-1 means of this forward (sage_ws_layout_t.agg1: the backward reads them, sage_two_hop_grad_w1):
+     * layer 1 then always runs as gather + contraction when it is split.  0: the library may run the split layer 1 as ONE launch that
+     * never writes the means (sage_layer1_fused below; bit-identical h1), and agg1 is then left as it was. */
+    int32_t        keep_means;
 } sage_model_t;
 
 /* Where the intermediates of one forward live inside the caller's workspace
