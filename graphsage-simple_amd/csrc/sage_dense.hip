@@ -700,20 +700,22 @@ bool sage_layer_dense_supported(int32_t dim, int32_t out_dim) {
     return dim >= 4 && dim % 4 == 0 && out_dim >= 1 && out_dim <= 128;
 }
 
-int sage_launch_layer_dense(const float* x, int64_t ldx, int32_t dim, int32_t n, const int32_t* n_dev, int32_t concat,
-                            const float* self_tab, int64_t ld_self, int64_t self_rows, const int32_t* self_index,
-                            const int32_t* cnt, const int32_t* any_nonempty,
-                            const float* weight, int64_t ldw, int32_t out_dim, int32_t act, float* out, int64_t ldo, int32_t n_off,
-                            sage_finish_t fin, const void* weight_prepared, hipStream_t st) {
-    if (!sage_layer_dense_supported(dim, out_dim) || ldx % 4 != 0 || ldw % 4 != 0 || !sage_aligned(x, 16) ||
-        !sage_aligned(weight, 16) || (concat && (ld_self % 4 != 0 || !sage_aligned(self_tab, 16)))) {
-        sage_set_error("layer_dense: unsupported shape dim=%d out_dim=%d", dim, out_dim);
+int sage_launch_layer_dense(const sage_rows_t& agg, const sage_lists_t& rows, const sage_self_t& self, const sage_contract_t& c,
+                            sage_finish_t fin, hipStream_t st) {
+    const float* x = agg.table;
+    const int64_t ldx = agg.ld;
+    const int32_t dim = agg.dim, n = rows.n;
+    const bool concat = self.self_tab != nullptr;
+    if (!sage_layer_dense_supported(dim, c.out_dim) || ldx % 4 != 0 || c.ldw % 4 != 0 || !sage_aligned(x, 16) ||
+        !sage_aligned(c.weight, 16) || (concat && (self.ld_self % 4 != 0 || !sage_aligned(self.self_tab, 16)))) {
+        sage_set_error("layer_dense: unsupported shape dim=%d out_dim=%d", dim, c.out_dim);
         return SAGE_EUNSUPPORTED;
     }
     if (n == 0) return SAGE_OK;
-    const DenseArgs a{x, ldx, dim, n, n_dev, n_off, concat ? self_tab : x, concat ? ld_self : ldx, concat ? (int)self_rows : n,
-                      self_index, cnt, any_nonempty, weight, ldw, out_dim, act, out, ldo, fin,
-                      (const uint4*)weight_prepared};
+    // (cnt / any_nonempty stay null: the means arrive finished, the gather has applied the empty-row rule)
+    const DenseArgs a{x, ldx, dim, n, rows.n_dev, rows.n_off, concat ? self.self_tab : x, concat ? self.ld_self : ldx,
+                      concat ? (int)self.self_rows : n, self.self_index, nullptr, nullptr, c.weight, c.ldw, c.out_dim, c.act, c.out, c.ldo, fin,
+                      (const uint4*)c.weight_prepared};
     const int kp = dim <= 64 ? 64 : dim <= 128 ? 128 : 256;
     if (dim > 256) return concat ? launch_bf16x3<256, true, true>(a, st) : launch_bf16x3<256, false, true>(a, st);
 #ifndef SAGE_DENSE_FP32

@@ -46,7 +46,7 @@ extern "C" int sage_forward2_layout(const sage_model_t* m, int32_t max_batch, sa
     const int64_t max_s1 = B * m->k2 + B;   // frontier of B*k2 ids + B self rows (concat or self-loop)
     size_t off = 0;
     auto take = [&](size_t bytes) { size_t o = off; off = align_up(off + bytes, 256); return o; };
-    L->counters = take(32 * sizeof(int32_t));    // 16 counters + a spare 64-bit slot (sampler key of a stage-wise forward)
+    L->counters = take(32 * sizeof(int32_t));    // 16 counters in use; the rest of the 32 is padding that keeps the offsets the Python layer reads
     L->hash_capacity = next_pow2(2 * B * (m->k2 + 1));
     L->hash_keys = take((size_t)L->hash_capacity * 4);
     L->hash_rows = take((size_t)L->hash_capacity * 4);
@@ -104,7 +104,7 @@ layer1_form_t layer1_form(const sage_model_t* m, const sage_ws_layout_t& L, cons
 
 int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes, const int32_t* seeds, int32_t batch,
                   uint64_t seed, float* out, int64_t ldo, sage_stream_t stream, void* const* ev, int stages = SAGE_STAGE_ALL,
-                  int cursor_off = 0, bool key_in_ws = false, void* tail_event = nullptr) {
+                  void* tail_event = nullptr) {
     if (int rc = check_model(m)) return rc;
     SAGE_REQUIRE(m->rowptr1 && m->col1 && m->rowptr2 && m->col2 && m->table && m->w1 && m->w2, "forward2: NULL model array");
     const bool queued = m->queue != nullptr;
@@ -163,30 +163,57 @@ int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes
     // The workspace is self-cleaning (sage_forward2_init once, then every forward leaves the hash
     // keys wiped and the counters zero), so a forward is exactly 4 launches (5 when layer 1 is split into
     // gather + contraction, 6 with the generic two-launch layers).
-    const int64_t ldw1 = (int64_t)m->d0 * (m->concat ? 2 : 1);
-    const int64_t ldw2 = (int64_t)m->h1 * (m->concat ? 2 : 1);
-    const int32_t* nan1 = m->nan_empty ? any1 : nullptr;
-    // outer hop: some neighbour was sampled  <=>  the frontier counter is non-zero, so layer 2 needs no flag at all
-    const int32_t* nan2 = m->nan_empty ? (self_loop ? any2 : s1_count) : nullptr;
     const bool fuse1 = m->fused && sage_layer_fused_supported(m->d0, m->h1, m->concat) && m->table_ld % 4 == 0 &&
                        sage_aligned(m->table, 16) && sage_aligned(m->w1, 16);
     // wide + large layer 1: column-sliced gather into agg1, then a dense contraction (or both in one phase-sliced launch);
     // otherwise the one-launch fused layer; otherwise the generic two-launch form
     const layer1_form_t form1 = layer1_form(m, L, agg1, h1);
     const bool split1 = form1.split1, gather_only1 = form1.gather_only1, phase1 = form1.phase1;
-    uint64_t* key_slot = key_in_ws ? (uint64_t*)(counters + 16) : nullptr;    // in the 256-B slot of the counters, past the 16 ints in use
     // Layer 2 as a one-launch layer resolves hash slots itself, so both hops can be sampled by ONE launch (sage_sample.hip:
     // sample_fused_kernel).  The choice depends on the model only, so every call on a workspace agrees on who resolves the slots.
     const bool fuse2 = m->fused && sage_layer_fused_supported(m->h1, m->h2, m->concat) && sage_aligned(m->w2, 16);
     const bool sfused = fuse2 && sage_tunables().sample_fused != 0 && m->k1 <= 64 && m->k2 <= 64;
+
+    // What the launches below read and write, each described once.
+    // Layer 1: rows [0, s1_count + first_row) of S1 gather from the feature table ...
+    const sage_rows_t table1{.table = m->table, .table_rows = m->num_nodes, .ld = m->table_ld, .dim = m->d0};
+    // ... or, in the column-sliced forms, from its optional slice-major copy ([d0 / sw][num_nodes][sw]: every XCD pair reads ONE contiguous array)
+    const int sw = m->table_slice_floats ? m->table_slice_floats : 64;
+    const bool sm = m->table_sliced != nullptr && (sw == 32 || sw == 64 || sw == 128) && m->d0 % sw == 0 && sage_aligned(m->table_sliced, 16);
+    const sage_rows_t table1_sliced = !sm ? table1 : sage_rows_t{.table = m->table_sliced, .table_rows = m->num_nodes, .ld = sw, .dim = m->d0,
+                                                                 .slice_stride = m->num_nodes * (int64_t)sw};
+    const sage_lists_t lists1{.nbr = nbr1, .cnt = cnt1, .k = m->k1, .n = L.max_s1, .n_dev = s1_count, .n_off = first_row,
+                              .self_row = self_loop ? s1_nodes : nullptr, .any_nonempty = m->nan_empty ? any1 : nullptr};
+    const sage_rows_t means1{.table = agg1, .table_rows = L.max_s1, .ld = m->d0, .dim = m->d0};
+    const sage_self_t self1{.self_tab = m->concat ? m->table : nullptr, .ld_self = m->table_ld, .self_rows = m->num_nodes, .self_index = s1_nodes};
+    const sage_contract_t contract1{.weight = m->w1, .ldw = (int64_t)m->d0 * (m->concat ? 2 : 1), .weight_prepared = m->w1_prepared,
+                                    .out_dim = m->h1, .act = m->act1, .out = h1, .ldo = m->h1};
+    // Layer 2: the seeds gather from h1, by frontier row -- or by hash slot when the fused sampler left the slots unresolved: the layer
+    // then resolves them (rows left in row2 / self_row2) and wipes the keys, the duties the inner-hop launch has otherwise.
+    // Outer hop: some neighbour was sampled  <=>  the frontier counter is non-zero, so layer 2 needs no flag at all
+    const int32_t* nan2 = m->nan_empty ? (self_loop ? any2 : s1_count) : nullptr;
+    const sage_rows_t table2{.table = h1, .table_rows = L.max_s1, .ld = m->h1, .dim = m->h1};
+    const sage_lists_t lists2 = sfused ? sage_lists_t{.nbr = slot2, .cnt = cnt2, .k = m->k2, .n = batch, .slot_rows = fr.rows,
+                                                      .self_row = self_loop ? self_slot2 : nullptr, .any_nonempty = nan2}
+                                       : sage_lists_t{.nbr = row2, .cnt = cnt2, .k = m->k2, .n = batch,
+                                                      .self_row = self_loop ? self_row2 : nullptr, .any_nonempty = nan2};
+    const sage_slot_resolve_t resolve2{fr.keys, row2, self_loop ? self_row2 : nullptr};
+    const sage_rows_t means2{.table = agg2, .table_rows = batch, .ld = m->h1, .dim = m->h1};
+    const sage_self_t self2{.self_tab = m->concat ? h1 : nullptr, .ld_self = m->h1, .self_rows = L.max_s1};
+    const sage_contract_t contract2{.weight = m->w2, .ldw = (int64_t)m->h1 * (m->concat ? 2 : 1), .out_dim = m->h2, .act = m->act2, .out = out,
+                                    .ldo = ldo};
+
     const int both = SAGE_STAGE_SAMPLE_OUTER | SAGE_STAGE_SAMPLE_INNER;
     if (sfused && (stages & both)) {
         SAGE_REQUIRE((stages & both) == both, "forward2: with the fused sampler the two sampling stages are one launch: pass "
                                                 "SAGE_STAGE_SAMPLE_OUTER | SAGE_STAGE_SAMPLE_INNER together");
         SAGE_EV(0);
-        if (int rc = sage_launch_sample_fused(m, seeds, batch, seed, nbr2, cnt2, (m->nan_empty && self_loop) ? any2 : nullptr, &fr, self_loop, slot2,
-                                              self_slot2, queued ? 1 : 0, m->concat ? s1_nodes : nullptr, first_row, nbr1, cnt1,
-                                              m->nan_empty ? any1 : nullptr, m->concat ? batch : 0, st))
+        if (int rc = sage_launch_sample_fused({.m = m, .seeds = seeds, .batch = batch, .seed = seed, .queued = queued ? 1 : 0,
+                                               .nbr2 = nbr2, .cnt2 = cnt2, .any2 = (m->nan_empty && self_loop) ? any2 : nullptr,
+                                               .frontier = &fr, .frontier_row_off = first_row, .insert_self = self_loop, .nbr_slot = slot2,
+                                               .self_slot = self_slot2, .nodes_copy = m->concat ? s1_nodes : nullptr,
+                                               .nbr1 = nbr1, .cnt1 = cnt1, .any1 = m->nan_empty ? any1 : nullptr,
+                                               .seed_rows = first_row /* = batch for the concat encoder, else 0 */}, st))
             return rc;
         SAGE_EV(1);
         SAGE_EV(2);
@@ -198,9 +225,12 @@ int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes
     // 1. outer hop: seeds -> nbr2, hash insert -> frontier rows [first_row, ...)
     SAGE_EV(0);
     arm(SAGE_STAGE_SAMPLE_OUTER);
-    if (int rc = sage_launch_sample(m->rowptr2, m->col2, m->num_nodes, seeds, batch, nullptr, m->k2, seed, SAGE_TAG_OUTER, 0, SAGE_TAG_OUTER, nbr2,
-                                    cnt2, (m->nan_empty && self_loop) ? any2 : nullptr, &fr, self_loop, slot2, self_slot2, qm, 1, m->concat ? s1_nodes : nullptr, 0, first_row,
-                                    nullptr, cursor_off, key_slot, m->seed_map, st))
+    if (int rc = sage_launch_sample({.rowptr = m->rowptr2, .col = m->col2, .num_nodes = m->num_nodes, .nodes = seeds, .n = batch, .k = m->k2,
+                                     .seed = seed, .tag = SAGE_TAG_OUTER, .tag_self = SAGE_TAG_OUTER,
+                                     .nbr = nbr2, .cnt = cnt2, .any_nonempty = (m->nan_empty && self_loop) ? any2 : nullptr,
+                                     .frontier = &fr, .frontier_row_off = first_row, .insert_self = self_loop, .nbr_slot = slot2,
+                                     .self_slot = self_slot2, .queue_model = qm, .nodes_from_batch = 1,
+                                     .nodes_copy = m->concat ? s1_nodes : nullptr, .seed_map = m->seed_map}, st))
         return rc;
     if (int rc = settle(SAGE_STAGE_SAMPLE_OUTER)) return rc;
     SAGE_EV(1);
@@ -213,9 +243,11 @@ int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes
     const sage_resolve_t resolve{slot2, row2, batch * m->k2, self_loop ? self_slot2 : nullptr, self_row2, batch, fr.rows, fr.keys};
     SAGE_EV(2);
     arm(SAGE_STAGE_SAMPLE_INNER);
-    if (int rc = sage_launch_sample(m->rowptr1, m->col1, m->num_nodes, s1_nodes, L.max_s1, s1_count, m->k1, seed, SAGE_TAG_INNER, first_row,
-                                    SAGE_TAG_INNER_SELF, nbr1, cnt1, m->nan_empty ? any1 : nullptr, nullptr, 0, nullptr, nullptr, qm, 0, nullptr, first_row, 0,
-                                    &resolve, cursor_off, key_slot, nullptr, st))
+    if (int rc = sage_launch_sample({.rowptr = m->rowptr1, .col = m->col1, .num_nodes = m->num_nodes, .nodes = s1_nodes, .n = L.max_s1,
+                                     .n_dev = s1_count, .n_off = first_row, .k = m->k1, .seed = seed, .tag = SAGE_TAG_INNER,
+                                     .tag_self_rows = first_row, .tag_self = SAGE_TAG_INNER_SELF,
+                                     .nbr = nbr1, .cnt = cnt1, .any_nonempty = m->nan_empty ? any1 : nullptr, .queue_model = qm,
+                                     .resolve = &resolve}, st))
         return rc;
     if (int rc = settle(SAGE_STAGE_SAMPLE_INNER)) return rc;
     SAGE_EV(3);
@@ -228,25 +260,11 @@ int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes
     if (ext_g) sage_ext_launch = &gx; else SAGE_EV(4);
     struct ClearHook { bool on; ~ClearHook() { if (on) sage_ext_launch = nullptr; } } clear_hook{ext_g};
     arm(SAGE_STAGE_GATHER1);               // (a launch that carries the measurement hook's events leaves it armed: settle() records)
-    if (gather_only1) {
-        const int sw = m->table_slice_floats ? m->table_slice_floats : 64;
-        const bool sm = m->table_sliced != nullptr && (sw == 32 || sw == 64 || sw == 128) && m->d0 % sw == 0 && sage_aligned(m->table_sliced, 16);
-        if (int rc = sage_launch_gather_mean(sm ? m->table_sliced : m->table, m->num_nodes, sm ? sw : m->table_ld, m->d0, nbr1, cnt1, m->k1, L.max_s1,
-                                             s1_count, nullptr, self_loop ? s1_nodes : nullptr, nan1, h1, m->h1, first_row, st,
-                                             sm ? m->num_nodes * (int64_t)sw : 0, m->act1))
-            return rc;
-    } else if (phase1) {
-        if (int rc = sage_launch_layer1_phase(m->table_sliced, m->num_nodes, m->d0, nbr1, cnt1, m->k1, L.max_s1, s1_count,
-                                              self_loop ? s1_nodes : nullptr, nan1, m->w1, ldw1, m->w1_prepared, m->h1, m->act1, h1, m->h1,
-                                              first_row, st))
-            return rc;
-    } else if (split1) {
-        // optional slice-major copy of the table ([d0 / 64][num_nodes][64]): every XCD pair reads ONE contiguous array
-        const int sw = m->table_slice_floats ? m->table_slice_floats : 64;
-        const bool sm = m->table_sliced != nullptr && (sw == 32 || sw == 64 || sw == 128) && m->d0 % sw == 0 && sage_aligned(m->table_sliced, 16);
-        if (int rc = sage_launch_gather_mean(sm ? m->table_sliced : m->table, m->num_nodes, sm ? sw : m->table_ld, m->d0, nbr1, cnt1, m->k1, L.max_s1,
-                                             s1_count, nullptr, self_loop ? s1_nodes : nullptr, nan1, agg1, m->d0, first_row, st,
-                                             sm ? m->num_nodes * (int64_t)sw : 0))
+    if (phase1) {
+        if (int rc = sage_launch_layer1_phase(table1_sliced, lists1, contract1, st)) return rc;
+    } else if (split1) {                   // means into agg1 -- or, on a pre-transformed table (gather_only1), activated and straight into h1
+        if (int rc = sage_launch_gather_mean(table1_sliced, lists1, gather_only1 ? h1 : agg1, gather_only1 ? m->h1 : m->d0,
+                                             gather_only1 ? m->act1 : SAGE_ACT_NONE, st))
             return rc;
     }
     if (int rc = settle(SAGE_STAGE_GATHER1)) return rc;
@@ -259,22 +277,13 @@ int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes
         // nothing: the gather stage wrote h1
     } else if (split1) {
         arm(SAGE_STAGE_CONTRACT1);
-        if (int rc = sage_launch_layer_dense(agg1, m->d0, m->d0, L.max_s1, s1_count, m->concat, m->table, m->table_ld, m->num_nodes,
-                                             s1_nodes, nullptr, nullptr, m->w1, ldw1, m->h1, m->act1, h1, m->h1, first_row, no_fin, m->w1_prepared, st))
-            return rc;
+        if (int rc = sage_launch_layer_dense(means1, lists1, self1, contract1, no_fin, st)) return rc;
     } else if (fuse1) {
         arm(SAGE_STAGE_CONTRACT1);
-        if (int rc = sage_launch_layer_fused(m->table, m->num_nodes, m->table_ld, m->d0, nbr1, cnt1, m->k1, L.max_s1, s1_count, nullptr,
-                                             self_loop ? s1_nodes : nullptr, nan1, m->concat, s1_nodes, m->w1, ldw1, m->h1, m->act1,
-                                             h1, m->h1, first_row, no_fin, st))
-            return rc;
+        if (int rc = sage_launch_layer_fused(table1, lists1, self1, contract1, nullptr, no_fin, st)) return rc;
     } else {
-        if (int rc = sage_launch_gather_mean(m->table, m->num_nodes, m->table_ld, m->d0, nbr1, cnt1, m->k1, L.max_s1, s1_count, nullptr,
-                                             self_loop ? s1_nodes : nullptr, nan1, agg1, m->d0, first_row, st))
-            return rc;
-        if (int rc = sage_launch_linear_act(m->concat ? m->table : nullptr, m->table_ld, s1_nodes, agg1, m->d0, m->d0, m->w1, ldw1,
-                                            m->h1, m->act1, L.max_s1, s1_count, h1, m->h1, first_row, no_fin, st))
-            return rc;
+        if (int rc = sage_launch_gather_mean(table1, lists1, agg1, m->d0, SAGE_ACT_NONE, st)) return rc;
+        if (int rc = sage_launch_linear_act(means1, lists1, self1, contract1, no_fin, st)) return rc;
     }
     if (int rc = settle(SAGE_STAGE_CONTRACT1)) return rc;
     SAGE_EV(7);
@@ -282,27 +291,12 @@ int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes
     if (stages & SAGE_STAGE_LAYER2) {
     // 4. layer 2 on the seeds; its last block zeroes the counters and advances the batch queue
     SAGE_EV(8);
-    if (fuse2 && sfused) {
-        // slots in, rows resolved (and left in row2 / self_row2), keys wiped: the duties the inner-hop launch had
-        const sage_slot_resolve_t rs{fr.keys, row2, self_loop ? self_row2 : nullptr};
+    if (fuse2) {
         arm(SAGE_STAGE_LAYER2);
-        if (int rc = sage_launch_layer_fused(h1, L.max_s1, m->h1, m->h1, slot2, cnt2, m->k2, batch, nullptr, fr.rows,
-                                             self_loop ? self_slot2 : nullptr, nan2, m->concat, nullptr, m->w2, ldw2, m->h2, m->act2,
-                                             out, ldo, 0, fin, st, &rs))
-            return rc;
-    } else if (fuse2) {
-        arm(SAGE_STAGE_LAYER2);
-        if (int rc = sage_launch_layer_fused(h1, L.max_s1, m->h1, m->h1, row2, cnt2, m->k2, batch, nullptr, nullptr,
-                                             self_loop ? self_row2 : nullptr, nan2, m->concat, nullptr, m->w2, ldw2, m->h2, m->act2,
-                                             out, ldo, 0, fin, st))
-            return rc;
+        if (int rc = sage_launch_layer_fused(table2, lists2, self2, contract2, sfused ? &resolve2 : nullptr, fin, st)) return rc;
     } else {
-        if (int rc = sage_launch_gather_mean(h1, L.max_s1, m->h1, m->h1, row2, cnt2, m->k2, batch, nullptr, nullptr,
-                                             self_loop ? self_row2 : nullptr, nan2, agg2, m->h1, 0, st))
-            return rc;
-        if (int rc = sage_launch_linear_act(m->concat ? h1 : nullptr, m->h1, nullptr, agg2, m->h1, m->h1, m->w2, ldw2, m->h2, m->act2,
-                                            batch, nullptr, out, ldo, 0, fin, st))
-            return rc;
+        if (int rc = sage_launch_gather_mean(table2, lists2, agg2, m->h1, SAGE_ACT_NONE, st)) return rc;
+        if (int rc = sage_launch_linear_act(means2, lists2, self2, contract2, fin, st)) return rc;
     }
     if (int rc = settle(SAGE_STAGE_LAYER2)) return rc;
     SAGE_EV(9);
@@ -328,7 +322,7 @@ bool sage_forward2_contract1_is_empty(const sage_model_t* m, int32_t batch) {
 // A subset of the forward's launches with the seeds and the sampler key taken from the call (sage_pipe.hip: one call per role stream)
 int sage_forward2_launch_stages(const sage_model_t* m, void* workspace, size_t workspace_bytes, const int32_t* seeds, int32_t batch,
                                 uint64_t seed, float* out, int64_t ldo, int32_t stages, hipStream_t stream, void* tail_event) {
-    return forward2_impl(m, workspace, workspace_bytes, seeds, batch, seed, out, ldo, (sage_stream_t)stream, nullptr, stages, 0, false, tail_event);
+    return forward2_impl(m, workspace, workspace_bytes, seeds, batch, seed, out, ldo, (sage_stream_t)stream, nullptr, stages, tail_event);
 }
 
 extern "C" int sage_forward2_profiled(const sage_model_t* m, void* workspace, size_t workspace_bytes, const int32_t* seeds,

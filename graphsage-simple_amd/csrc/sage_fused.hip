@@ -517,20 +517,20 @@ bool sage_layer_fused_supported(int32_t dim, int32_t out_dim, int32_t concat) {
     return dim >= 4 && dim <= 256 && dim % 4 == 0 && out_dim >= 1 && out_dim <= 128;
 }
 
-int sage_launch_layer_fused(const float* table, int64_t table_rows, int64_t ld, int32_t dim, const int32_t* nbr,
-                            const int32_t* cnt, int32_t k, int32_t n, const int32_t* n_dev, const int32_t* slot_rows,
-                            const int32_t* self_row, const int32_t* any_nonempty, int32_t concat, const int32_t* self_index,
-                            const float* weight, int64_t ldw, int32_t out_dim, int32_t act, float* out, int64_t ldo,
-                            int32_t n_off, sage_finish_t fin, hipStream_t st, const sage_slot_resolve_t* resolve) {
-    if (!sage_layer_fused_supported(dim, out_dim, concat) || ld % 4 != 0 || ldw % 4 != 0 || !sage_aligned(table, 16) ||
-        !sage_aligned(weight, 16)) {
+int sage_launch_layer_fused(const sage_rows_t& src, const sage_lists_t& l, const sage_self_t& self, const sage_contract_t& c,
+                            const sage_slot_resolve_t* resolve, sage_finish_t fin, hipStream_t st) {
+    const int32_t dim = src.dim, concat = self.self_tab != nullptr;
+    SAGE_REQUIRE(!concat || (self.self_tab == src.table && self.ld_self == src.ld && self.self_rows == src.table_rows),
+                 "layer_forward: the fused layer takes a row's own features from the source table");
+    if (!sage_layer_fused_supported(dim, c.out_dim, concat) || src.ld % 4 != 0 || c.ldw % 4 != 0 || !sage_aligned(src.table, 16) ||
+        !sage_aligned(c.weight, 16)) {
         sage_set_error("layer_forward: no fused kernel for dim=%d out_dim=%d ld=%lld (needs dim%%4==0, dim<=256, out_dim<=128, 16-B rows)",
-                       dim, out_dim, (long long)ld);
+                       dim, c.out_dim, (long long)src.ld);
         return SAGE_EUNSUPPORTED;
     }
-    if (n == 0) return SAGE_OK;
-    const FusedArgs a{table, (int)table_rows, ld, dim, nbr, cnt, k, n, n_dev, slot_rows, self_row, any_nonempty, self_index,
-                      table, ld, (int)table_rows, weight, ldw, out_dim, act, out, ldo, n_off, fin,
+    if (l.n == 0) return SAGE_OK;
+    const FusedArgs a{src.table, (int)src.table_rows, src.ld, dim, l.nbr, l.cnt, l.k, l.n, l.n_dev, l.slot_rows, l.self_row, l.any_nonempty,
+                      self.self_index, src.table, src.ld, (int)src.table_rows, c.weight, c.ldw, c.out_dim, c.act, c.out, c.ldo, l.n_off, fin,
                       resolve ? resolve->wipe_keys : nullptr, resolve ? resolve->rows_out : nullptr, resolve ? resolve->self_rows_out : nullptr};
     const int kp = dim <= 64 ? 64 : dim <= 128 ? 128 : 256;
     if (!concat) {
@@ -557,7 +557,10 @@ extern "C" int sage_layer_forward(const float* table, int64_t table_rows, int64_
     SAGE_REQUIRE(ld >= dim && ldo >= out_dim && ldw >= (concat ? 2 : 1) * (int64_t)dim, "layer_forward: leading dimensions");
     SAGE_REQUIRE(table_rows >= 1 && table_rows < (1ll << 31), "layer_forward: table_rows = %lld", (long long)table_rows);
     SAGE_REQUIRE(act >= 0 && act <= SAGE_ACT_NONE, "layer_forward: act = %d", act);
-    return sage_launch_layer_fused(table, table_rows, ld, dim, nbr, cnt, k, n, n_dev, slot_rows, self_row, any_nonempty, concat,
-                                   self_index, weight, ldw, out_dim, act, out, ldo, 0, sage_finish_t{nullptr, nullptr},
-                                   (hipStream_t)stream, nullptr);
+    const sage_self_t self{concat ? table : nullptr, ld, table_rows, self_index};
+    return sage_launch_layer_fused({.table = table, .table_rows = table_rows, .ld = ld, .dim = dim},
+                                   {.nbr = nbr, .cnt = cnt, .k = k, .n = n, .n_dev = n_dev, .slot_rows = slot_rows, .self_row = self_row,
+                                    .any_nonempty = any_nonempty},
+                                   self, {.weight = weight, .ldw = ldw, .out_dim = out_dim, .act = act, .out = out, .ldo = ldo}, nullptr,
+                                   sage_finish_t{nullptr, nullptr}, (hipStream_t)stream);
 }

@@ -145,19 +145,22 @@ __global__ __launch_bounds__(256) void gather_mean_rows_kernel(
             SAGE_LAUNCH_TAIL((kernel), dim3(blocks), dim3(256), 0, st, __VA_ARGS__);                                                 \
     } while (0)
 
-template <int SL, typename... A>
-void launch_rows(int blocks, bool slot, hipStream_t st, A... args) {
-    if (slot) SAGE_LAUNCH_G((gather_mean_rows_kernel<SL, 8, true>), args...);
-    else if (sage_tunables().gather_trip >= 16) SAGE_LAUNCH_G((gather_mean_rows_kernel<SL, 16, false>), args...);
-    else SAGE_LAUNCH_G((gather_mean_rows_kernel<SL, 8, false>), args...);
+// Every column-sliced kernel has this signature: the dispatch below picks one, sage_launch_gather_mean launches it.
+using sliced_kernel_t = decltype(&gather_mean_sliced_kernel<16>);
+
+template <int SL>
+sliced_kernel_t pick_rows(bool slot) {
+    if (slot) return gather_mean_rows_kernel<SL, 8, true>;
+    if (sage_tunables().gather_trip >= 16) return gather_mean_rows_kernel<SL, 16, false>;
+    return gather_mean_rows_kernel<SL, 8, false>;
 }
 
-template <int SL, int U, typename... A>
-void launch_pipe(int blocks, hipStream_t st, A... args) {
+template <int SL, int U>
+sliced_kernel_t pick_pipe() {
     const int rows = sage_tunables().gather_rows_in_flight;
-    if (rows >= 4) SAGE_LAUNCH_G((gather_mean_sliced_pipe_kernel<SL, U, 4>), args...);
-    else if (rows >= 2) SAGE_LAUNCH_G((gather_mean_sliced_pipe_kernel<SL, U, 2>), args...);
-    else SAGE_LAUNCH_G((gather_mean_sliced_pipe_kernel<SL, U, 1>), args...);
+    if (rows >= 4) return gather_mean_sliced_pipe_kernel<SL, U, 4>;
+    if (rows >= 2) return gather_mean_sliced_pipe_kernel<SL, U, 2>;
+    return gather_mean_sliced_pipe_kernel<SL, U, 1>;
 }
 
 }  // namespace
@@ -167,10 +170,10 @@ bool sage_gather_is_sliced(int32_t dim, int64_t ld, int64_t ldo, const float* ta
     return vec4 && k <= kWave && ((dim >= SAGE_SPLIT_MIN_DIM && n >= 8192) || dim > 256);   // rows wider than 256 have no one-launch kernel
 }
 
-int sage_launch_gather_mean(const float* table, int64_t table_rows, int64_t ld, int32_t dim, const int32_t* nbr,
-                            const int32_t* cnt, int32_t k, int32_t n, const int32_t* n_dev, const int32_t* slot_rows,
-                            const int32_t* self_row, const int32_t* any_nonempty, float* out, int64_t ldo, int32_t n_off,
-                            hipStream_t st, int64_t slice_stride, int act) {
+int sage_launch_gather_mean(const sage_rows_t& src, const sage_lists_t& l, float* out, int64_t ldo, int32_t act, hipStream_t st) {
+    const float* table = src.table;
+    const int64_t ld = src.ld, slice_stride = src.slice_stride;
+    const int32_t dim = src.dim, k = l.k, n = l.n;
     if (n == 0) return SAGE_OK;
     if (slice_stride != 0 || sage_gather_is_sliced(dim, ld, ldo, table, out, n, k)) {
         // 256-B slices (16 lanes; 512-B rows: 29.1 us as two slices vs 32.5 us as one).  A narrow row that does not end
@@ -191,57 +194,40 @@ int sage_launch_gather_mean(const float* table, int64_t table_rows, int64_t ld, 
         (void)kForce;
         const int nslice = sage_cdiv(dim, sl * 4);
         const int blocks = nslice * max(1, kNumCU * sage_tunables().gather_blocks_per_cu / nslice);   // >= one block per slice (very wide rows)
+        sliced_kernel_t kernel;
+        const char* name;
         if (variant == 2) {
             // one destination row per lane group (see sage_gather_body.h)
-            if (sl == 8) launch_rows<8>(blocks, slot_rows != nullptr, st, table, (int)table_rows, ld, dim, nbr, cnt, k, n, n_dev, slot_rows, self_row, any_nonempty, out, ldo, n_off, nslice, slice_stride, act);
-            else if (sl == 32) launch_rows<32>(blocks, slot_rows != nullptr, st, table, (int)table_rows, ld, dim, nbr, cnt, k, n, n_dev, slot_rows, self_row, any_nonempty, out, ldo, n_off, nslice, slice_stride, act);
-            else launch_rows<16>(blocks, slot_rows != nullptr, st, table, (int)table_rows, ld, dim, nbr, cnt, k, n, n_dev, slot_rows, self_row, any_nonempty, out, ldo, n_off, nslice, slice_stride, act);
-            SAGE_CHECK_LAUNCH("gather_mean_rows_kernel");
-            return SAGE_OK;
-        }
-        if (variant == 1) {
+            const bool slot = l.slot_rows != nullptr;
+            kernel = sl == 8 ? pick_rows<8>(slot) : sl == 32 ? pick_rows<32>(slot) : pick_rows<16>(slot);
+            name = "gather_mean_rows_kernel";
+        } else if (variant == 1) {
             // rows software-pipelined: every neighbour of a row in ONE trip (U wave-instructions of 64/sl neighbours), the
             // next row's ids requested meanwhile.  U by fanout; lists longer than U x 64/sl take further trips.
             const int per = kWave / sl, need = sage_cdiv(k, per);
-            if (sl == 64) {     // whole 1-KiB rows, one neighbour per wave-instruction: graphs with little reuse (every row read once)
-                if (need <= 8) launch_pipe<64, 8>(blocks, st, table, (int)table_rows, ld, dim, nbr, cnt, k, n, n_dev, slot_rows, self_row, any_nonempty, out, ldo, n_off, nslice, slice_stride, act);
-                else launch_pipe<64, 16>(blocks, st, table, (int)table_rows, ld, dim, nbr, cnt, k, n, n_dev, slot_rows, self_row, any_nonempty, out, ldo, n_off, nslice, slice_stride, act);
-            } else if (sl == 8) {
-                if (need <= 2) launch_pipe<8, 2>(blocks, st, table, (int)table_rows, ld, dim, nbr, cnt, k, n, n_dev, slot_rows, self_row, any_nonempty, out, ldo, n_off, nslice, slice_stride, act);
-                else if (need <= 4) launch_pipe<8, 4>(blocks, st, table, (int)table_rows, ld, dim, nbr, cnt, k, n, n_dev, slot_rows, self_row, any_nonempty, out, ldo, n_off, nslice, slice_stride, act);
-                else launch_pipe<8, 8>(blocks, st, table, (int)table_rows, ld, dim, nbr, cnt, k, n, n_dev, slot_rows, self_row, any_nonempty, out, ldo, n_off, nslice, slice_stride, act);
-            } else if (sl == 32) {
-                if (need <= 4) launch_pipe<32, 4>(blocks, st, table, (int)table_rows, ld, dim, nbr, cnt, k, n, n_dev, slot_rows, self_row, any_nonempty, out, ldo, n_off, nslice, slice_stride, act);
-                else launch_pipe<32, 8>(blocks, st, table, (int)table_rows, ld, dim, nbr, cnt, k, n, n_dev, slot_rows, self_row, any_nonempty, out, ldo, n_off, nslice, slice_stride, act);
-            } else {
-                if (need <= 2) launch_pipe<16, 2>(blocks, st, table, (int)table_rows, ld, dim, nbr, cnt, k, n, n_dev, slot_rows, self_row, any_nonempty, out, ldo, n_off, nslice, slice_stride, act);
-                else if (need <= 4) launch_pipe<16, 4>(blocks, st, table, (int)table_rows, ld, dim, nbr, cnt, k, n, n_dev, slot_rows, self_row, any_nonempty, out, ldo, n_off, nslice, slice_stride, act);
-                else launch_pipe<16, 8>(blocks, st, table, (int)table_rows, ld, dim, nbr, cnt, k, n, n_dev, slot_rows, self_row, any_nonempty, out, ldo, n_off, nslice, slice_stride, act);
-            }
-            SAGE_CHECK_LAUNCH("gather_mean_sliced_pipe_kernel");
-            return SAGE_OK;
+            if (sl == 64)       // whole 1-KiB rows, one neighbour per wave-instruction: graphs with little reuse (every row read once)
+                kernel = need <= 8 ? pick_pipe<64, 8>() : pick_pipe<64, 16>();
+            else if (sl == 8)
+                kernel = need <= 2 ? pick_pipe<8, 2>() : need <= 4 ? pick_pipe<8, 4>() : pick_pipe<8, 8>();
+            else if (sl == 32)
+                kernel = need <= 4 ? pick_pipe<32, 4>() : pick_pipe<32, 8>();
+            else
+                kernel = need <= 2 ? pick_pipe<16, 2>() : need <= 4 ? pick_pipe<16, 4>() : pick_pipe<16, 8>();
+            name = "gather_mean_sliced_pipe_kernel";
+        } else {
+            kernel = sl == 32 ? gather_mean_sliced_kernel<32> : sl == 8 ? gather_mean_sliced_kernel<8> : gather_mean_sliced_kernel<16>;
+            name = "gather_mean_sliced_kernel";
         }
-        if (sl == 32)
-            SAGE_LAUNCH_G(gather_mean_sliced_kernel<32>, table, (int)table_rows, ld, dim, nbr, cnt, k,
-                               n, n_dev, slot_rows, self_row, any_nonempty, out, ldo, n_off, nslice, slice_stride, act);
-        else if (sl == 8)
-            SAGE_LAUNCH_G(gather_mean_sliced_kernel<8>, table, (int)table_rows, ld, dim, nbr, cnt, k,
-                               n, n_dev, slot_rows, self_row, any_nonempty, out, ldo, n_off, nslice, slice_stride, act);
-        else
-            SAGE_LAUNCH_G(gather_mean_sliced_kernel<16>, table, (int)table_rows, ld, dim, nbr, cnt, k,
-                               n, n_dev, slot_rows, self_row, any_nonempty, out, ldo, n_off, nslice, slice_stride, act);
-        SAGE_CHECK_LAUNCH("gather_mean_sliced_kernel");
+        SAGE_LAUNCH_G(kernel, table, (int)src.table_rows, ld, dim, l.nbr, l.cnt, k, n, l.n_dev, l.slot_rows, l.self_row, l.any_nonempty, out, ldo,
+                      l.n_off, nslice, slice_stride, act);
+        SAGE_CHECK_LAUNCH(name);
         return SAGE_OK;
     }
     if (act != SAGE_ACT_NONE) { sage_set_error("gather_mean: an activation in the epilogue exists in the column-sliced forms only"); return SAGE_EUNSUPPORTED; }
     const int blocks = min(sage_cdiv(n, 4), kNumCU * 8);
     const bool vec4 = (dim % 4 == 0) && (ld % 4 == 0) && (ldo % 4 == 0) && sage_aligned(table, 16) && sage_aligned(out, 16);
-    if (vec4)
-        hipLaunchKernelGGL(gather_mean_kernel<4>, dim3(blocks), dim3(256), 0, st, table, (int)table_rows, ld, dim, nbr, cnt, k, n,
-                           n_dev, slot_rows, self_row, any_nonempty, out, ldo, n_off);
-    else
-        hipLaunchKernelGGL(gather_mean_kernel<1>, dim3(blocks), dim3(256), 0, st, table, (int)table_rows, ld, dim, nbr, cnt, k, n,
-                           n_dev, slot_rows, self_row, any_nonempty, out, ldo, n_off);
+    hipLaunchKernelGGL(vec4 ? gather_mean_kernel<4> : gather_mean_kernel<1>, dim3(blocks), dim3(256), 0, st, table, (int)src.table_rows, ld, dim,
+                       l.nbr, l.cnt, k, n, l.n_dev, l.slot_rows, l.self_row, l.any_nonempty, out, ldo, l.n_off);
     SAGE_CHECK_LAUNCH("gather_mean_kernel");
     return SAGE_OK;
 }
@@ -254,6 +240,8 @@ extern "C" int sage_gather_mean(const float* table, int64_t table_rows, int64_t 
     SAGE_REQUIRE(n >= 0 && k >= 1, "gather_mean: n = %d, k = %d", n, k);
     SAGE_REQUIRE(dim >= 1 && ld >= dim && ldo >= dim, "gather_mean: dim = %d, ld = %lld, ldo = %lld", dim, (long long)ld, (long long)ldo);
     SAGE_REQUIRE(table_rows >= 1 && table_rows < (1ll << 31), "gather_mean: table_rows = %lld", (long long)table_rows);
-    return sage_launch_gather_mean(table, table_rows, ld, dim, nbr, cnt, k, n, n_dev, slot_rows, self_row, any_nonempty, out, ldo, 0,
-                                   (hipStream_t)stream);
+    return sage_launch_gather_mean({.table = table, .table_rows = table_rows, .ld = ld, .dim = dim},
+                                   {.nbr = nbr, .cnt = cnt, .k = k, .n = n, .n_dev = n_dev, .slot_rows = slot_rows, .self_row = self_row,
+                                    .any_nonempty = any_nonempty},
+                                   out, ldo, SAGE_ACT_NONE, (hipStream_t)stream);
 }

@@ -23,51 +23,85 @@ struct sage_finish_t {
     int32_t* counters;           // nullable = no finish duty
     int32_t* cursor;             // nullable
 };
-// Device-side row count = min(*n_dev + n_off, n).
+// What the launchers take ------------------------------------------------------------------
+// Plain aggregates, filled at the call site by member name (designated initialisers, which hipcc accepts under -std=c++17);
+// every nullable / optional member defaults to "absent".
+//
+// The rows a launch reads: a row-major table (row stride ld), or a slice-major one ([dim / ld][table_rows][ld], slice_stride =
+// table_rows * ld floats between slices; ld IS the slice width then).
+struct sage_rows_t {
+    const float* table; int64_t table_rows; int64_t ld; int32_t dim;
+    int64_t slice_stride = 0;
+};
+// The n destination rows of a launch and their neighbour lists.  Device-side row count = min(*n_dev + n_off, n).  A launch that
+// reads finished means instead of lists (sage_launch_layer_dense, sage_launch_linear_act) uses n, n_dev and n_off only.
+struct sage_lists_t {
+    const int32_t* nbr = nullptr;            // [n, k] ids of table rows (hash slots with slot_rows), -1 = padding
+    const int32_t* cnt = nullptr;            // [n]
+    int32_t k = 0;
+    int32_t n;
+    const int32_t* n_dev = nullptr; int32_t n_off = 0;
+    const int32_t* slot_rows = nullptr;      // ids in nbr / self_row are slots of this array
+    const int32_t* self_row = nullptr;       // [n] the row's own id joins its set (aggregators.py:50-51)
+    const int32_t* any_nonempty = nullptr;   // the reference's 0/0 = NaN rule for empty rows applies when *any_nonempty != 0
+};
+// Concat encoder: where a destination row's own features come from (row self_index[r], or r).  self_tab == NULL: no concat.
+struct sage_self_t {
+    const float* self_tab = nullptr; int64_t ld_self = 0; int64_t self_rows = 0; const int32_t* self_index = nullptr;
+};
+// out = act([self |] mean . weight^T)
+struct sage_contract_t {
+    const float* weight; int64_t ldw; const void* weight_prepared = nullptr;      // (sage_prepare_weights)
+    int32_t out_dim; int32_t act; float* out; int64_t ldo;
+};
 
-int sage_launch_sample(const int64_t* rowptr, const int32_t* col, int64_t num_nodes, const int32_t* nodes, int32_t n, const int32_t* n_dev,
-                       int32_t k, uint64_t seed, uint32_t tag, int32_t tag_self_rows, uint32_t tag_self,
-                       int32_t* nbr, int32_t* cnt, int32_t* any_nonempty, const sage_frontier_t* frontier,
-                       int32_t insert_self, int32_t* nbr_slot, int32_t* self_slot, const sage_model_t* queue_model,
-                       int nodes_from_batch, int32_t* nodes_copy, int32_t n_off, int32_t frontier_row_off,
-                       const sage_resolve_t* resolve, int32_t cursor_off, uint64_t* key_slot, const int32_t* seed_map, hipStream_t st);
+// One sampling hop (sage_sample.hip).  Rows [0, tag_self_rows) draw from stream `tag_self` (the concat encoder's second enc1 call on
+// the seeds); with `frontier` the sampled ids are inserted and get rows from frontier_row_off on.
+struct sage_sample_t {
+    const int64_t* rowptr; const int32_t* col; int64_t num_nodes;
+    const int32_t* nodes; int32_t n; const int32_t* n_dev = nullptr; int32_t n_off = 0;
+    int32_t k; uint64_t seed; uint32_t tag; int32_t tag_self_rows = 0; uint32_t tag_self = 0;
+    int32_t* nbr; int32_t* cnt; int32_t* any_nonempty = nullptr;
+    const sage_frontier_t* frontier = nullptr; int32_t frontier_row_off = 0; int32_t insert_self = 0;
+    int32_t* nbr_slot = nullptr; int32_t* self_slot = nullptr;
+    const sage_model_t* queue_model = nullptr;     // seeds (nodes_from_batch) and sampler key come from the model's batch queue
+    int nodes_from_batch = 0;
+    int32_t* nodes_copy = nullptr;                 // nodes[r] (internal id) is also written here
+    const int32_t* seed_map = nullptr;             // nodes[r] is a caller id
+    const sage_resolve_t* resolve = nullptr;
+};
+int sage_launch_sample(const sage_sample_t& s, hipStream_t st);
 
-int sage_launch_sample_fused(const sage_model_t* m, const int32_t* seeds, int32_t batch, uint64_t seed, int32_t* nbr2, int32_t* cnt2,
-                             int32_t* any2, const sage_frontier_t* frontier, int32_t insert_self, int32_t* nbr_slot, int32_t* self_slot,
-                             int queued, int32_t* nodes_copy, int32_t frontier_row_off, int32_t* nbr1, int32_t* cnt1, int32_t* any1,
-                             int32_t seed_rows, hipStream_t st);
+// Both hops of a forward as one launch (see sample_fused_kernel).  `seed_rows` = batch for the concat encoder (rows [0, batch) of
+// S1 are the seeds themselves), else 0.
+struct sage_sample_fused_t {
+    const sage_model_t* m; const int32_t* seeds; int32_t batch; uint64_t seed; int queued = 0;
+    int32_t* nbr2; int32_t* cnt2; int32_t* any2 = nullptr;
+    const sage_frontier_t* frontier; int32_t frontier_row_off = 0; int32_t insert_self = 0; int32_t* nbr_slot; int32_t* self_slot = nullptr;
+    int32_t* nodes_copy = nullptr;
+    int32_t* nbr1; int32_t* cnt1; int32_t* any1 = nullptr; int32_t seed_rows = 0;
+};
+int sage_launch_sample_fused(const sage_sample_fused_t& s, hipStream_t st);
 
-int sage_launch_gather_mean(const float* table, int64_t table_rows, int64_t ld, int32_t dim, const int32_t* nbr,
-                            const int32_t* cnt, int32_t k, int32_t n, const int32_t* n_dev, const int32_t* slot_rows,
-                            const int32_t* self_row, const int32_t* any_nonempty, float* out, int64_t ldo, int32_t n_off,
-                            hipStream_t st, int64_t slice_stride = 0, int act = SAGE_ACT_NONE /* column-sliced forms only */);
+// `act` exists in the column-sliced forms only
+int sage_launch_gather_mean(const sage_rows_t& src, const sage_lists_t& l, float* out, int64_t ldo, int32_t act, hipStream_t st);
 bool sage_layer_dense_supported(int32_t dim, int32_t out_dim);
 bool sage_gather_is_sliced(int32_t dim, int64_t ld, int64_t ldo, const float* table, const float* out, int32_t n, int32_t k);
 
-int sage_launch_linear_act(const float* self_tab, int64_t ld_self, const int32_t* self_index, const float* agg, int64_t ld_agg,
-                           int32_t dim, const float* weight, int64_t ldw, int32_t out_dim, int32_t act, int32_t n,
-                           const int32_t* n_dev, float* out, int64_t ldo, int32_t n_off, sage_finish_t fin, hipStream_t st);
+int sage_launch_linear_act(const sage_rows_t& agg, const sage_lists_t& rows, const sage_self_t& self, const sage_contract_t& c,
+                           sage_finish_t fin, hipStream_t st);
 
-// Fused layer (sage_fused.hip).  Returns SAGE_EUNSUPPORTED when no instantiation fits.
-int sage_launch_layer_fused(const float* table, int64_t table_rows, int64_t ld, int32_t dim, const int32_t* nbr,
-                            const int32_t* cnt, int32_t k, int32_t n, const int32_t* n_dev, const int32_t* slot_rows,
-                            const int32_t* self_row, const int32_t* any_nonempty, int32_t concat, const int32_t* self_index,
-                            const float* weight, int64_t ldw, int32_t out_dim, int32_t act, float* out, int64_t ldo,
-                            int32_t n_off, sage_finish_t fin, hipStream_t st, const sage_slot_resolve_t* resolve = nullptr);
+// Fused layer (sage_fused.hip).  Returns SAGE_EUNSUPPORTED when no instantiation fits.  `self` must name the source table (SAGE_EINVAL).
+int sage_launch_layer_fused(const sage_rows_t& src, const sage_lists_t& l, const sage_self_t& self, const sage_contract_t& c,
+                            const sage_slot_resolve_t* resolve, sage_finish_t fin, hipStream_t st);
 bool sage_layer_fused_supported(int32_t dim, int32_t out_dim, int32_t concat);
-int sage_launch_layer_dense(const float* agg, int64_t ld_agg, int32_t dim, int32_t n, const int32_t* n_dev, int32_t concat,
-                            const float* self_tab, int64_t ld_self, int64_t self_rows, const int32_t* self_index,
-                            const int32_t* cnt, const int32_t* any_nonempty,
-                            const float* weight, int64_t ldw, int32_t out_dim, int32_t act, float* out, int64_t ldo, int32_t n_off,
-                            sage_finish_t fin, const void* weight_prepared, hipStream_t st);
+int sage_launch_layer_dense(const sage_rows_t& agg, const sage_lists_t& rows, const sage_self_t& self, const sage_contract_t& c,
+                            sage_finish_t fin, hipStream_t st);
 
 // Phase-sliced layer 1 (sage_layer1_phase.hip): gather + contraction of the gcn encoder's layer 1 in one launch on the slice-major table
 // of 32-float slices, bit-identical to sage_launch_gather_mean + sage_launch_layer_dense.  SAGE_EUNSUPPORTED when the shape has no kernel.
 bool sage_layer1_phase_supported(int32_t d0, int32_t h1, int32_t k);
-int sage_launch_layer1_phase(const float* table_sliced, int64_t table_rows, int32_t d0, const int32_t* nbr, const int32_t* cnt, int32_t k,
-                             int32_t n, const int32_t* n_dev, const int32_t* self_row, const int32_t* any_nonempty, const float* weight,
-                             int64_t ldw, const void* weight_prepared, int32_t out_dim, int32_t act, float* out, int64_t ldo, int32_t n_off,
-                             hipStream_t st);
+int sage_launch_layer1_phase(const sage_rows_t& src, const sage_lists_t& l, const sage_contract_t& c, hipStream_t st);
 
 // Measurement hook (sage_gather.hip): set by the thread that is about to launch the layer-1 gather, cleared right after.
 struct sage_ext_launch_t { void* start; void* stop; };

@@ -214,18 +214,18 @@ bool sage_layer1_phase_supported(int32_t d0, int32_t h1, int32_t k) {
     return (d0 == 64 || d0 == 128 || d0 == 256) && h1 >= 32 && h1 <= 128 && h1 % 32 == 0 && k >= 1 && k <= kMaxK;
 }
 
-int sage_launch_layer1_phase(const float* table_sliced, int64_t table_rows, int32_t d0, const int32_t* nbr, const int32_t* cnt, int32_t k,
-                             int32_t n, const int32_t* n_dev, const int32_t* self_row, const int32_t* any_nonempty, const float* weight,
-                             int64_t ldw, const void* weight_prepared, int32_t out_dim, int32_t act, float* out, int64_t ldo, int32_t n_off,
-                             hipStream_t st) {
-    if (!sage_layer1_phase_supported(d0, out_dim, k) || !weight_prepared || !sage_aligned(table_sliced, 16) || !sage_aligned(out, 16) ||
-        !sage_aligned(weight_prepared, 16) || ldo % 4 != 0 || ldo < out_dim || ldw < d0) {
-        sage_set_error("layer1_fused: unsupported shape d0=%d h1=%d k=%d (or unaligned arrays / no prepared weights)", d0, out_dim, k);
+int sage_launch_layer1_phase(const sage_rows_t& src, const sage_lists_t& l, const sage_contract_t& c, hipStream_t st) {
+    const int32_t d0 = src.dim;
+    SAGE_REQUIRE(src.ld == kSliceFloats && src.slice_stride == src.table_rows * (int64_t)kSliceFloats,
+                 "layer1_fused: the table must be slice-major with %d-float slices", kSliceFloats);
+    if (!sage_layer1_phase_supported(d0, c.out_dim, l.k) || !c.weight_prepared || !sage_aligned(src.table, 16) || !sage_aligned(c.out, 16) ||
+        !sage_aligned(c.weight_prepared, 16) || c.ldo % 4 != 0 || c.ldo < c.out_dim || c.ldw < d0) {
+        sage_set_error("layer1_fused: unsupported shape d0=%d h1=%d k=%d (or unaligned arrays / no prepared weights)", d0, c.out_dim, l.k);
         return SAGE_EUNSUPPORTED;
     }
-    if (n == 0) return SAGE_OK;
-    const PhaseArgs a{table_sliced, (int)table_rows, table_rows * (int64_t)kSliceFloats, nbr, cnt, k, n, n_dev, n_off, self_row, any_nonempty,
-                      weight, ldw, (const uint4*)weight_prepared, out_dim, act, out, ldo};
+    if (l.n == 0) return SAGE_OK;
+    const PhaseArgs a{src.table, (int)src.table_rows, src.slice_stride, l.nbr, l.cnt, l.k, l.n, l.n_dev, l.n_off, l.self_row, l.any_nonempty,
+                      c.weight, c.ldw, (const uint4*)c.weight_prepared, c.out_dim, c.act, c.out, c.ldo};
     if (d0 == 64) return launch_phase<2>(a, st);
     if (d0 == 128) return launch_phase<4>(a, st);
     return launch_phase<8>(a, st);
@@ -240,6 +240,10 @@ extern "C" int sage_layer1_fused(const float* table_sliced, int64_t table_rows, 
     SAGE_REQUIRE(table_sliced && nbr && cnt && weight && weight_prepared && out, "layer1_fused: NULL array");
     SAGE_REQUIRE(n >= 0 && table_rows >= 1 && table_rows < (1ll << 31), "layer1_fused: n = %d, table_rows = %lld", n, (long long)table_rows);
     SAGE_REQUIRE(act >= 0 && act <= SAGE_ACT_NONE, "layer1_fused: bad activation");
-    return sage_launch_layer1_phase(table_sliced, table_rows, d0, nbr, cnt, k, n, n_dev, self_row, any_nonempty, weight, ldw, weight_prepared,
-                                    out_dim, act, out, ldo, 0, (hipStream_t)stream);
+    return sage_launch_layer1_phase({.table = table_sliced, .table_rows = table_rows, .ld = kSliceFloats, .dim = d0,
+                                     .slice_stride = table_rows * (int64_t)kSliceFloats},
+                                    {.nbr = nbr, .cnt = cnt, .k = k, .n = n, .n_dev = n_dev, .self_row = self_row, .any_nonempty = any_nonempty},
+                                    {.weight = weight, .ldw = ldw, .weight_prepared = weight_prepared, .out_dim = out_dim, .act = act, .out = out,
+                                     .ldo = ldo},
+                                    (hipStream_t)stream);
 }

@@ -97,13 +97,12 @@ __global__ __launch_bounds__(256) void linear_act_kernel(
 
 }  // namespace
 
-int sage_launch_linear_act(const float* self_tab, int64_t ld_self, const int32_t* self_index, const float* agg, int64_t ld_agg,
-                           int32_t dim, const float* weight, int64_t ldw, int32_t out_dim, int32_t act, int32_t n,
-                           const int32_t* n_dev, float* out, int64_t ldo, int32_t n_off, sage_finish_t fin, hipStream_t st) {
-    if (n == 0) return SAGE_OK;
-    dim3 grid(sage_cdiv(n, BM), sage_cdiv(out_dim, BN));
-    hipLaunchKernelGGL(linear_act_kernel, grid, dim3(256), 0, st, self_tab, ld_self, self_index, agg, ld_agg, dim, weight, ldw,
-                       out_dim, act, n, n_dev, out, ldo, n_off, fin);
+int sage_launch_linear_act(const sage_rows_t& agg, const sage_lists_t& rows, const sage_self_t& self, const sage_contract_t& c,
+                           sage_finish_t fin, hipStream_t st) {
+    if (rows.n == 0) return SAGE_OK;
+    dim3 grid(sage_cdiv(rows.n, BM), sage_cdiv(c.out_dim, BN));
+    hipLaunchKernelGGL(linear_act_kernel, grid, dim3(256), 0, st, self.self_tab, self.ld_self, self.self_index, agg.table, agg.ld, agg.dim,
+                       c.weight, c.ldw, c.out_dim, c.act, rows.n, rows.n_dev, c.out, c.ldo, rows.n_off, fin);
     SAGE_CHECK_LAUNCH("linear_act_kernel");
     return SAGE_OK;
 }
@@ -117,6 +116,8 @@ extern "C" int sage_linear_act(const float* self_tab, int64_t ld_self, const int
     SAGE_REQUIRE(!self_tab || ld_self >= dim, "linear_act: ld_self = %lld < dim", (long long)ld_self);
     SAGE_REQUIRE(ldw >= (self_tab ? 2 : 1) * (int64_t)dim, "linear_act: ldw = %lld too small", (long long)ldw);
     SAGE_REQUIRE(act >= 0 && act <= SAGE_ACT_NONE, "linear_act: act = %d", act);
-    return sage_launch_linear_act(self_tab, ld_self, self_index, agg, ld_agg, dim, weight, ldw, out_dim, act, n, n_dev, out, ldo, 0,
+    return sage_launch_linear_act({.table = agg, .table_rows = n, .ld = ld_agg, .dim = dim}, {.n = n, .n_dev = n_dev},
+                                  {.self_tab = self_tab, .ld_self = ld_self, .self_index = self_index},
+                                  {.weight = weight, .ldw = ldw, .out_dim = out_dim, .act = act, .out = out, .ldo = ldo},
                                   sage_finish_t{nullptr, nullptr}, (hipStream_t)stream);
 }

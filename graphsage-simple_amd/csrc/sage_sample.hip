@@ -97,106 +97,85 @@ int check_frontier(const sage_frontier_t* f, int64_t inserts) {
     return SAGE_OK;
 }
 
-template <int G, int THREADS, bool SAMPLE, bool FRONTIER, typename... A>
-void launch_one(int n, hipStream_t st, A... args) {
-    SAGE_LAUNCH_TAIL((sample_kernel<G, THREADS, SAMPLE, FRONTIER>), dim3(sage_cdiv(n, THREADS / G)), dim3(THREADS), 0, st, args...);
+// A sampler kernel and the launch shape that goes with it (nodes per block = threads / G)
+using sample_kernel_t = decltype(&sample_kernel<8, 256, true, false>);
+struct SampleLaunch { sample_kernel_t kernel; int threads; int nodes_per_block; };
+
+template <int T, bool SAMPLE, bool FRONTIER>
+SampleLaunch pick_by_fanout_t(int k) {
+    if (k <= 8) return {sample_kernel<8, T, SAMPLE, FRONTIER>, T, T / 8};
+    if (k <= 16) return {sample_kernel<16, T, SAMPLE, FRONTIER>, T, T / 16};
+    if (k <= 32) return {sample_kernel<32, T, SAMPLE, FRONTIER>, T, T / 32};
+    return {sample_kernel<64, T, SAMPLE, FRONTIER>, T, T / 64};
 }
 
-template <int T, bool SAMPLE, bool FRONTIER, typename... A>
-void launch_by_fanout_t(int k, int n, hipStream_t st, A... args) {
-    if (k <= 8) launch_one<8, T, SAMPLE, FRONTIER>(n, st, args...);
-    else if (k <= 16) launch_one<16, T, SAMPLE, FRONTIER>(n, st, args...);
-    else if (k <= 32) launch_one<32, T, SAMPLE, FRONTIER>(n, st, args...);
-    else launch_one<64, T, SAMPLE, FRONTIER>(n, st, args...);
-}
-
-template <bool SAMPLE, bool FRONTIER, typename... A>
-void launch_by_fanout(int k, int n, hipStream_t st, A... args) {
+template <bool SAMPLE, bool FRONTIER>
+SampleLaunch pick_by_fanout(int k) {
     // frontier variants use 1024-thread blocks: one global counter atomic per 1024/G nodes (256- and 512-thread
     // blocks were measured 3-5 % slower end to end)
     if constexpr (FRONTIER) {
         const int so = sage_tunables().outer_threads;
-        if (so == 256) launch_by_fanout_t<256, SAMPLE, FRONTIER>(k, n, st, args...);
-        else if (so == 512) launch_by_fanout_t<512, SAMPLE, FRONTIER>(k, n, st, args...);
-        else launch_by_fanout_t<1024, SAMPLE, FRONTIER>(k, n, st, args...);
+        if (so == 256) return pick_by_fanout_t<256, SAMPLE, FRONTIER>(k);
+        if (so == 512) return pick_by_fanout_t<512, SAMPLE, FRONTIER>(k);
+        return pick_by_fanout_t<1024, SAMPLE, FRONTIER>(k);
     }
 #ifndef SAGE_SI_THREADS
 #define SAGE_SI_THREADS 256
 #endif
-    else launch_by_fanout_t<SAGE_SI_THREADS, SAMPLE, FRONTIER>(k, n, st, args...);
+    else return pick_by_fanout_t<SAGE_SI_THREADS, SAMPLE, FRONTIER>(k);
 }
 
 }  // namespace
 
-// Internal launcher shared with sage_forward.hip (tag_self_rows: rows [0, tag_self_rows)
-// draw from stream `tag_self` -- the concat encoder's second enc1 call on the seeds).
-int sage_launch_sample(const int64_t* rowptr, const int32_t* col, int64_t num_nodes, const int32_t* nodes, int32_t n, const int32_t* n_dev,
-                       int32_t k, uint64_t seed, uint32_t tag, int32_t tag_self_rows, uint32_t tag_self,
-                       int32_t* nbr, int32_t* cnt, int32_t* any_nonempty, const sage_frontier_t* frontier,
-                       int32_t insert_self, int32_t* nbr_slot, int32_t* self_slot, const sage_model_t* qm, int nodes_from_batch,
-                       int32_t* nodes_copy, int32_t n_off, int32_t frontier_row_off, const sage_resolve_t* resolve,
-                       int32_t cursor_off, uint64_t* key_slot, const int32_t* seed_map, hipStream_t st) {
-    if (n == 0) return SAGE_OK;
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    const BatchSrc bs{qm ? qm->queue : nullptr, qm ? qm->queue_cursor : nullptr, qm ? qm->queue_len : 0, nodes_from_batch, nodes_copy,
-                      cursor_off, key_slot, (qm && nodes_from_batch) ? qm->seed_map : seed_map, (int)num_nodes};
+// Internal launcher shared with sage_forward.hip (sage_sample_t: sage_internal.h)
+int sage_launch_sample(const sage_sample_t& s, hipStream_t st) {
+    if (s.n == 0) return SAGE_OK;
+    const sage_model_t* qm = s.queue_model;
+    const BatchSrc bs{qm ? qm->queue : nullptr, qm ? qm->queue_cursor : nullptr, qm ? qm->queue_len : 0, s.nodes_from_batch, s.nodes_copy,
+                      (qm && s.nodes_from_batch) ? qm->seed_map : s.seed_map, (int)s.num_nodes};
     ResolveJob rj{};
-    if (resolve) rj = ResolveJob{resolve->slots, resolve->rows_out, resolve->n_slots, resolve->self_slots, resolve->self_rows_out,
-                                 resolve->n_self, resolve->hash_rows, resolve->hash_keys};
+    if (const sage_resolve_t* r = s.resolve)
+        rj = ResolveJob{r->slots, r->rows_out, r->n_slots, r->self_slots, r->self_rows_out, r->n_self, r->hash_rows, r->hash_keys};
     FrontierDev fd{};
+    if (const sage_frontier_t* f = s.frontier)
+        fd = FrontierDev{f->keys, f->rows, (uint32_t)f->capacity - 1u, f->nodes, f->count, f->max_nodes, s.frontier_row_off};
+    const SampleLaunch L = s.frontier ? pick_by_fanout<true, true>(s.k) : pick_by_fanout<true, false>(s.k);
     const int32_t* none = nullptr;
-    if (frontier) {
-        fd = FrontierDev{frontier->keys, frontier->rows, (uint32_t)frontier->capacity - 1u,
-                         frontier->nodes, frontier->count, frontier->max_nodes, frontier_row_off};
-        launch_by_fanout<true, true>(k, n, st, rowptr, col, nodes, n, n_dev, k, k0, k1, tag, tag_self_rows, tag_self, none, none,
-                                     nbr, cnt, any_nonempty, fd, insert_self, nbr_slot, self_slot, bs, n_off, rj);
-    } else {
-        launch_by_fanout<true, false>(k, n, st, rowptr, col, nodes, n, n_dev, k, k0, k1, tag, tag_self_rows, tag_self, none, none,
-                                      nbr, cnt, any_nonempty, fd, 0, (int32_t*)nullptr, (int32_t*)nullptr, bs, n_off, rj);
-    }
+    SAGE_LAUNCH_TAIL(L.kernel, dim3(sage_cdiv(s.n, L.nodes_per_block)), dim3(L.threads), 0, st, s.rowptr, s.col, s.nodes, s.n, s.n_dev, s.k,
+                     (uint32_t)s.seed, (uint32_t)(s.seed >> 32), s.tag, s.tag_self_rows, s.tag_self, none, none, s.nbr, s.cnt, s.any_nonempty, fd,
+                     s.frontier ? s.insert_self : 0, s.frontier ? s.nbr_slot : nullptr, s.frontier ? s.self_slot : nullptr, bs, s.n_off, rj);
     SAGE_CHECK_LAUNCH("sample_kernel");
     return SAGE_OK;
 }
 
 namespace {
-template <int G2, int G1, int T, typename... A>
-void launch_fused_t(int n, hipStream_t st, A... args) {
-    hipLaunchKernelGGL((sample_fused_kernel<G2, G1, T>), dim3(sage_cdiv(n, T / G2)), dim3(T), 0, st, args...);
+using sample_fused_kernel_t = decltype(&sample_fused_kernel<16, 16, 512>);
+struct FusedSampleLaunch { sample_fused_kernel_t kernel; int threads; int seeds_per_block; };
+
+template <int G2, int G1>
+FusedSampleLaunch pick_fused_by_threads() {
+    if (sage_tunables().outer_threads >= 1024) return {sample_fused_kernel<G2, G1, 1024>, 1024, 1024 / G2};
+    return {sample_fused_kernel<G2, G1, 512>, 512, 512 / G2};
 }
-template <int G2, int G1, typename... A>
-void launch_fused_by_threads(int n, hipStream_t st, A... args) {
-    if (sage_tunables().outer_threads >= 1024) launch_fused_t<G2, G1, 1024>(n, st, args...);
-    else launch_fused_t<G2, G1, 512>(n, st, args...);
-}
-template <int G2, typename... A>
-void launch_fused_by_k1(int k1, int n, hipStream_t st, A... args) {
-    if (k1 <= 16) launch_fused_by_threads<G2, 16>(n, st, args...);
-    else if (k1 <= 32) launch_fused_by_threads<G2, 32>(n, st, args...);
-    else launch_fused_by_threads<G2, 64>(n, st, args...);
+template <int G2>
+FusedSampleLaunch pick_fused_by_k1(int k1) {
+    if (k1 <= 16) return pick_fused_by_threads<G2, 16>();
+    if (k1 <= 32) return pick_fused_by_threads<G2, 32>();
+    return pick_fused_by_threads<G2, 64>();
 }
 }  // namespace
 
-// Both hops of a forward as one launch (see sample_fused_kernel).  `seed_rows` = batch for the concat encoder (rows [0, batch) of
-// S1 are the seeds themselves), else 0.
-int sage_launch_sample_fused(const sage_model_t* m, const int32_t* seeds, int32_t batch, uint64_t seed, int32_t* nbr2, int32_t* cnt2,
-                             int32_t* any2, const sage_frontier_t* frontier, int32_t insert_self, int32_t* nbr_slot, int32_t* self_slot,
-                             int queued, int32_t* nodes_copy, int32_t frontier_row_off, int32_t* nbr1, int32_t* cnt1, int32_t* any1,
-                             int32_t seed_rows, hipStream_t st) {
-    if (batch == 0) return SAGE_OK;
-    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
-    const BatchSrc bs{queued ? m->queue : nullptr, queued ? m->queue_cursor : nullptr, queued ? m->queue_len : 0, 1, nodes_copy, 0, nullptr,
+int sage_launch_sample_fused(const sage_sample_fused_t& s, hipStream_t st) {
+    if (s.batch == 0) return SAGE_OK;
+    const sage_model_t* m = s.m;
+    const BatchSrc bs{s.queued ? m->queue : nullptr, s.queued ? m->queue_cursor : nullptr, s.queued ? m->queue_len : 0, 1, s.nodes_copy,
                       m->seed_map, (int)m->num_nodes};
-    const FrontierDev fd{frontier->keys, frontier->rows, (uint32_t)frontier->capacity - 1u, frontier->nodes, frontier->count,
-                         frontier->max_nodes, frontier_row_off};
-    if (m->k2 <= 16)
-        launch_fused_by_k1<16>(m->k1, batch, st, m->rowptr2, m->col2, m->rowptr1, m->col1, seeds, batch, m->k2, m->k1, k0, k1, nbr2, cnt2, any2, fd,
-                               insert_self, nbr_slot, self_slot, bs, nbr1, cnt1, any1, seed_rows);
-    else if (m->k2 <= 32)
-        launch_fused_by_k1<32>(m->k1, batch, st, m->rowptr2, m->col2, m->rowptr1, m->col1, seeds, batch, m->k2, m->k1, k0, k1, nbr2, cnt2, any2, fd,
-                               insert_self, nbr_slot, self_slot, bs, nbr1, cnt1, any1, seed_rows);
-    else
-        launch_fused_by_k1<64>(m->k1, batch, st, m->rowptr2, m->col2, m->rowptr1, m->col1, seeds, batch, m->k2, m->k1, k0, k1, nbr2, cnt2, any2, fd,
-                               insert_self, nbr_slot, self_slot, bs, nbr1, cnt1, any1, seed_rows);
+    const sage_frontier_t* f = s.frontier;
+    const FrontierDev fd{f->keys, f->rows, (uint32_t)f->capacity - 1u, f->nodes, f->count, f->max_nodes, s.frontier_row_off};
+    const FusedSampleLaunch L = m->k2 <= 16 ? pick_fused_by_k1<16>(m->k1) : m->k2 <= 32 ? pick_fused_by_k1<32>(m->k1) : pick_fused_by_k1<64>(m->k1);
+    hipLaunchKernelGGL(L.kernel, dim3(sage_cdiv(s.batch, L.seeds_per_block)), dim3(L.threads), 0, st, m->rowptr2, m->col2, m->rowptr1, m->col1,
+                       s.seeds, s.batch, m->k2, m->k1, (uint32_t)s.seed, (uint32_t)(s.seed >> 32), s.nbr2, s.cnt2, s.any2, fd, s.insert_self,
+                       s.nbr_slot, s.self_slot, bs, s.nbr1, s.cnt1, s.any1, s.seed_rows);
     SAGE_CHECK_LAUNCH("sample_fused_kernel");
     return SAGE_OK;
 }
@@ -224,8 +203,10 @@ extern "C" int sage_sample_neighbors(const int64_t* rowptr, const int32_t* col, 
         SAGE_REQUIRE(nbr_slot, "sample_neighbors: frontier given but nbr_slot is NULL");
         SAGE_REQUIRE(!insert_self || self_slot, "sample_neighbors: insert_self needs self_slot");
     }
-    return sage_launch_sample(rowptr, col, num_nodes, nodes, n, n_dev, k, seed, tag, 0, tag, nbr, cnt, any_nonempty, frontier, insert_self,
-                              nbr_slot, self_slot, nullptr, 0, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, (hipStream_t)stream);
+    return sage_launch_sample({.rowptr = rowptr, .col = col, .num_nodes = num_nodes, .nodes = nodes, .n = n, .n_dev = n_dev, .k = k, .seed = seed,
+                               .tag = tag, .tag_self = tag, .nbr = nbr, .cnt = cnt, .any_nonempty = any_nonempty, .frontier = frontier,
+                               .insert_self = insert_self, .nbr_slot = nbr_slot, .self_slot = self_slot},
+                              (hipStream_t)stream);
 }
 
 extern "C" int sage_frontier_insert(const int32_t* nbr, const int32_t* cnt, int32_t k, const int32_t* self_nodes, int32_t n,
@@ -241,9 +222,10 @@ extern "C" int sage_frontier_insert(const int32_t* nbr, const int32_t* cnt, int3
                          frontier->nodes, frontier->count, frontier->max_nodes, 0};
     const int64_t* no64 = nullptr;
     const int32_t* no32 = nullptr;
-    launch_by_fanout<false, true>(k, n, (hipStream_t)stream, no64, no32, self_nodes, n, n_dev, k, 0u, 0u, 0u, 0, 0u, nbr, cnt,
-                                  (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, fd, self_nodes ? 1 : 0, nbr_slot,
-                                  self_slot, BatchSrc{nullptr, nullptr, 0, 0, nullptr, 0, nullptr, nullptr, 0}, 0, ResolveJob{});
+    const SampleLaunch L = pick_by_fanout<false, true>(k);
+    SAGE_LAUNCH_TAIL(L.kernel, dim3(sage_cdiv(n, L.nodes_per_block)), dim3(L.threads), 0, (hipStream_t)stream, no64, no32, self_nodes, n, n_dev, k,
+                     0u, 0u, 0u, 0, 0u, nbr, cnt, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, fd, self_nodes ? 1 : 0, nbr_slot,
+                     self_slot, BatchSrc{nullptr, nullptr, 0, 0, nullptr, nullptr, 0}, 0, ResolveJob{});
     SAGE_CHECK_LAUNCH("frontier_insert_kernel");
     return SAGE_OK;
 }

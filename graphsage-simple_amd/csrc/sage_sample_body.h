@@ -9,14 +9,11 @@ namespace sage_sample_detail {
 // Where a launch takes its node list / sampler key from: the call arguments, or the current
 // descriptor of a device-side batch queue (graph replay).
 struct BatchSrc {
-    const sage_batch_t* queue;
+    const sage_batch_t* queue;     // descriptor = queue[*cursor % len]
     const int32_t* cursor;
     int len;
     int nodes_from_batch;     // outer hop: nodes = descriptor seeds; inner hop: only the key
     int32_t* nodes_copy;      // nullable: nodes[r] is also written here (concat: seeds head S1)
-    int cursor_off;           // descriptor = queue[(*cursor + cursor_off) % len]  (pipelined forwards sample one batch ahead)
-    uint64_t* key_slot;       // nullable: the outer hop leaves the sampler key here, the inner hop takes it from here
-                              // instead of the queue (it then never reads the cursor, which another batch's last kernel advances)
     const int32_t* seed_map;  // nullable: outer hop only -- nodes[r] is a CALLER id, seed_map[nodes[r]] the internal one
     int num_nodes;            // ids outside [0, num_nodes) are treated as isolated nodes (degree 0): the reference raises
                               // IndexError for them (nn.Embedding lookup); a device kernel must not walk rowptr[] with them.
@@ -54,7 +51,7 @@ struct WinList {
     int* count;          // ids in the list
     int* base;           // frontier row of ids[0]
     int32_t* seeds;      // [THREADS / G] the block's own nodes (internal ids, -1 past the end)
-    uint32_t* key;       // [2] the sampler key the block resolved (queue / key slot)
+    uint32_t* key;       // [2] the sampler key the block resolved (the call's, or the queue descriptor's)
 };
 
 // G lanes per node (k <= G).  SAMPLE: draw from the CSR row; otherwise ids come from
@@ -102,19 +99,10 @@ __device__ __forceinline__ void sample_block(
         }
     }
     if (bs.queue) {
-        if (bs.key_slot && !bs.nodes_from_batch) {
-            const uint64_t kq = *bs.key_slot;
-            key0 = (uint32_t)kq;
-            key1 = (uint32_t)(kq >> 32);
-        } else {
-            const sage_batch_t b = bs.queue[(uint32_t)(*bs.cursor + bs.cursor_off) % (uint32_t)bs.len];
-            key0 = (uint32_t)b.seed;
-            key1 = (uint32_t)(b.seed >> 32);
-            if (bs.nodes_from_batch) {
-                nodes = b.seeds;
-                if (bs.key_slot && bid == 0 && tid == 0) *bs.key_slot = b.seed;
-            }
-        }
+        const sage_batch_t b = bs.queue[(uint32_t)*bs.cursor % (uint32_t)bs.len];
+        key0 = (uint32_t)b.seed;
+        key1 = (uint32_t)(b.seed >> 32);
+        if (bs.nodes_from_batch) nodes = b.seeds;
     }
     const bool active = r < nn;
     int32_t v = -1, id = -1;

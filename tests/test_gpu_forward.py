@@ -448,6 +448,31 @@ def test_graph_replay_of_queued_batches_equals_direct_calls():
                 assert torch.equal(out3[j], want[(first + j) % 5]), f"concat={concat} multi-batch replay, batch {(first + j) % 5}"
 
 
+@pytest.mark.parametrize("concat", [False, True])
+def test_queued_forwards_read_the_descriptor_at_the_cursor(concat):
+    """The sampler's queue read, descriptor = queue[cursor % len], without a graph around it: five forward_queued calls on a
+    ring of three batches (the cursor wraps) each equal, bit for bit, forward(seeds[i % 3], seed=keys[i % 3]) on a second
+    engine over the same tensors."""
+    graph = rmat_graph(10, 8_000, seed=2)
+    gen = torch.Generator().manual_seed(6)
+    m = 2 if concat else 1
+    table = torch.randn(graph.num_nodes, 64, generator=gen).to(DEV)
+    w1 = (torch.randn(32, m * 64, generator=gen) / 8).to(DEV)
+    w2 = (torch.randn(32, m * 32, generator=gen) / 6).to(DEV)
+    rowptr, col = graph.to(DEV)
+    rs = np.random.default_rng(8)
+    seeds = torch.from_numpy(np.stack([rs.choice(graph.num_nodes, 64, replace=False) for _ in range(3)]).astype(np.int32)).to(DEV)
+    keys = [21, 2**63 + 22, 23]
+    direct = TwoHopEngine(rowptr, col, table, w1, w2, 5, 5, concat=concat, max_batch=64)
+    eng = TwoHopEngine(rowptr, col, table, w1, w2, 5, 5, concat=concat, max_batch=64)
+    eng.set_queue(seeds, keys)
+    out = torch.empty(64, 32, device=DEV)
+    for i in range(5):
+        eng.forward_queued(out)
+        want = direct.forward(seeds[i % 3], seed=keys[i % 3])
+        assert torch.equal(out.view(torch.int32), want.view(torch.int32)), f"concat={concat} call {i}"      # the bits, NaN rows included
+
+
 
 
 def test_integration_md_ctypes_stub():
