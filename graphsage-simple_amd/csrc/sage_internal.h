@@ -103,6 +103,20 @@ int sage_launch_layer_dense(const sage_rows_t& agg, const sage_lists_t& rows, co
 bool sage_layer1_phase_supported(int32_t d0, int32_t h1, int32_t k);
 int sage_launch_layer1_phase(const sage_rows_t& src, const sage_lists_t& l, const sage_contract_t& c, hipStream_t st);
 
+// Classifier head (sage_head.hip): scores, cross-entropy and its gradients of one batch.  The row kernel takes this struct by value.
+// part_w / part_loss: the per-range partials in the caller's workspace ([ranges][C * dim] and [ranges]); part_w == NULL: no weight
+// gradient.  The launcher runs the fixed-order reduce into grad_w / loss when either is asked for.  Arguments are validated by the caller.
+struct sage_head_t {
+    const float* emb; int64_t lde; int32_t dim;
+    const float* w_cls; int64_t ldw; int32_t num_classes;
+    const int64_t* labels = nullptr; int32_t n; float scale = 1.f;
+    float* scores = nullptr; int64_t lds = 0; int32_t* pred = nullptr;
+    float* grad_emb = nullptr; int64_t ldg = 0;
+    float* part_w = nullptr; float* part_loss = nullptr;
+    float* grad_w = nullptr; int64_t ldgw = 0; float* loss = nullptr;
+};
+int sage_launch_xent_head(const sage_head_t& h, hipStream_t st);
+
 // Measurement hook (sage_gather.hip): set by the thread that is about to launch the layer-1 gather, cleared right after.
 struct sage_ext_launch_t { void* start; void* stop; };
 extern thread_local const sage_ext_launch_t* sage_ext_launch;

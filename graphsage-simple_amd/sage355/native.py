@@ -6,7 +6,7 @@ There is NO fallback: if the library is missing or a call fails, this raises.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char_p, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_char_p, c_float, c_int32, c_int64, c_size_t, c_uint32, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SAGE355_LIB") or os.path.join(os.path.dirname(_HERE), "lib", "libsage355.so")   # env: A/B another build
@@ -15,8 +15,9 @@ CSRC_DIR = os.path.join(os.path.dirname(_HERE), "csrc")
 ACT_RELU, ACT_SIGMOID, ACT_NONE = 0, 1, 2
 TAG_INNER, TAG_OUTER, TAG_INNER_SELF = 1, 2, 3
 MAX_FANOUT = 64
-ABI_VERSION = 8
+ABI_VERSION = 9
 CSR_MEAN_CHUNK = 512                                          # SAGE_CSR_MEAN_CHUNK
+HEAD_MAX_CLASSES, HEAD_MAX_DIM, HEAD_RANGE_ROWS = 64, 256, 64  # SAGE_HEAD_MAX_CLASSES / _MAX_DIM / _RANGE_ROWS
 EINVAL, EUNSUPPORTED, ELAUNCH, ENOSPACE = -1, -2, -3, -4      # include/sage355.h
 
 # every symbol include/sage355.h declares (tests check the library exports each one)
@@ -34,6 +35,7 @@ SYMBOLS = [
     "sage_pipe_join", "sage_pipe_fork", "sage_pipe_reset", "sage_pipe_set_threads", "sage_pipe_flush",
     "sage_pipe_express_count", "sage_csr_mean_workspace_bytes", "sage_csr_mean",
     "sage_layer1_fused", "sage_layer1_fused_supported",
+    "sage_xent_head_supported", "sage_xent_head_workspace_bytes", "sage_xent_head",
 ]
 PIPE_MAX_DEPTH = 8
 
@@ -147,6 +149,9 @@ def lib():
     L.sage_csr_mean.argtypes = [P, P, I64, P, I32, I64, P, I64, I64, I32, I32, P, P, I64, P, c_size_t, P]
     L.sage_layer1_fused_supported.argtypes = [I32, I32, I32]
     L.sage_layer1_fused.argtypes = [P, I64, I32, P, P, I32, I32, P, P, P, P, I64, P, I32, I32, P, I64, P]
+    L.sage_xent_head_supported.argtypes = [I32, I32]
+    L.sage_xent_head_workspace_bytes.argtypes = [I32, I32, I32]
+    L.sage_xent_head.argtypes = [P, I64, I32, P, I64, I32, P, I32, c_float, P, I64, P, P, P, I64, P, I64, P, c_size_t, P]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name == "sage_prepared_weight_bytes" or name.endswith("_workspace_bytes"):

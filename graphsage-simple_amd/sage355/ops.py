@@ -298,3 +298,78 @@ def csr_mean(rowptr, col, table, nodes=None, self_loop=False, any_nonempty=None,
                                     native.ptr(out), ldo, native.ptr(workspace), workspace.numel(), native.stream_handle())
     native.check(rc, "csr_mean")
     return out
+
+
+def xent_head_supported(dim, num_classes):
+    return bool(native.lib().sage_xent_head_supported(int(dim), int(num_classes)))
+
+
+def xent_head_workspace_bytes(n, dim, num_classes):
+    """Bytes of the workspace sage_xent_head needs (host arithmetic; 0 = shape out of range)."""
+    return int(native.lib().sage_xent_head_workspace_bytes(int(n), int(dim), int(num_classes)))
+
+
+def xent_head(emb, w_cls, labels=None, scale=None, scores=False, pred=False, grads=True, workspace=None, out=None):
+    """model.py:59-69 + model.py:249: scores = emb . w_cls^T, CrossEntropyLoss and its gradients in one call (sage_xent_head).
+    emb [n, dim], w_cls [C, dim] (the reference Parameter), labels int64 [n] or None (the inference form: scores / pred only).
+    scale: factor of the summed loss, default 1 / n (a data-parallel shard passes 1 / global_batch).
+    scores / pred / grads: which outputs to produce -- with labels the loss always is; grads = grad_emb and grad_w.
+    out: dict of tensors to write into instead of fresh ones (keys as returned; rows beyond n are left alone).
+    -> dict with the requested ones of scores [n, C], pred int32 [n], loss [1], grad_emb [n, dim], grad_w [C, dim]."""
+    _need_gpu()
+    emb, lde = _row_major(emb, "emb")
+    w_cls, ldw = _row_major(w_cls, "w_cls")
+    n, dim = emb.shape
+    c = w_cls.shape[0]
+    if w_cls.shape[1] != dim:
+        raise native.SageError(f"xent_head: w_cls is {tuple(w_cls.shape)}, emb is {dim} wide")
+    if n < 1:
+        raise native.SageError("xent_head: no rows")
+    if not xent_head_supported(dim, c):
+        raise native.SageError(f"xent_head: no kernel for dim = {dim}, num_classes = {c}")
+    if labels is None:
+        if grads:
+            raise native.SageError("xent_head: gradients need labels")
+    else:
+        _chk(labels, torch.int64, "labels", 1)
+        if labels.shape[0] != n:
+            raise native.SageError(f"xent_head: {labels.shape[0]} labels for {n} rows")
+    dev = emb.device
+    out = dict(out or {})
+    res = {}
+
+    def take(name, want, shape, dtype=torch.float32):
+        if not want:
+            return None
+        t = out.get(name)
+        if t is None:
+            t = torch.empty(shape, dtype=dtype, device=dev)
+        elif not t.is_cuda or t.dtype != dtype or t.dim() != len(shape) or t.shape[0] < shape[0] or tuple(t.shape[1:]) != tuple(shape[1:]):
+            raise native.SageError(f"xent_head: out[{name!r}] is {tuple(t.shape)} {t.dtype}, expected {tuple(shape)} {dtype}")
+        res[name] = t[:shape[0]]
+        return res[name]
+
+    t_scores = take("scores", scores, (n, c))
+    t_pred = take("pred", pred, (n,), torch.int32)
+    t_loss = take("loss", labels is not None, (1,))
+    t_gemb = take("grad_emb", grads, (n, dim))
+    t_gw = take("grad_w", grads, (c, dim))
+    lds = ldg = ldgw = 0
+    if t_scores is not None:
+        t_scores, lds = _row_major(t_scores, "scores")
+    if t_gemb is not None:
+        t_gemb, ldg = _row_major(t_gemb, "grad_emb")
+        t_gw, ldgw = _row_major(t_gw, "grad_w")
+    if t_pred is not None:
+        _chk(t_pred, torch.int32, "pred", 1)
+    need = xent_head_workspace_bytes(n, dim, c)
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    elif not workspace.is_cuda or workspace.dtype != torch.uint8 or workspace.numel() < need:
+        raise native.SageError(f"xent_head: workspace must be a uint8 device tensor of >= {need} bytes")
+    rc = native.lib().sage_xent_head(native.ptr(emb), lde, dim, native.ptr(w_cls), ldw, c, native.ptr(labels), n,
+                                     float(1.0 / n if scale is None else scale), native.ptr(t_scores), lds, native.ptr(t_pred),
+                                     native.ptr(t_loss), native.ptr(t_gemb), ldg, native.ptr(t_gw), ldgw, native.ptr(workspace),
+                                     workspace.numel(), native.stream_handle())
+    native.check(rc, "xent_head")
+    return res

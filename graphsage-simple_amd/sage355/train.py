@@ -157,8 +157,16 @@ class EngineTrainer:
     runs of one schedule give the same bits."""
 
     def __init__(self, rowptr, col, table, num_classes, hidden1=50, hidden2=128, num_sample1=10, num_sample2=10, gcn=True, lr=0.7,
-                 max_batch=256, agg_self_loop=False, relabel=None):
+                 max_batch=256, agg_self_loop=False, relabel=None, head="torch"):
+        """head: "torch" -- the classifier, its loss and their gradients as stock torch ops (the default: its bits are the recorded
+        w_cls trajectories); "native" -- one sage_xent_head call, its sums in an order fixed by the shape.  With the
+        native head the loss and the classifier gradient that grads() returns live in buffers of the trainer, rewritten by its next call."""
         from . import native, ops
+        if head not in ("torch", "native"):
+            raise native.SageError(f"EngineTrainer: head = {head!r}, expected 'torch' or 'native'")
+        if head == "native" and not ops.xent_head_supported(hidden2, num_classes):
+            raise native.SageError(f"EngineTrainer: head='native' has no kernel for hidden2 = {hidden2}, num_classes = {num_classes}")
+        self.head = head
         from .engine import TwoHopEngine
         dev = table.device
         d0 = table.shape[1]
@@ -181,6 +189,17 @@ class EngineTrainer:
         self._native, self._ops = native, ops
         self._out_q = None
         self._step_graph = None
+        self._head = None
+        if head == "native":
+            self._head_reserve(max_batch)
+
+    def _head_reserve(self, rows):
+        """Outputs and workspace of the native head for batches of up to `rows` seeds: allocated here, never inside a (captured) step."""
+        c, h2 = self.w_cls.shape
+        dev = self.w_cls.device
+        self._head = {"rows": int(rows), "loss": torch.zeros(1, device=dev), "grad_emb": torch.empty(rows, h2, device=dev),
+                      "grad_w": torch.empty(c, h2, device=dev), "pred": torch.empty(rows, dtype=torch.int32, device=dev),
+                      "workspace": torch.empty(self._ops.xent_head_workspace_bytes(rows, h2, c), dtype=torch.uint8, device=dev)}
 
     def parameters(self):
         return [self.w1, self.w2, self.w_cls]
@@ -191,6 +210,17 @@ class EngineTrainer:
 
     def scores(self, seeds, key=0):
         return self.embed(seeds, key) @ self.w_cls.t()
+
+    def predict(self, seeds, key=0):
+        """int32 [B]: the class of the highest score (model.py:256, `val_output.data.numpy().argmax(axis=1)`).  The native head computes
+        it from the embeddings in one launch (the inference form of sage_xent_head); the torch head takes scores().argmax(1)."""
+        if self.head != "native":
+            return self.scores(seeds, key).argmax(1).to(torch.int32)
+        emb = self.embed(seeds, key)
+        if emb.shape[0] > self._head["rows"]:
+            self._head_reserve(emb.shape[0])
+        hd = self._head
+        return self._ops.xent_head(emb, self.w_cls, grads=False, pred=True, workspace=hd["workspace"], out={"pred": hd["pred"]})["pred"].clone()
 
     def grads(self, seeds, labels, key, global_batch=None):
         """loss (device scalar) and the gradients of (w1, w2, w_cls) for one batch; nothing is updated.
@@ -205,6 +235,18 @@ class EngineTrainer:
         else:
             b = seeds.shape[0]
             out = e.forward(seeds, seed=key)                               # sample, frontier, sample, layer 1, layer 2
+        if self.head == "native":
+            # classifier + loss + their gradients in one call (model.py:59-69): no autograd, and the sum over the batch runs in 64-row
+            # ranges added in range order, so w_cls keeps its run-to-run bit identity at any batch size
+            if b > self._head["rows"]:
+                self._head_reserve(b)                                      # never while capturing: capture_step's batch is <= max_batch
+            hd = self._head
+            r = self._ops.xent_head(out, self.w_cls, labels, scale=1.0 / float(b if global_batch is None else global_batch),
+                                    workspace=hd["workspace"], out=hd)
+            g_w1, g_w2 = e.backward_weights(out, r["grad_emb"])
+            # eager: the caller may keep the loss of every step (run_engine_training does); queued: the captured step copies it at once
+            loss = r["loss"][0]
+            return (loss if seeds is None else loss.clone()), (g_w1, g_w2, r["grad_w"])
         # classifier + loss + their gradients: stock torch on the same stream (model.py:59-69)
         # The classifier's weight gradient is a [C, B] x [B, H2] product whose reduction runs over the BATCH: for B >= 1024 the BLAS behind
         # torch.mm may split it and add the pieces with atomics, and two runs of one schedule then differ in the last bits of w_cls (seen
@@ -290,7 +332,7 @@ class EngineTrainer:
 
 
 def run_engine_training(graph, feat_data, labels, num_classes, seed=1, epochs=1, batch_size=128, ref_batching=False, lr=0.7,
-                        sample_seed=0, hidden1=50, hidden2=128, num_sample1=10, num_sample2=10, gcn=True):
+                        sample_seed=0, hidden1=50, hidden2=128, num_sample1=10, num_sample2=10, gcn=True, head="torch"):
     """run_model (model.py:184-259) on the engine path: same split, shuffles, batching and optimiser as run_training above, every
     step through EngineTrainer.  -> dict(f1_micro, f1_macro, mean_step_time, losses, trainer)."""
     from sklearn.metrics import f1_score
@@ -303,7 +345,8 @@ def run_engine_training(graph, feat_data, labels, num_classes, seed=1, epochs=1,
     val = rand_indices[int(0.1 * n):int(0.2 * n)]
     train = list(rand_indices[int(0.2 * n):])
     top = len(train) if ref_batching else batch_size
-    tr = EngineTrainer(rowptr, col, table, num_classes, hidden1, hidden2, num_sample1, num_sample2, gcn=gcn, lr=lr, max_batch=max(top, len(val)))
+    tr = EngineTrainer(rowptr, col, table, num_classes, hidden1, hidden2, num_sample1, num_sample2, gcn=gcn, lr=lr, max_batch=max(top, len(val)),
+                       head=head)
     labels_dev = torch.as_tensor(np.asarray(labels).reshape(-1), dtype=torch.int64).to(dev)
     shuffler = random.Random(seed)
     losses, key = [], int(sample_seed) << 20
@@ -322,7 +365,8 @@ def run_engine_training(graph, feat_data, labels, num_classes, seed=1, epochs=1,
     torch.cuda.synchronize()
     elapsed = time.time() - t0
     with torch.no_grad():
-        pred = tr.scores(torch.as_tensor(val.astype(np.int32)).to(dev), key=key).argmax(1).cpu().numpy()
+        val_ids = torch.as_tensor(val.astype(np.int32)).to(dev)
+        pred = (tr.predict(val_ids, key=key) if head == "native" else tr.scores(val_ids, key=key).argmax(1)).cpu().numpy()
     truth = np.asarray(labels)[val].reshape(-1)
     return {"f1_micro": float(f1_score(truth, pred, average="micro")), "f1_macro": float(f1_score(truth, pred, average="macro")),
             "mean_step_time": elapsed / max(steps, 1), "losses": [float(x) for x in losses], "trainer": tr}

@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define SAGE_ABI_VERSION 8
+#define SAGE_ABI_VERSION 9
 
 #define SAGE_OK            0
 #define SAGE_EINVAL       -1   /* bad argument (NULL, size, alignment, range) */
@@ -497,6 +497,47 @@ int sage_pipe_flush(sage_pipe_t* p);
  * once).  Same kernels and workspace, bit-identical results; never inside a stream capture; needs four distinct role streams;
  * SAGE_PIPE_EXPRESS=0 (environment, read once) turns it off.  Returns how many batches of this pipe took it so far (-1: NULL pipe). */
 int64_t sage_pipe_express_count(const sage_pipe_t* p);
+
+/* ---------------------------------------------------------------------------
+ * Classifier head (ABI 9): SupervisedGraphSage's scores, CrossEntropyLoss and the three gradients that follow
+ * (model.py:59-69: `scores = self.weight.mm(embeds)`, `self.xent(scores.t(), labels)`; model.py:249: `loss.backward()`)
+ * as one row-tiled kernel plus one fixed-order reduce.  Per row r of emb [n, dim], with w_cls [C, dim] the reference's Parameter:
+ *   s[r, c] = sum_d emb[r, d] * w_cls[c, d]        m_r = max_c s[r, c]        lse_r = m_r + log sum_c exp(s[r, c] - m_r)
+ *   loss           = scale * sum_r (lse_r - s[r, labels[r]])        (scale = 1 / n, or 1 / global_batch for a data-parallel shard)
+ *   g[r, c]        = scale * (softmax(s[r, :])[c] - [c == labels[r]])
+ *   grad_emb[r, :] = sum_c g[r, c] * w_cls[c, :]
+ *   grad_w[c, :]   = sum_r g[r, c] * emb[r, :]      STORED, not accumulated: the caller zeroes nothing, and what grad_w and the
+ *                                                   workspace held before the call does not matter
+ *   pred[r]        = first index of the maximum of s[r, :]; a NaN counts as the maximum (torch.argmax)
+ * A row whose label lies outside [0, C) adds nothing to the loss and has g[r, :] = 0; the label is never used as an index; its
+ * scores and pred are still written.  labels == NULL is the inference form: loss, grad_emb and grad_w must be NULL too and only
+ * scores / pred are produced.  Every output is nullable.  NaN and Inf propagate as the arithmetic dictates, nothing is clamped.
+ * Columns [dim, ldg) of grad_emb, [dim, ldgw) of grad_w and [C, lds) of scores are not written; columns [dim, lde) of emb are not read.
+ * Order of the sums: no float atomics, every sum runs in an order fixed by (n, C, dim) alone.  The rows are cut into ranges of
+ * SAGE_HEAD_RANGE_ROWS; each range STORES its partial [C, dim] tile of grad_w and its partial loss in the workspace, terms in
+ * ascending row order; a second kernel adds the partials in range order and stores grad_w and loss.  scores, pred and grad_emb of
+ * a row depend on that row, w_cls, its label and scale only: row r of a call with n rows has the bits of row r of a call with
+ * more rows.  Everything is fp32, the dots are plain FMA chains in ascending d / c / r.
+ * Host validation, before any launch: NULL emb / w_cls / workspace, n < 1, a leading dimension shorter than its width, loss or
+ * gradients requested without labels: SAGE_EINVAL; dim outside [4, SAGE_HEAD_MAX_DIM] or dim % 4 != 0, num_classes outside
+ * [1, SAGE_HEAD_MAX_CLASSES], lde / ldw / ldg / ldgw not a multiple of 4, emb / w_cls / grad_emb / grad_w / workspace not 16-byte
+ * aligned: SAGE_EUNSUPPORTED; short workspace: SAGE_ENOSPACE.  sage_xent_head_supported and sage_xent_head_workspace_bytes are
+ * host arithmetic (the latter 0 for an unsupported shape or n < 1).
+ * ------------------------------------------------------------------------- */
+#define SAGE_HEAD_MAX_CLASSES 64
+#define SAGE_HEAD_MAX_DIM     256
+#define SAGE_HEAD_RANGE_ROWS  64      /* rows per partial: a constant, NOT a tunable (it fixes the order of the sums) */
+int    sage_xent_head_supported(int32_t dim, int32_t num_classes);
+size_t sage_xent_head_workspace_bytes(int32_t n, int32_t dim, int32_t num_classes);
+int    sage_xent_head(const float* emb, int64_t lde, int32_t dim,            /* [n, dim]                      */
+                      const float* w_cls, int64_t ldw, int32_t num_classes,   /* [C, dim], the reference Parameter */
+                      const int64_t* labels /* [n], nullable */, int32_t n, float scale,
+                      float* scores   /* [n, C]   nullable */, int64_t lds,
+                      int32_t* pred   /* [n]      nullable */,
+                      float* loss     /* [1]      nullable */,
+                      float* grad_emb /* [n, dim] nullable */, int64_t ldg,
+                      float* grad_w   /* [C, dim] nullable, STORED */, int64_t ldgw,
+                      void* workspace, size_t workspace_bytes, sage_stream_t stream);
 
 /* (ABI 5: sage_set_option is gone with the only option it carried -- the producer / consumer contraction kernel of round 3 was measured
  * slower inside the pipeline and deleted in round 4.) */
