@@ -71,6 +71,11 @@ struct sage_sample_t {
     const sage_resolve_t* resolve = nullptr;
 };
 int sage_launch_sample(const sage_sample_t& s, hipStream_t st);
+// The same hop for k up to SAGE_MAX_FANOUT_WIDE, one wave per node (sage_sample_wide.hip).  Takes the members of a plain call only:
+// a batch queue, seed map, resolve job, row offset or second tag is refused (SAGE_EINVAL).
+int sage_launch_sample_wide(const sage_sample_t& s, hipStream_t st);
+// Host check of a frontier that is about to take up to `inserts` ids (sage_sample.hip)
+int sage_check_frontier(const sage_frontier_t* f, int64_t inserts);
 
 // Both hops of a forward as one launch (see sample_fused_kernel).  `seed_rows` = batch for the concat encoder (rows [0, batch) of
 // S1 are the seeds themselves), else 0.

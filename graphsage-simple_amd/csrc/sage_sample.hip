@@ -127,6 +127,8 @@ SampleLaunch pick_by_fanout(int k) {
 
 }  // namespace
 
+int sage_check_frontier(const sage_frontier_t* f, int64_t inserts) { return check_frontier(f, inserts); }
+
 // Internal launcher shared with sage_forward.hip (sage_sample_t: sage_internal.h)
 int sage_launch_sample(const sage_sample_t& s, hipStream_t st) {
     if (s.n == 0) return SAGE_OK;

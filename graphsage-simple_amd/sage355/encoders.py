@@ -39,9 +39,11 @@ need one call on either Encoder of the pair before the next forward:
 
 Sampling: the device sampler draws k distinct uniform neighbours per node
 (all of them when deg < k), the reference's rule (aggregators.py:42-46), from a
-counter-based generator.  The two device-sampler paths (``_forward_two_hop``,
-``_forward_table``) take ONE 64-bit value from Python's global ``random`` per
-``forward`` as the key, so ``random.seed(s)`` (model.py:193) still makes a run
+counter-based generator, for any fanout up to ``native.MAX_FANOUT_WIDE`` (1024;
+above ``native.MAX_FANOUT`` the stack runs from the public operators,
+``_forward_two_hop_ops``).  The device-sampler paths (``_forward_two_hop``,
+``_forward_two_hop_ops``, ``_forward_table``) take ONE 64-bit value from
+Python's global ``random`` per ``forward`` as the key, so ``random.seed(s)`` (model.py:193) still makes a run
 reproducible, but (a) the sets differ from the reference's for the same seed and
 (b) the global stream is advanced by one ``getrandbits(64)`` per call instead of
 one ``random.sample`` per node -- a program that interleaves its own draws from
@@ -58,7 +60,7 @@ import torch
 import torch.nn as nn
 from torch.nn import init
 
-from . import autograd, native, ops
+from . import autograd, native, ops, twohop_ops
 from .aggregators import MeanAggregator
 from .engine import TwoHopEngine
 from .graph import csr_from_adj_lists
@@ -294,6 +296,17 @@ class Encoder(nn.Module):
                 and self.num_sample is not None and base.num_sample is not None
                 and 1 <= self.num_sample <= native.MAX_FANOUT and 1 <= base.num_sample <= native.MAX_FANOUT)
 
+    def _can_two_hop_ops(self):
+        """The stack _can_fuse_two_hop describes, with a fanout the engine's samplers do not take (above native.MAX_FANOUT, up to
+        native.MAX_FANOUT_WIDE): it runs from the public operators (twohop_ops.two_hop_forward)."""
+        base = getattr(self, "base_model", None)
+        return (self.fuse_base_model and isinstance(base, Encoder) and base._is_table()
+                and isinstance(self.aggregator, MeanAggregator) and isinstance(base.aggregator, MeanAggregator)
+                and self.gcn == base.gcn and self._agg_self_loop() == base._agg_self_loop()
+                and self.num_sample is not None and base.num_sample is not None
+                and 1 <= self.num_sample <= native.MAX_FANOUT_WIDE and 1 <= base.num_sample <= native.MAX_FANOUT_WIDE
+                and max(self.num_sample, base.num_sample) > native.MAX_FANOUT)
+
     # ------------------------------------------------------------------ forward
     def forward(self, nodes):
         """Generates embeddings for a batch of nodes.  nodes -- list / array / LongTensor of node ids.
@@ -311,7 +324,9 @@ class Encoder(nn.Module):
         table_trains = grad and self._can_fuse_two_hop() and self.base_model.features.weight.requires_grad
         if self._can_fuse_two_hop() and not table_trains:
             out = self._forward_two_hop(nodes, training)
-        elif self._is_table() and self.num_sample is not None and self.num_sample <= native.MAX_FANOUT \
+        elif self._can_two_hop_ops():
+            out = self._forward_two_hop_ops(nodes)
+        elif self._is_table() and self.num_sample is not None and self.num_sample <= native.MAX_FANOUT_WIDE \
                 and isinstance(self.aggregator, MeanAggregator):
             out = self._forward_table(nodes)
         else:
@@ -369,19 +384,37 @@ class Encoder(nn.Module):
             return autograd.two_hop(base.weight, self.weight, self._engine, ids, sampler_key)
         return self._engine.forward(nodes, seed=sampler_key)
 
+    def _table_dev(self):
+        """The device tensor the per-operator paths read the feature table from."""
+        tw = self.features.weight
+        if torch.is_grad_enabled() and tw.requires_grad and not tw.is_cuda:
+            return tw.to("cuda", torch.float32)              # differentiable copy: the gradient flows back to the host table
+        return self._on_device(tw, "table")
+
+    def _forward_two_hop_ops(self, nodes):
+        """Both layers from the public operators (twohop_ops.two_hop_forward): the stack of _forward_two_hop with a fanout above
+        native.MAX_FANOUT.  The sets come from the device sampler's stream under one key per forward, as on the engine path."""
+        base = self.base_model
+        dev = torch.device("cuda")
+        table = base._table_dev()
+        n = table.shape[0]
+        probe = nodes if isinstance(nodes, (list, tuple, np.ndarray)) else None
+        rp1, c1 = _device_csr(base.adj_lists, n, dev, probe)
+        rp2, c2 = (rp1, c1) if self.adj_lists is base.adj_lists else _device_csr(self.adj_lists, n, dev, probe)
+        ids = ops.as_ids(nodes, dev, n)
+        return twohop_ops.two_hop_forward(rp1, c1, table, base._weight_dev(), self._weight_dev(), ids, base.num_sample, self.num_sample,
+                                          random.getrandbits(64), concat=not self.gcn, agg_self_loop=self._agg_self_loop(),
+                                          act1=base._act(), act2=self._act(), rowptr_outer=rp2, col_outer=c2)
+
     def _forward_table(self, nodes):
         """One layer over a raw feature table (encoders.py:47-62 with features = nn.Embedding)."""
         dev = torch.device("cuda")
-        tw = self.features.weight
-        if torch.is_grad_enabled() and tw.requires_grad and not tw.is_cuda:
-            table = tw.to("cuda", torch.float32)             # differentiable copy: the gradient flows back to the host table
-        else:
-            table = self._on_device(tw, "table")
+        table = self._table_dev()
         rowptr, col = _device_csr(self.adj_lists, table.shape[0], dev, nodes if isinstance(nodes, (list, tuple, np.ndarray)) else None)
         ids = ops.as_ids(nodes, dev, table.shape[0])
         any_nonempty = torch.zeros(1, dtype=torch.int32, device=dev)
-        nbr, cnt, _, _ = ops.sample_neighbors(rowptr, col, ids, self.num_sample, random.getrandbits(64), ops.TAG_INNER,
-                                              any_nonempty=any_nonempty)
+        nbr, cnt, _, _ = ops.sample_neighbors_any(rowptr, col, ids, self.num_sample, random.getrandbits(64), ops.TAG_INNER,
+                                                  any_nonempty=any_nonempty)
         self_row = ids if self._agg_self_loop() else None
         w = self._weight_dev()
         agg = autograd.gather_mean(table, nbr, cnt, any_nonempty, None, self_row)

@@ -15,6 +15,7 @@ CSRC_DIR = os.path.join(os.path.dirname(_HERE), "csrc")
 ACT_RELU, ACT_SIGMOID, ACT_NONE = 0, 1, 2
 TAG_INNER, TAG_OUTER, TAG_INNER_SELF = 1, 2, 3
 MAX_FANOUT = 64
+MAX_FANOUT_WIDE = 1024                                       # SAGE_MAX_FANOUT_WIDE: sage_sample_neighbors_wide
 ABI_VERSION = 9
 CSR_MEAN_CHUNK = 512                                          # SAGE_CSR_MEAN_CHUNK
 HEAD_MAX_CLASSES, HEAD_MAX_DIM, HEAD_RANGE_ROWS = 64, 256, 64  # SAGE_HEAD_MAX_CLASSES / _MAX_DIM / _RANGE_ROWS
@@ -23,7 +24,7 @@ EINVAL, EUNSUPPORTED, ELAUNCH, ENOSPACE = -1, -2, -3, -4      # include/sage355.
 # every symbol include/sage355.h declares (tests check the library exports each one)
 SYMBOLS = [
     "sage_abi_version", "sage_last_error", "sage_build_arch", "sage_frontier_reset", "sage_sample_neighbors",
-    "sage_frontier_insert", "sage_gather_mean", "sage_linear_act", "sage_layer_forward", "sage_layer_forward_supported",
+    "sage_sample_neighbors_wide", "sage_frontier_insert", "sage_gather_mean", "sage_linear_act", "sage_layer_forward", "sage_layer_forward_supported",
     "sage_forward2_layout", "sage_forward2_init", "sage_forward2", "sage_forward2_profiled",
     "sage_linear_act_backward", "sage_gather_mean_backward",
     "sage_linear_act_backward_workspace_bytes", "sage_linear_act_backward_ws",
@@ -110,6 +111,7 @@ def lib():
     L.sage_frontier_reset.argtypes = [POINTER(Frontier), I32, P]
     L.sage_sample_neighbors.argtypes = [P, P, I64, P, I32, P, I32, c_uint64, c_uint32, P, P, P,
                                         POINTER(Frontier), I32, P, P, P]
+    L.sage_sample_neighbors_wide.argtypes = L.sage_sample_neighbors.argtypes
     L.sage_frontier_insert.argtypes = [P, P, I32, P, I32, P, POINTER(Frontier), P, P, P]
     L.sage_gather_mean.argtypes = [P, I64, I64, I32, P, P, I32, I32, P, P, P, P, P, I64, P]
     L.sage_linear_act.argtypes = [P, I64, P, P, I64, I32, P, I64, I32, I32, I32, P, P, I64, P]

@@ -93,10 +93,8 @@ class Frontier:
         return self.nodes[: self.size()]
 
 
-def sample_neighbors(rowptr, col, nodes, k, seed, tag=TAG_OUTER, n_dev=None, frontier=None, insert_self=False,
-                     any_nonempty=None, out_nbr=None, out_cnt=None):
-    """encoders.py:47 + aggregators.py:42-48 (+52-53 with a frontier).
-    -> (nbr int32 [n,k], cnt int32 [n], nbr_slot or None, self_slot or None)."""
+def _sample(entry, rowptr, col, nodes, k, seed, tag, n_dev, frontier, insert_self, any_nonempty, out_nbr, out_cnt):
+    """Body of the two sampler wrappers: `entry` names the C entry point (same argument list)."""
     _need_gpu()
     _chk(rowptr, torch.int64, "rowptr", 1)
     _chk(col, torch.int32, "col", 1)
@@ -106,16 +104,37 @@ def sample_neighbors(rowptr, col, nodes, k, seed, tag=TAG_OUTER, n_dev=None, fro
     nbr = torch.empty((n, k), dtype=torch.int32, device=dev) if out_nbr is None else _chk(out_nbr, torch.int32, "out_nbr")
     cnt = torch.empty(n, dtype=torch.int32, device=dev) if out_cnt is None else _chk(out_cnt, torch.int32, "out_cnt")
     if nbr.numel() < n * k or cnt.numel() < n:
-        raise native.SageError("sample_neighbors: output buffers too small")
+        raise native.SageError(f"{entry}: output buffers too small")
     nbr_slot = torch.empty((n, k), dtype=torch.int32, device=dev) if frontier is not None else None
     self_slot = torch.empty(n, dtype=torch.int32, device=dev) if (frontier is not None and insert_self) else None
-    rc = native.lib().sage_sample_neighbors(
+    rc = getattr(native.lib(), "sage_" + entry)(
         native.ptr(rowptr), native.ptr(col), rowptr.shape[0] - 1, native.ptr(nodes), n, native.ptr(n_dev), int(k),
         int(seed) & 0xFFFFFFFFFFFFFFFF, int(tag), native.ptr(nbr), native.ptr(cnt), native.ptr(any_nonempty),
         frontier.c if frontier is not None else None, 1 if insert_self else 0, native.ptr(nbr_slot),
         native.ptr(self_slot), native.stream_handle())
-    native.check(rc, "sample_neighbors")
+    native.check(rc, entry)
     return nbr, cnt, nbr_slot, self_slot
+
+
+def sample_neighbors(rowptr, col, nodes, k, seed, tag=TAG_OUTER, n_dev=None, frontier=None, insert_self=False,
+                     any_nonempty=None, out_nbr=None, out_cnt=None):
+    """encoders.py:47 + aggregators.py:42-48 (+52-53 with a frontier), k <= native.MAX_FANOUT.
+    -> (nbr int32 [n,k], cnt int32 [n], nbr_slot or None, self_slot or None)."""
+    return _sample("sample_neighbors", rowptr, col, nodes, k, seed, tag, n_dev, frontier, insert_self, any_nonempty, out_nbr, out_cnt)
+
+
+def sample_neighbors_wide(rowptr, col, nodes, k, seed, tag=TAG_OUTER, n_dev=None, frontier=None, insert_self=False,
+                          any_nonempty=None, out_nbr=None, out_cnt=None):
+    """The same hop for any k <= native.MAX_FANOUT_WIDE (sage_sample_neighbors_wide: one wave per node).  Same draw: for
+    k <= native.MAX_FANOUT the outputs equal sample_neighbors' bit for bit."""
+    return _sample("sample_neighbors_wide", rowptr, col, nodes, k, seed, tag, n_dev, frontier, insert_self, any_nonempty, out_nbr, out_cnt)
+
+
+def sample_neighbors_any(rowptr, col, nodes, k, seed, tag=TAG_OUTER, n_dev=None, frontier=None, insert_self=False,
+                         any_nonempty=None, out_nbr=None, out_cnt=None):
+    """sample_neighbors for k <= native.MAX_FANOUT (a lane per slot: at small k several nodes share a wave), sample_neighbors_wide above."""
+    entry = "sample_neighbors" if int(k) <= native.MAX_FANOUT else "sample_neighbors_wide"
+    return _sample(entry, rowptr, col, nodes, k, seed, tag, n_dev, frontier, insert_self, any_nonempty, out_nbr, out_cnt)
 
 
 def frontier_insert(nbr, cnt, frontier, self_nodes=None, n_dev=None):

@@ -109,6 +109,28 @@ int sage_sample_neighbors(const int64_t* rowptr, const int32_t* col, int64_t num
                           int32_t* nbr_slot, int32_t* self_slot,
                           sage_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * sage_sample_neighbors_wide -- the same hop for the fanouts the entry above
+ * refuses: aggregators.py:42-48 takes ANY num_sample, this entry any k in
+ * [1, SAGE_MAX_FANOUT_WIDE].  Arguments, outputs and the draw are those of
+ * sage_sample_neighbors (one wave per node, lane l owns slots l, l+64, ...;
+ * draw i is word i&3 of Philox block i>>2, Floyd's walk over i = 0..k-1), so
+ * for k <= SAGE_MAX_FANOUT the two entries write identical nbr / cnt, and the
+ * sets stay a pure function of (seed, tag, v).  Ids outside [0, num_nodes)
+ * are empty rows; rows at or past min(*n_dev, n) are not written.  With a
+ * frontier: capacity >= 2 * n * (k + insert_self), rows start at the value
+ * *count had, the order of nodes[] is arbitrary.
+ * sage_frontier_insert and sage_forward2 keep the SAGE_MAX_FANOUT limit.
+ * ------------------------------------------------------------------------- */
+#define SAGE_MAX_FANOUT_WIDE 1024
+int sage_sample_neighbors_wide(const int64_t* rowptr, const int32_t* col, int64_t num_nodes,
+                               const int32_t* nodes, int32_t n, const int32_t* n_dev,
+                               int32_t k, uint64_t seed, uint32_t tag,
+                               int32_t* nbr, int32_t* cnt, int32_t* any_nonempty,
+                               const sage_frontier_t* frontier, int32_t insert_self,
+                               int32_t* nbr_slot, int32_t* self_slot,
+                               sage_stream_t stream);
+
 /* Insert already-sampled ids (e.g. sets injected by a caller, the reference's
  * num_sample=None path) into a frontier.  Same outputs as above. */
 int sage_frontier_insert(const int32_t* nbr, const int32_t* cnt, int32_t k,
