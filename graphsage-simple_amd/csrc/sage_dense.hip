@@ -156,7 +156,7 @@ __global__ __launch_bounds__((CONCAT && KP == 256) ? 512 : 256, 2) void dense_la
 }
 
 template <int KP, bool CONCAT>
-int launch(const DenseArgs& a, hipStream_t st) {
+int launch(const DenseArgs& a, hipStream_t st, sage_launch_events_t* ev) {
     constexpr bool KSPLIT = CONCAT && KP == 256;
     constexpr size_t lds = ((size_t)2 * (CONCAT ? 2 : 1) * 32 * (KP + 4) + (KSPLIT ? 4 * 16 * 64 : 0)) * sizeof(float);
     static std::atomic<bool> configured{false};           // role threads (and the express lane's thread) may launch the same kernel concurrently
@@ -174,7 +174,7 @@ int launch(const DenseArgs& a, hipStream_t st) {
 #define SAGE_DENSE_PER_CU 1
 #endif
     const int grid = min(sage_cdiv(a.n, 32), SAGE_DENSE_PER_CU * kNumCU);
-    SAGE_LAUNCH_TAIL((dense_layer_kernel<KP, CONCAT>), dim3(grid), dim3(KSPLIT ? 512 : 256), lds, st, a);
+    sage_launch(dense_layer_kernel<KP, CONCAT>, dim3(grid), dim3(KSPLIT ? 512 : 256), lds, st, ev, a);
     SAGE_CHECK_LAUNCH("dense_layer_kernel");
     return SAGE_OK;
 }
@@ -581,9 +581,9 @@ __global__ __launch_bounds__(512) void dense_bf16x3_kernel(const DenseArgs a) {
 }
 
 template <int KP, bool CONCAT, bool MP = false, bool PREP = false>
-int launch_bf16x3(const DenseArgs& a, hipStream_t st) {
+int launch_bf16x3(const DenseArgs& a, hipStream_t st, sage_launch_events_t* ev) {
     if constexpr (!PREP)
-        if (a.wsplit) return launch_bf16x3<KP, CONCAT, MP, true>(a, st);
+        if (a.wsplit) return launch_bf16x3<KP, CONCAT, MP, true>(a, st, ev);
     constexpr int KPASS = (CONCAT && KP < 256) ? 2 * KP : KP;
     constexpr size_t lds = (size_t)2 * 3 * 32 * (KPASS + 8) * 2 + (size_t)2 * 32 * (128 + 4) * sizeof(float) + 384;
     static std::atomic<bool> configured{false};           // role threads (and the express lane's thread) may launch the same kernel concurrently
@@ -600,7 +600,7 @@ int launch_bf16x3(const DenseArgs& a, hipStream_t st) {
     // and the other batch's latency-bound kernels get the remaining CUs to themselves (same-box A/B: 184-224 blocks
     // 81.3-81.9 us, 256 blocks 84.2, 160 blocks 83.1).
     const int grid = min(sage_cdiv(a.n, 32), sage_tunables().dense_blocks);
-    SAGE_LAUNCH_TAIL((dense_bf16x3_kernel<KP, CONCAT, MP, PREP>), dim3(grid), dim3(512), lds, st, a);
+    sage_launch(dense_bf16x3_kernel<KP, CONCAT, MP, PREP>, dim3(grid), dim3(512), lds, st, ev, a);
     SAGE_CHECK_LAUNCH("dense_bf16x3_kernel");
     return SAGE_OK;
 }
@@ -701,7 +701,7 @@ bool sage_layer_dense_supported(int32_t dim, int32_t out_dim) {
 }
 
 int sage_launch_layer_dense(const sage_rows_t& agg, const sage_lists_t& rows, const sage_self_t& self, const sage_contract_t& c,
-                            sage_finish_t fin, hipStream_t st) {
+                            sage_finish_t fin, hipStream_t st, sage_launch_events_t* ev) {
     const float* x = agg.table;
     const int64_t ldx = agg.ld;
     const int32_t dim = agg.dim, n = rows.n;
@@ -717,24 +717,24 @@ int sage_launch_layer_dense(const sage_rows_t& agg, const sage_lists_t& rows, co
                       concat ? (int)self.self_rows : n, self.self_index, nullptr, nullptr, c.weight, c.ldw, c.out_dim, c.act, c.out, c.ldo, fin,
                       (const uint4*)c.weight_prepared};
     const int kp = dim <= 64 ? 64 : dim <= 128 ? 128 : 256;
-    if (dim > 256) return concat ? launch_bf16x3<256, true, true>(a, st) : launch_bf16x3<256, false, true>(a, st);
+    if (dim > 256) return concat ? launch_bf16x3<256, true, true>(a, st, ev) : launch_bf16x3<256, false, true>(a, st, ev);
 #ifndef SAGE_DENSE_FP32
     if (!concat) {
-        if (kp == 64) return launch_bf16x3<64, false>(a, st);
-        if (kp == 128) return launch_bf16x3<128, false>(a, st);
-        return launch_bf16x3<256, false>(a, st);
+        if (kp == 64) return launch_bf16x3<64, false>(a, st, ev);
+        if (kp == 128) return launch_bf16x3<128, false>(a, st, ev);
+        return launch_bf16x3<256, false>(a, st, ev);
     }
-    if (kp == 64) return launch_bf16x3<64, true>(a, st);
-    if (kp == 128) return launch_bf16x3<128, true>(a, st);
-    return launch_bf16x3<256, true>(a, st);
+    if (kp == 64) return launch_bf16x3<64, true>(a, st, ev);
+    if (kp == 128) return launch_bf16x3<128, true>(a, st, ev);
+    return launch_bf16x3<256, true>(a, st, ev);
 #else
     if (!concat) {
-        if (kp == 64) return launch<64, false>(a, st);
-        if (kp == 128) return launch<128, false>(a, st);
-        return launch<256, false>(a, st);
+        if (kp == 64) return launch<64, false>(a, st, ev);
+        if (kp == 128) return launch<128, false>(a, st, ev);
+        return launch<256, false>(a, st, ev);
     }
-    if (kp == 64) return launch<64, true>(a, st);
-    if (kp == 128) return launch<128, true>(a, st);
-    return launch<256, true>(a, st);
+    if (kp == 64) return launch<64, true>(a, st, ev);
+    if (kp == 128) return launch<128, true>(a, st, ev);
+    return launch<256, true>(a, st, ev);
 #endif
 }

@@ -104,7 +104,7 @@ layer1_form_t layer1_form(const sage_model_t* m, const sage_ws_layout_t& L, cons
 
 int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes, const int32_t* seeds, int32_t batch,
                   uint64_t seed, float* out, int64_t ldo, sage_stream_t stream, void* const* ev, int stages = SAGE_STAGE_ALL,
-                  void* tail_event = nullptr) {
+                  void* tail_event = nullptr, void* const* gather_events = nullptr) {
     if (int rc = check_model(m)) return rc;
     SAGE_REQUIRE(m->rowptr1 && m->col1 && m->rowptr2 && m->col2 && m->table && m->w1 && m->w2, "forward2: NULL model array");
     const bool queued = m->queue != nullptr;
@@ -122,20 +122,10 @@ int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes
     }
     hipStream_t st = (hipStream_t)stream;
     // tail_event (sage_pipe.hip): to be recorded behind the LAST launch of `stages` -- as that launch's own completion signal where its
-    // launcher knows SAGE_LAUNCH_TAIL (arm() right before the stage's final launcher call), by hipEventRecord otherwise (settle())
+    // launcher takes events, by hipEventRecord otherwise (run_stage below)
     int last_stage = 0;
     for (int bit = SAGE_STAGE_LAYER2; bit >= 1; bit >>= 1)
         if (tail_event && (stages & bit)) { last_stage = bit; break; }
-    struct TailGuard { ~TailGuard() { sage_tail_event = nullptr; } } tail_guard;      // an error return must not leave it armed on this thread
-    bool armed = false;
-    auto arm = [&](int stage) { if (stage == last_stage) { sage_tail_event = tail_event; armed = true; } };
-    auto settle = [&](int stage) -> int {
-        if (stage != last_stage) return SAGE_OK;
-        if (armed && !sage_tail_event) return SAGE_OK;                                // the stage's last launch carried it
-        sage_tail_event = nullptr;                                                    // nothing launched, or by a launcher that does not know it
-        if (hipEventRecord((hipEvent_t)tail_event, st) != hipSuccess) { sage_set_error("forward2: hipEventRecord failed"); return SAGE_ELAUNCH; }
-        return SAGE_OK;
-    };
     char* ws = (char*)workspace;
     int32_t* counters = (int32_t*)(ws + L.counters);
     int32_t* s1_count = counters + 0;      // frontier rows claimed so far (zero based; rows start at first_row)
@@ -203,104 +193,100 @@ int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes
     const sage_contract_t contract2{.weight = m->w2, .ldw = (int64_t)m->h1 * (m->concat ? 2 : 1), .out_dim = m->h2, .act = m->act2, .out = out,
                                     .ldo = ldo};
 
+    // One stage: body(e) makes the stage's launches and hands e to the launcher of the LAST one.  e holds the events that launch is to
+    // carry: `own` (the gather's measurement pair, which replaces the stage's marker events) when given, otherwise the tail when this is
+    // the last requested stage, otherwise nothing.  A tail that did not ride -- the stage launched nothing, its last launcher takes no
+    // events or returned early, or the launch carried the measurement pair -- is recorded behind the stage.  Profiled forward: marker
+    // events `first` and `first + 1` around the stage.
+    auto run_stage = [&](int stage, int first, const sage_launch_events_t* own, auto body) -> int {
+        const bool tail_here = (stage & last_stage) != 0;
+        sage_launch_events_t e = own ? *own : tail_here ? sage_launch_events_t{nullptr, tail_event} : sage_launch_events_t{};
+        if (!own) SAGE_EV(first);
+        if (int rc = body(&e)) return rc;
+        if (tail_here && !(e.carried && !own) && hipEventRecord((hipEvent_t)tail_event, st) != hipSuccess) {
+            sage_set_error("forward2: hipEventRecord failed");
+            return SAGE_ELAUNCH;
+        }
+        if (!own) SAGE_EV(first + 1);
+        return SAGE_OK;
+    };
+
     const int both = SAGE_STAGE_SAMPLE_OUTER | SAGE_STAGE_SAMPLE_INNER;
     if (sfused && (stages & both)) {
         SAGE_REQUIRE((stages & both) == both, "forward2: with the fused sampler the two sampling stages are one launch: pass "
                                                 "SAGE_STAGE_SAMPLE_OUTER | SAGE_STAGE_SAMPLE_INNER together");
-        SAGE_EV(0);
-        if (int rc = sage_launch_sample_fused({.m = m, .seeds = seeds, .batch = batch, .seed = seed, .queued = queued ? 1 : 0,
-                                               .nbr2 = nbr2, .cnt2 = cnt2, .any2 = (m->nan_empty && self_loop) ? any2 : nullptr,
-                                               .frontier = &fr, .frontier_row_off = first_row, .insert_self = self_loop, .nbr_slot = slot2,
-                                               .self_slot = self_slot2, .nodes_copy = m->concat ? s1_nodes : nullptr,
-                                               .nbr1 = nbr1, .cnt1 = cnt1, .any1 = m->nan_empty ? any1 : nullptr,
-                                               .seed_rows = first_row /* = batch for the concat encoder, else 0 */}, st))
+        // (event 0 before the one launch, events 1 to 3 behind it)
+        if (int rc = run_stage(both, 0, nullptr, [&](sage_launch_events_t*) {
+                return sage_launch_sample_fused({.m = m, .seeds = seeds, .batch = batch, .seed = seed, .queued = queued ? 1 : 0,
+                                                 .nbr2 = nbr2, .cnt2 = cnt2, .any2 = (m->nan_empty && self_loop) ? any2 : nullptr,
+                                                 .frontier = &fr, .frontier_row_off = first_row, .insert_self = self_loop, .nbr_slot = slot2,
+                                                 .self_slot = self_slot2, .nodes_copy = m->concat ? s1_nodes : nullptr,
+                                                 .nbr1 = nbr1, .cnt1 = cnt1, .any1 = m->nan_empty ? any1 : nullptr,
+                                                 .seed_rows = first_row /* = batch for the concat encoder, else 0 */}, st);
+            }))
             return rc;
-        SAGE_EV(1);
         SAGE_EV(2);
         SAGE_EV(3);
-        if (last_stage == SAGE_STAGE_SAMPLE_INNER || last_stage == SAGE_STAGE_SAMPLE_OUTER)
-            if (int rc = settle(last_stage)) return rc;
     }
-    if (!sfused && (stages & SAGE_STAGE_SAMPLE_OUTER)) {
     // 1. outer hop: seeds -> nbr2, hash insert -> frontier rows [first_row, ...)
-    SAGE_EV(0);
-    arm(SAGE_STAGE_SAMPLE_OUTER);
-    if (int rc = sage_launch_sample({.rowptr = m->rowptr2, .col = m->col2, .num_nodes = m->num_nodes, .nodes = seeds, .n = batch, .k = m->k2,
-                                     .seed = seed, .tag = SAGE_TAG_OUTER, .tag_self = SAGE_TAG_OUTER,
-                                     .nbr = nbr2, .cnt = cnt2, .any_nonempty = (m->nan_empty && self_loop) ? any2 : nullptr,
-                                     .frontier = &fr, .frontier_row_off = first_row, .insert_self = self_loop, .nbr_slot = slot2,
-                                     .self_slot = self_slot2, .queue_model = qm, .nodes_from_batch = 1,
-                                     .nodes_copy = m->concat ? s1_nodes : nullptr, .seed_map = m->seed_map}, st))
-        return rc;
-    if (int rc = settle(SAGE_STAGE_SAMPLE_OUTER)) return rc;
-    SAGE_EV(1);
-    }
-    if (!sfused && (stages & SAGE_STAGE_SAMPLE_INNER)) {
+    if (!sfused && (stages & SAGE_STAGE_SAMPLE_OUTER))
+        if (int rc = run_stage(SAGE_STAGE_SAMPLE_OUTER, 0, nullptr, [&](sage_launch_events_t* e) {
+                return sage_launch_sample({.rowptr = m->rowptr2, .col = m->col2, .num_nodes = m->num_nodes, .nodes = seeds, .n = batch,
+                                           .k = m->k2, .seed = seed, .tag = SAGE_TAG_OUTER, .tag_self = SAGE_TAG_OUTER,
+                                           .nbr = nbr2, .cnt = cnt2, .any_nonempty = (m->nan_empty && self_loop) ? any2 : nullptr,
+                                           .frontier = &fr, .frontier_row_off = first_row, .insert_self = self_loop, .nbr_slot = slot2,
+                                           .self_slot = self_slot2, .queue_model = qm, .nodes_from_batch = 1,
+                                           .nodes_copy = m->concat ? s1_nodes : nullptr, .seed_map = m->seed_map}, st, e);
+            }))
+            return rc;
     // 2. inner hop: S1 -> nbr1 (raw table rows; duplicates are served by L2 / Infinity Cache).  Its spare
     //    threads turn the outer hop's hash slots into frontier rows and wipe the used keys.
     //    (Drawing these samples inside the layer-1 gather instead was measured: the gather went from 48 to
     //    100 us, its per-row dependent chain growing from 2 to 5 round trips.)
-    const sage_resolve_t resolve{slot2, row2, batch * m->k2, self_loop ? self_slot2 : nullptr, self_row2, batch, fr.rows, fr.keys};
-    SAGE_EV(2);
-    arm(SAGE_STAGE_SAMPLE_INNER);
-    if (int rc = sage_launch_sample({.rowptr = m->rowptr1, .col = m->col1, .num_nodes = m->num_nodes, .nodes = s1_nodes, .n = L.max_s1,
-                                     .n_dev = s1_count, .n_off = first_row, .k = m->k1, .seed = seed, .tag = SAGE_TAG_INNER,
-                                     .tag_self_rows = first_row, .tag_self = SAGE_TAG_INNER_SELF,
-                                     .nbr = nbr1, .cnt = cnt1, .any_nonempty = m->nan_empty ? any1 : nullptr, .queue_model = qm,
-                                     .resolve = &resolve}, st))
-        return rc;
-    if (int rc = settle(SAGE_STAGE_SAMPLE_INNER)) return rc;
-    SAGE_EV(3);
-    }
-    // 3. layer 1 on S1: the HBM-bound gather ...
+    if (!sfused && (stages & SAGE_STAGE_SAMPLE_INNER))
+        if (int rc = run_stage(SAGE_STAGE_SAMPLE_INNER, 2, nullptr, [&](sage_launch_events_t* e) {
+                const sage_resolve_t resolve{slot2, row2, batch * m->k2, self_loop ? self_slot2 : nullptr, self_row2, batch, fr.rows, fr.keys};
+                return sage_launch_sample({.rowptr = m->rowptr1, .col = m->col1, .num_nodes = m->num_nodes, .nodes = s1_nodes, .n = L.max_s1,
+                                           .n_dev = s1_count, .n_off = first_row, .k = m->k1, .seed = seed, .tag = SAGE_TAG_INNER,
+                                           .tag_self_rows = first_row, .tag_self = SAGE_TAG_INNER_SELF,
+                                           .nbr = nbr1, .cnt = cnt1, .any_nonempty = m->nan_empty ? any1 : nullptr, .queue_model = qm,
+                                           .resolve = &resolve}, st, e);
+            }))
+            return rc;
+    // 3. layer 1 on S1: the HBM-bound gather (nothing when layer 1 is a one-launch or a generic layer) ...
     if (stages & SAGE_STAGE_GATHER1) {
-    // (sage_forward2_profiled: events 4 / 5 are the gather launch's own start / stop events when it takes a column-sliced form)
-    const sage_ext_launch_t gx{ev ? ev[4] : nullptr, ev ? ev[5] : nullptr};
-    const bool ext_g = ev && ev[4] && ev[5] && (gather_only1 || split1) && sage_ext_launch == nullptr;
-    if (ext_g) sage_ext_launch = &gx; else SAGE_EV(4);
-    struct ClearHook { bool on; ~ClearHook() { if (on) sage_ext_launch = nullptr; } } clear_hook{ext_g};
-    arm(SAGE_STAGE_GATHER1);               // (a launch that carries the measurement hook's events leaves it armed: settle() records)
-    if (phase1) {
-        if (int rc = sage_launch_layer1_phase(table1_sliced, lists1, contract1, st)) return rc;
-    } else if (split1) {                   // means into agg1 -- or, on a pre-transformed table (gather_only1), activated and straight into h1
-        if (int rc = sage_launch_gather_mean(table1_sliced, lists1, gather_only1 ? h1 : agg1, gather_only1 ? m->h1 : m->d0,
-                                             gather_only1 ? m->act1 : SAGE_ACT_NONE, st))
+        // The measurement pair, as the gather launch's own start / stop events when it takes a column-sliced or the phase-sliced form:
+        // the caller's (sage_pipe_submit_profiled), or events 4 / 5 of sage_forward2_profiled, which are marker records otherwise
+        sage_launch_events_t pair;
+        if (gather_events) pair = {gather_events[0], gather_events[1]};
+        else if (ev && (gather_only1 || split1)) pair = {ev[4], ev[5]};
+        if (int rc = run_stage(SAGE_STAGE_GATHER1, 4, pair.start && pair.stop ? &pair : nullptr, [&](sage_launch_events_t* e) {
+                if (phase1) return sage_launch_layer1_phase(table1_sliced, lists1, contract1, st, e);
+                if (split1)      // means into agg1 -- or, on a pre-transformed table (gather_only1), activated and straight into h1
+                    return sage_launch_gather_mean(table1_sliced, lists1, gather_only1 ? h1 : agg1, gather_only1 ? m->h1 : m->d0,
+                                                   gather_only1 ? m->act1 : SAGE_ACT_NONE, st, e);
+                return (int)SAGE_OK;
+            }))
             return rc;
     }
-    if (int rc = settle(SAGE_STAGE_GATHER1)) return rc;
-    if (!ext_g) SAGE_EV(5);
-    }
-    // ... and its contraction (one launch with the gather unless the layer is split); then layer 2
-    if (stages & SAGE_STAGE_CONTRACT1) {
-    SAGE_EV(6);
-    if (gather_only1 || phase1) {
-        // nothing: the gather stage wrote h1
-    } else if (split1) {
-        arm(SAGE_STAGE_CONTRACT1);
-        if (int rc = sage_launch_layer_dense(means1, lists1, self1, contract1, no_fin, st)) return rc;
-    } else if (fuse1) {
-        arm(SAGE_STAGE_CONTRACT1);
-        if (int rc = sage_launch_layer_fused(table1, lists1, self1, contract1, nullptr, no_fin, st)) return rc;
-    } else {
-        if (int rc = sage_launch_gather_mean(table1, lists1, agg1, m->d0, SAGE_ACT_NONE, st)) return rc;
-        if (int rc = sage_launch_linear_act(means1, lists1, self1, contract1, no_fin, st)) return rc;
-    }
-    if (int rc = settle(SAGE_STAGE_CONTRACT1)) return rc;
-    SAGE_EV(7);
-    }
-    if (stages & SAGE_STAGE_LAYER2) {
+    // ... and its contraction (one launch with the gather unless the layer is split; nothing when the gather stage wrote h1)
+    if (stages & SAGE_STAGE_CONTRACT1)
+        if (int rc = run_stage(SAGE_STAGE_CONTRACT1, 6, nullptr, [&](sage_launch_events_t* e) {
+                if (gather_only1 || phase1) return (int)SAGE_OK;
+                if (split1) return sage_launch_layer_dense(means1, lists1, self1, contract1, no_fin, st, e);
+                if (fuse1) return sage_launch_layer_fused(table1, lists1, self1, contract1, nullptr, no_fin, st, e);
+                if (int rc = sage_launch_gather_mean(table1, lists1, agg1, m->d0, SAGE_ACT_NONE, st)) return rc;
+                return sage_launch_linear_act(means1, lists1, self1, contract1, no_fin, st);
+            }))
+            return rc;
     // 4. layer 2 on the seeds; its last block zeroes the counters and advances the batch queue
-    SAGE_EV(8);
-    if (fuse2) {
-        arm(SAGE_STAGE_LAYER2);
-        if (int rc = sage_launch_layer_fused(table2, lists2, self2, contract2, sfused ? &resolve2 : nullptr, fin, st)) return rc;
-    } else {
-        if (int rc = sage_launch_gather_mean(table2, lists2, agg2, m->h1, SAGE_ACT_NONE, st)) return rc;
-        if (int rc = sage_launch_linear_act(means2, lists2, self2, contract2, fin, st)) return rc;
-    }
-    if (int rc = settle(SAGE_STAGE_LAYER2)) return rc;
-    SAGE_EV(9);
-    }
+    if (stages & SAGE_STAGE_LAYER2)
+        if (int rc = run_stage(SAGE_STAGE_LAYER2, 8, nullptr, [&](sage_launch_events_t* e) {
+                if (fuse2) return sage_launch_layer_fused(table2, lists2, self2, contract2, sfused ? &resolve2 : nullptr, fin, st, e);
+                if (int rc = sage_launch_gather_mean(table2, lists2, agg2, m->h1, SAGE_ACT_NONE, st)) return rc;
+                return sage_launch_linear_act(means2, lists2, self2, contract2, fin, st);
+            }))
+            return rc;
     return SAGE_OK;
 }
 }  // namespace
@@ -321,8 +307,10 @@ bool sage_forward2_contract1_is_empty(const sage_model_t* m, int32_t batch) {
 
 // A subset of the forward's launches with the seeds and the sampler key taken from the call (sage_pipe.hip: one call per role stream)
 int sage_forward2_launch_stages(const sage_model_t* m, void* workspace, size_t workspace_bytes, const int32_t* seeds, int32_t batch,
-                                uint64_t seed, float* out, int64_t ldo, int32_t stages, hipStream_t stream, void* tail_event) {
-    return forward2_impl(m, workspace, workspace_bytes, seeds, batch, seed, out, ldo, (sage_stream_t)stream, nullptr, stages, tail_event);
+                                uint64_t seed, float* out, int64_t ldo, int32_t stages, hipStream_t stream, void* tail_event,
+                                void* const* gather_events) {
+    return forward2_impl(m, workspace, workspace_bytes, seeds, batch, seed, out, ldo, (sage_stream_t)stream, nullptr, stages, tail_event,
+                         gather_events);
 }
 
 extern "C" int sage_forward2_profiled(const sage_model_t* m, void* workspace, size_t workspace_bytes, const int32_t* seeds,

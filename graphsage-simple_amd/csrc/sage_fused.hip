@@ -439,7 +439,7 @@ __global__ __launch_bounds__(WAVES * 64, CONCAT ? SAGE_T16_CONCAT_MIN_WAVES : 4)
 }
 
 template <int KP, bool CONCAT>
-int launch_tile16(const FusedArgs& a, hipStream_t st) {
+int launch_tile16(const FusedArgs& a, hipStream_t st, sage_launch_events_t* ev) {
     // neighbour lists up to NPI x INFLIGHT entries are fetched in one trip: 14 (KP = 128) / 28 (KP = 64).  13 in flight (the
     // whole 25-entry list of config 3 in ONE trip, 110 VGPRs) is no faster alone and 1.4 us per forward slower with a second
     // batch in flight than 7 (two trips, 86 VGPRs): the smaller block shares a CU more easily (same-box A/B, 3 x 3 runs)
@@ -453,15 +453,15 @@ int launch_tile16(const FusedArgs& a, hipStream_t st) {
     const int tiles = sage_cdiv(a.n, 16);
     const int grid = min(tiles, sage_tunables().tile16_grid);
     if (sage_tunables().tile16_waves == 8)
-        SAGE_LAUNCH_TAIL((layer_tile16_kernel<KP, CONCAT, INFLIGHT, 8>), dim3(grid), dim3(512), 0, st, a);
+        sage_launch(layer_tile16_kernel<KP, CONCAT, INFLIGHT, 8>, dim3(grid), dim3(512), 0, st, ev, a);
     else
-        SAGE_LAUNCH_TAIL((layer_tile16_kernel<KP, CONCAT, INFLIGHT, 16>), dim3(grid), dim3(1024), 0, st, a);
+        sage_launch(layer_tile16_kernel<KP, CONCAT, INFLIGHT, 16>, dim3(grid), dim3(1024), 0, st, ev, a);
     SAGE_CHECK_LAUNCH("layer_tile16_kernel");
     return SAGE_OK;
 }
 
 template <int KP, int M, int WAVES, bool WREG, bool CONCAT, int INFLIGHT = 8>
-int launch(const FusedArgs& a, hipStream_t st) {
+int launch(const FusedArgs& a, hipStream_t st, sage_launch_events_t* ev) {
     constexpr size_t lds = (size_t)(CONCAT ? 2 : 1) * M * (KP + 4) * sizeof(float);
     static std::atomic<bool> configured{false};           // role threads (and the express lane's thread) may launch the same kernel concurrently
     if (!configured.load(std::memory_order_acquire)) {
@@ -476,7 +476,7 @@ int launch(const FusedArgs& a, hipStream_t st) {
     const int tiles = sage_cdiv(a.n, M);
     const int per_cu = WAVES >= 16 ? 2 : (WAVES == 8 ? 1 : (WREG ? 2 : 4));
     const int grid = min(tiles, per_cu * kNumCU);
-    SAGE_LAUNCH_TAIL((layer_fused_kernel<KP, M, WAVES, WREG, CONCAT, INFLIGHT>), dim3(grid), dim3(WAVES * 64), lds, st, a);
+    sage_launch(layer_fused_kernel<KP, M, WAVES, WREG, CONCAT, INFLIGHT>, dim3(grid), dim3(WAVES * 64), lds, st, ev, a);
     SAGE_CHECK_LAUNCH("layer_fused_kernel");
     return SAGE_OK;
 }
@@ -491,22 +491,22 @@ int launch(const FusedArgs& a, hipStream_t st) {
 // bound instead: 16 gathering waves per 32-row tile, and the W slice preloaded into VGPRs BEFORE
 // the gather so the MFMA loop never waits on L2 (a streamed W cost ~1 us per k-step there).
 template <int KP, bool CONCAT>
-int launch_by_rows(const FusedArgs& a, hipStream_t st) {
+int launch_by_rows(const FusedArgs& a, hipStream_t st, sage_launch_events_t* ev) {
     constexpr bool kWide = CONCAT && KP == 256;           // two 256-wide chunks: 32-row tiles to fit LDS
     if (a.n >= 8192) {
-        if constexpr (kWide) return launch<KP, 32, 4, true, CONCAT>(a, st);
-        else if constexpr (KP == 256) return launch<KP, 32, 4, false, CONCAT>(a, st);
-        else return launch<KP, 64, 4, true, CONCAT>(a, st);
+        if constexpr (kWide) return launch<KP, 32, 4, true, CONCAT>(a, st, ev);
+        else if constexpr (KP == 256) return launch<KP, 32, 4, false, CONCAT>(a, st, ev);
+        else return launch<KP, 64, 4, true, CONCAT>(a, st, ev);
     }
     // (A dedicated 2-trip kernel for this case -- ids+counts in one load, all rows in flight, W through LDS, 133 KB of
     // LDS per 1024-thread block -- ran 1 us faster alone and 7 % SLOWER with a second batch in flight: its footprint
     // keeps other kernels off the CU.  What shares the chip well beats what is fastest alone.)
 #ifdef SAGE_NO_TILE16
-    if constexpr (KP <= 128 && !CONCAT) return launch<KP, 32, 16, true, CONCAT, 6>(a, st);    // 6 in flight: inside the 128-VGPR budget of a 16-wave block
-    else return launch<KP, 32, 8, true, CONCAT>(a, st);
+    if constexpr (KP <= 128 && !CONCAT) return launch<KP, 32, 16, true, CONCAT, 6>(a, st, ev);    // 6 in flight: inside the 128-VGPR budget of a 16-wave block
+    else return launch<KP, 32, 8, true, CONCAT>(a, st, ev);
 #else
-    if constexpr (KP <= 128) return launch_tile16<KP, CONCAT>(a, st);
-    else return launch<KP, 32, 8, true, CONCAT>(a, st);
+    if constexpr (KP <= 128) return launch_tile16<KP, CONCAT>(a, st, ev);
+    else return launch<KP, 32, 8, true, CONCAT>(a, st, ev);
 #endif
 }
 
@@ -518,7 +518,7 @@ bool sage_layer_fused_supported(int32_t dim, int32_t out_dim, int32_t concat) {
 }
 
 int sage_launch_layer_fused(const sage_rows_t& src, const sage_lists_t& l, const sage_self_t& self, const sage_contract_t& c,
-                            const sage_slot_resolve_t* resolve, sage_finish_t fin, hipStream_t st) {
+                            const sage_slot_resolve_t* resolve, sage_finish_t fin, hipStream_t st, sage_launch_events_t* ev) {
     const int32_t dim = src.dim, concat = self.self_tab != nullptr;
     SAGE_REQUIRE(!concat || (self.self_tab == src.table && self.ld_self == src.ld && self.self_rows == src.table_rows),
                  "layer_forward: the fused layer takes a row's own features from the source table");
@@ -534,13 +534,13 @@ int sage_launch_layer_fused(const sage_rows_t& src, const sage_lists_t& l, const
                       resolve ? resolve->wipe_keys : nullptr, resolve ? resolve->rows_out : nullptr, resolve ? resolve->self_rows_out : nullptr};
     const int kp = dim <= 64 ? 64 : dim <= 128 ? 128 : 256;
     if (!concat) {
-        if (kp == 64) return launch_by_rows<64, false>(a, st);
-        if (kp == 128) return launch_by_rows<128, false>(a, st);
-        return launch_by_rows<256, false>(a, st);
+        if (kp == 64) return launch_by_rows<64, false>(a, st, ev);
+        if (kp == 128) return launch_by_rows<128, false>(a, st, ev);
+        return launch_by_rows<256, false>(a, st, ev);
     }
-    if (kp == 64) return launch_by_rows<64, true>(a, st);
-    if (kp == 128) return launch_by_rows<128, true>(a, st);
-    return launch_by_rows<256, true>(a, st);
+    if (kp == 64) return launch_by_rows<64, true>(a, st, ev);
+    if (kp == 128) return launch_by_rows<128, true>(a, st, ev);
+    return launch_by_rows<256, true>(a, st, ev);
 }
 
 extern "C" int sage_layer_forward_supported(int32_t dim, int32_t out_dim, int32_t concat) {

@@ -7,15 +7,7 @@
 // owns 4 consecutive columns (16-B loads, 1 KiB per wave-instruction = one 256-float
 // row), neighbour ids are broadcast from a VGPR with v_readlane so every row address
 // is scalar; the j-loop is unrolled so 8 row loads are in flight per wave.
-#include <hip/hip_ext.h>
-
 #include "sage_gather_body.h"
-
-// Measurement hook (bench.py's dominant-kernel duration): when set by the calling thread, the column-sliced gather is launched through
-// hipExtLaunchKernelGGL with these two TIMING events as the launch's own start / stop events, i.e. the interval is the kernel's
-// execution (what rocprofv3 reports) and not the distance between two marker packets around it in a busy queue.
-thread_local const sage_ext_launch_t* sage_ext_launch = nullptr;
-thread_local void* sage_tail_event = nullptr;
 
 namespace {
 
@@ -136,15 +128,6 @@ __global__ __launch_bounds__(256) void gather_mean_rows_kernel(
                                        n_off, nslice, (int)blockIdx.x, (int)gridDim.x, slice_stride, act);
 }
 
-// one launch, plain or (measurement hook) with the launch's own start / stop events
-#define SAGE_LAUNCH_G(kernel, ...)                                                                                                   \
-    do {                                                                                                                             \
-        if (const sage_ext_launch_t* x_ = sage_ext_launch)                                                                           \
-            hipExtLaunchKernelGGL((kernel), dim3(blocks), dim3(256), 0, st, (hipEvent_t)x_->start, (hipEvent_t)x_->stop, 0u, __VA_ARGS__); \
-        else                                                                                                                         \
-            SAGE_LAUNCH_TAIL((kernel), dim3(blocks), dim3(256), 0, st, __VA_ARGS__);                                                 \
-    } while (0)
-
 // Every column-sliced kernel has this signature: the dispatch below picks one, sage_launch_gather_mean launches it.
 using sliced_kernel_t = decltype(&gather_mean_sliced_kernel<16>);
 
@@ -170,7 +153,8 @@ bool sage_gather_is_sliced(int32_t dim, int64_t ld, int64_t ldo, const float* ta
     return vec4 && k <= kWave && ((dim >= SAGE_SPLIT_MIN_DIM && n >= 8192) || dim > 256);   // rows wider than 256 have no one-launch kernel
 }
 
-int sage_launch_gather_mean(const sage_rows_t& src, const sage_lists_t& l, float* out, int64_t ldo, int32_t act, hipStream_t st) {
+int sage_launch_gather_mean(const sage_rows_t& src, const sage_lists_t& l, float* out, int64_t ldo, int32_t act, hipStream_t st,
+                            sage_launch_events_t* ev) {
     const float* table = src.table;
     const int64_t ld = src.ld, slice_stride = src.slice_stride;
     const int32_t dim = src.dim, k = l.k, n = l.n;
@@ -218,8 +202,9 @@ int sage_launch_gather_mean(const sage_rows_t& src, const sage_lists_t& l, float
             kernel = sl == 32 ? gather_mean_sliced_kernel<32> : sl == 8 ? gather_mean_sliced_kernel<8> : gather_mean_sliced_kernel<16>;
             name = "gather_mean_sliced_kernel";
         }
-        SAGE_LAUNCH_G(kernel, table, (int)src.table_rows, ld, dim, l.nbr, l.cnt, k, n, l.n_dev, l.slot_rows, l.self_row, l.any_nonempty, out, ldo,
-                      l.n_off, nslice, slice_stride, act);
+        // (ev: a tail event, or the measurement pair -- this is the launch bench.py times)
+        sage_launch(kernel, dim3(blocks), dim3(256), 0, st, ev, table, (int)src.table_rows, ld, dim, l.nbr, l.cnt, k, n, l.n_dev, l.slot_rows,
+                    l.self_row, l.any_nonempty, out, ldo, l.n_off, nslice, slice_stride, act);
         SAGE_CHECK_LAUNCH(name);
         return SAGE_OK;
     }

@@ -55,6 +55,32 @@ struct sage_contract_t {
     int32_t out_dim; int32_t act; float* out; int64_t ldo;
 };
 
+// The events one launch is to carry as ITS OWN start / stop events (the two slots of hipExtLaunchKernelGGL), passed by the caller to
+// the launcher of the kernel that is to carry them; `carried` is set by sage_launch when the launch really did (a launcher's n == 0
+// early return, or a form of it that does not take events, leaves it false).
+//   {nullptr, tail}: a tail event.  A stage's hand-off event rides on the stage's LAST kernel as that dispatch's own completion signal
+//       instead of being a packet of its own behind the kernel (hipEventRecord): one barrier packet less between two kernels of a role
+//       stream (experiments/r04/handoff.hip: 7.3 against 8.5 us per hand-off; in the pipeline the record was one of the two packets
+//       that separate consecutive kernels of a stream).  Where it was not carried the caller records it (sage_forward.hip).
+//   {start, stop}: the measurement pair (bench.py's dominant-kernel duration): two TIMING events around the layer-1 gather launch,
+//       i.e. the interval is the kernel's execution (what rocprofv3 reports) and not the distance between two marker packets around
+//       it in a busy queue.  Only the stop slot can hold a tail, so a launch that carries the pair cannot carry a tail as well.
+// Never while a stream is capturing (hipExtLaunchKernel is not a capturable launch).
+struct sage_launch_events_t { void* start = nullptr; void* stop = nullptr; bool carried = false; };
+#ifdef __HIPCC__
+#include <hip/hip_ext.h>
+// One kernel launch: plain, or with `e`'s events as the launch's own
+template <class... P, class... A>
+void sage_launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t st, sage_launch_events_t* e, A&&... a) {
+    if (e && (e->start || e->stop)) {
+        hipExtLaunchKernelGGL(kernel, grid, block, lds, st, (hipEvent_t)e->start, (hipEvent_t)e->stop, 0u, static_cast<P>(a)...);
+        e->carried = true;
+    } else {
+        hipLaunchKernelGGL(kernel, grid, block, lds, st, static_cast<P>(a)...);
+    }
+}
+#endif
+
 // One sampling hop (sage_sample.hip).  Rows [0, tag_self_rows) draw from stream `tag_self` (the concat encoder's second enc1 call on
 // the seeds); with `frontier` the sampled ids are inserted and get rows from frontier_row_off on.
 struct sage_sample_t {
@@ -70,7 +96,7 @@ struct sage_sample_t {
     const int32_t* seed_map = nullptr;             // nodes[r] is a caller id
     const sage_resolve_t* resolve = nullptr;
 };
-int sage_launch_sample(const sage_sample_t& s, hipStream_t st);
+int sage_launch_sample(const sage_sample_t& s, hipStream_t st, sage_launch_events_t* ev = nullptr);
 // The same hop for k up to SAGE_MAX_FANOUT_WIDE, one wave per node (sage_sample_wide.hip).  Takes the members of a plain call only:
 // a batch queue, seed map, resolve job, row offset or second tag is refused (SAGE_EINVAL).
 int sage_launch_sample_wide(const sage_sample_t& s, hipStream_t st);
@@ -88,8 +114,9 @@ struct sage_sample_fused_t {
 };
 int sage_launch_sample_fused(const sage_sample_fused_t& s, hipStream_t st);
 
-// `act` exists in the column-sliced forms only
-int sage_launch_gather_mean(const sage_rows_t& src, const sage_lists_t& l, float* out, int64_t ldo, int32_t act, hipStream_t st);
+// `act` exists in the column-sliced forms only, and only they carry `ev`
+int sage_launch_gather_mean(const sage_rows_t& src, const sage_lists_t& l, float* out, int64_t ldo, int32_t act, hipStream_t st,
+                            sage_launch_events_t* ev = nullptr);
 bool sage_layer_dense_supported(int32_t dim, int32_t out_dim);
 bool sage_gather_is_sliced(int32_t dim, int64_t ld, int64_t ldo, const float* table, const float* out, int32_t n, int32_t k);
 
@@ -98,15 +125,16 @@ int sage_launch_linear_act(const sage_rows_t& agg, const sage_lists_t& rows, con
 
 // Fused layer (sage_fused.hip).  Returns SAGE_EUNSUPPORTED when no instantiation fits.  `self` must name the source table (SAGE_EINVAL).
 int sage_launch_layer_fused(const sage_rows_t& src, const sage_lists_t& l, const sage_self_t& self, const sage_contract_t& c,
-                            const sage_slot_resolve_t* resolve, sage_finish_t fin, hipStream_t st);
+                            const sage_slot_resolve_t* resolve, sage_finish_t fin, hipStream_t st, sage_launch_events_t* ev = nullptr);
 bool sage_layer_fused_supported(int32_t dim, int32_t out_dim, int32_t concat);
 int sage_launch_layer_dense(const sage_rows_t& agg, const sage_lists_t& rows, const sage_self_t& self, const sage_contract_t& c,
-                            sage_finish_t fin, hipStream_t st);
+                            sage_finish_t fin, hipStream_t st, sage_launch_events_t* ev = nullptr);
 
 // Phase-sliced layer 1 (sage_layer1_phase.hip): gather + contraction of the gcn encoder's layer 1 in one launch on the slice-major table
 // of 32-float slices, bit-identical to sage_launch_gather_mean + sage_launch_layer_dense.  SAGE_EUNSUPPORTED when the shape has no kernel.
 bool sage_layer1_phase_supported(int32_t d0, int32_t h1, int32_t k);
-int sage_launch_layer1_phase(const sage_rows_t& src, const sage_lists_t& l, const sage_contract_t& c, hipStream_t st);
+int sage_launch_layer1_phase(const sage_rows_t& src, const sage_lists_t& l, const sage_contract_t& c, hipStream_t st,
+                             sage_launch_events_t* ev = nullptr);
 
 // Classifier head (sage_head.hip): scores, cross-entropy and its gradients of one batch.  The row kernel takes this struct by value.
 // part_w / part_loss: the per-range partials in the caller's workspace ([ranges][C * dim] and [ranges]); part_w == NULL: no weight
@@ -122,31 +150,6 @@ struct sage_head_t {
 };
 int sage_launch_xent_head(const sage_head_t& h, hipStream_t st);
 
-// Measurement hook (sage_gather.hip): set by the thread that is about to launch the layer-1 gather, cleared right after.
-struct sage_ext_launch_t { void* start; void* stop; };
-extern thread_local const sage_ext_launch_t* sage_ext_launch;
-
-// Tail event (round 4).  A stage's hand-off event can ride on the stage's LAST kernel as that dispatch's own completion signal
-// (hipExtLaunchKernel stopEvent) instead of being a packet of its own behind the kernel (hipEventRecord): one barrier packet less between
-// two kernels of a role stream (experiments/r04/handoff.hip: 7.3 against 8.5 us per hand-off; in the pipeline the record was one of the two
-// packets that separate consecutive kernels of a stream).  One-shot and thread-local: whoever is about to call the launcher of a stage's
-// last kernel sets it; the first launch made through SAGE_LAUNCH_TAIL consumes it; a launcher that does not know it leaves it set, and the
-// setter then records the event explicitly (sage_forward.hip).  Never while a stream is capturing.
-extern thread_local void* sage_tail_event;
-#ifdef __HIPCC__
-#include <hip/hip_ext.h>
-#define SAGE_LAUNCH_TAIL(kernel, grid, block, lds, st, ...)                                                               \
-    do {                                                                                                                  \
-        if (sage_tail_event) {                                                                                            \
-            hipEvent_t tail_ = (hipEvent_t)sage_tail_event;                                                               \
-            sage_tail_event = nullptr;                                                                                    \
-            hipExtLaunchKernelGGL((kernel), (grid), (block), (lds), (st), nullptr, tail_, 0u, __VA_ARGS__);               \
-        } else {                                                                                                          \
-            hipLaunchKernelGGL((kernel), (grid), (block), (lds), (st), __VA_ARGS__);                                      \
-        }                                                                                                                 \
-    } while (0)
-#endif
-
 // The launches of one forward, by stage (sage_pipe.hip enqueues each stage on its role stream)
 #define SAGE_STAGE_SAMPLE_OUTER 1
 #define SAGE_STAGE_SAMPLE_INNER 2
@@ -155,7 +158,8 @@ extern thread_local void* sage_tail_event;
 #define SAGE_STAGE_LAYER2       16
 #define SAGE_STAGE_ALL          31
 int sage_forward2_launch_stages(const sage_model_t* m, void* workspace, size_t workspace_bytes, const int32_t* seeds, int32_t batch,
-                                uint64_t seed, float* out, int64_t ldo, int32_t stages, hipStream_t stream, void* tail_event = nullptr);
+                                uint64_t seed, float* out, int64_t ldo, int32_t stages, hipStream_t stream, void* tail_event = nullptr,
+                                void* const* gather_events = nullptr);
 
 bool sage_forward2_contract1_is_empty(const sage_model_t* m, int32_t batch);
 

@@ -22,8 +22,6 @@
 // Rows that hold |x| >= 2^127 / Inf / NaN in their means (the empty-set NaN rule included), or every row when W1 holds one, are
 // recomputed by the exact fp32 fma chain of the contraction's cold path, from the table.
 // Latency: 3 blocks of 4 waves per CU take turns -- while one contracts and stages, the others have their 16 x 1 KiB per wave in flight.
-#include <hip/hip_ext.h>
-
 #include "sage_gather_body.h"
 #include "sage_split_bf16.h"
 
@@ -196,14 +194,11 @@ __global__ __launch_bounds__(256, 3) void layer1_phase_kernel(const PhaseArgs a)
 }
 
 template <int NSLICE>
-int launch_phase(const PhaseArgs& a, hipStream_t st) {
+int launch_phase(const PhaseArgs& a, hipStream_t st, sage_launch_events_t* ev) {
     // persistent blocks, 3 per CU, a multiple of 8 so that a tile's class (tile mod 8) is its XCD
     const int per_cu = sage_tunables().layer1_phase_per_cu;
     const int grid = min((sage_cdiv(a.n, kTileRows) + 7) / 8 * 8, kNumCU * per_cu);
-    if (const sage_ext_launch_t* x = sage_ext_launch)     // measurement hook: the launch's own start / stop events (sage_gather.hip)
-        hipExtLaunchKernelGGL((layer1_phase_kernel<NSLICE>), dim3(grid), dim3(256), 0, st, (hipEvent_t)x->start, (hipEvent_t)x->stop, 0u, a);
-    else
-        SAGE_LAUNCH_TAIL((layer1_phase_kernel<NSLICE>), dim3(grid), dim3(256), 0, st, a);
+    sage_launch(layer1_phase_kernel<NSLICE>, dim3(grid), dim3(256), 0, st, ev, a);
     SAGE_CHECK_LAUNCH("layer1_phase_kernel");
     return SAGE_OK;
 }
@@ -214,7 +209,8 @@ bool sage_layer1_phase_supported(int32_t d0, int32_t h1, int32_t k) {
     return (d0 == 64 || d0 == 128 || d0 == 256) && h1 >= 32 && h1 <= 128 && h1 % 32 == 0 && k >= 1 && k <= kMaxK;
 }
 
-int sage_launch_layer1_phase(const sage_rows_t& src, const sage_lists_t& l, const sage_contract_t& c, hipStream_t st) {
+int sage_launch_layer1_phase(const sage_rows_t& src, const sage_lists_t& l, const sage_contract_t& c, hipStream_t st,
+                             sage_launch_events_t* ev) {
     const int32_t d0 = src.dim;
     SAGE_REQUIRE(src.ld == kSliceFloats && src.slice_stride == src.table_rows * (int64_t)kSliceFloats,
                  "layer1_fused: the table must be slice-major with %d-float slices", kSliceFloats);
@@ -226,9 +222,9 @@ int sage_launch_layer1_phase(const sage_rows_t& src, const sage_lists_t& l, cons
     if (l.n == 0) return SAGE_OK;
     const PhaseArgs a{src.table, (int)src.table_rows, src.slice_stride, l.nbr, l.cnt, l.k, l.n, l.n_dev, l.n_off, l.self_row, l.any_nonempty,
                       c.weight, c.ldw, (const uint4*)c.weight_prepared, c.out_dim, c.act, c.out, c.ldo};
-    if (d0 == 64) return launch_phase<2>(a, st);
-    if (d0 == 128) return launch_phase<4>(a, st);
-    return launch_phase<8>(a, st);
+    if (d0 == 64) return launch_phase<2>(a, st, ev);
+    if (d0 == 128) return launch_phase<4>(a, st, ev);
+    return launch_phase<8>(a, st, ev);
 }
 
 extern "C" int sage_layer1_fused_supported(int32_t d0, int32_t h1, int32_t k) { return sage_layer1_phase_supported(d0, h1, k) ? 1 : 0; }

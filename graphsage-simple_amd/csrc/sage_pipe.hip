@@ -244,8 +244,9 @@ static int role_enqueue(sage_pipe* p, int r, const pipe_desc& d, unsigned long l
     const sage_model_t* m = &p->model;
     const int slot = d.slot;
     void* ws = p->ws[slot];
-    // the role's hand-off event rides on its stage's last kernel (sage_internal.h: tail event) instead of being recorded behind it -- not while
-    // capturing (hipExtLaunchKernel is not a capturable launch), and SAGE_PIPE_TAIL=0 keeps the separate record (A/B)
+    // the role's hand-off event is passed down as the tail of its stages (sage_internal.h: sage_launch_events_t): it rides on their last kernel,
+    // or sage_forward2_launch_stages records it behind them -- not while capturing (hipExtLaunchKernel is not a capturable launch), and
+    // SAGE_PIPE_TAIL=0 keeps the separate record made here (A/B)
     static const bool tail_on = [] { const char* v = getenv("SAGE_PIPE_TAIL"); return !(v && *v == '0'); }();
     auto tail = [&](int role, bool needed) -> void* { return (tail_on && cap == 0 && needed) ? (void*)p->ev[role][slot] : nullptr; };
     // Stage D launches nothing when the gather stage writes h1 itself (the phase-sliced layer 1, the pre-transformed table): its wait and its
@@ -258,80 +259,67 @@ static int role_enqueue(sage_pipe* p, int r, const pipe_desc& d, unsigned long l
     if (d.express) {
         // the pipeline was idle at submit: no release to wait for, nothing to hand over; roles S, G, D have no calls to make
         if (r != RL) return SAGE_OK;
-        const sage_ext_launch_t x{d.gev[0], d.gev[1]};
-        if (d.gev[0] && d.gev[1]) sage_ext_launch = &x;
-        const int rc = sage_forward2_launch_stages(m, ws, p->ws_bytes, d.seeds, p->batch, d.key, d.out, d.ldo, SAGE_STAGE_ALL, p->st[RL],
-                                                   tail(RL, true));
-        sage_ext_launch = nullptr;
-        if (rc) return rc;
-        return tail(RL, true) ? SAGE_OK : record(p, RL, slot, true);
+        void* const t = tail(RL, true);
+        if (int rc = sage_forward2_launch_stages(m, ws, p->ws_bytes, d.seeds, p->batch, d.key, d.out, d.ldo, SAGE_STAGE_ALL, p->st[RL], t, d.gev))
+            return rc;
+        return t ? SAGE_OK : record(p, RL, slot, true);
     }
-    switch (r) {
-    case RS:
-        // S: outer + inner sample.  Needs the slot's previous batch to have left layer 2 (its last block zeroes the counters).
-        if (!d.fresh && p->st[RS] != p->st[RL]) {
-            if (cap != 0) {
-                // captured: the release edge as an explicit node dependency (an event wait here crashes hipStreamEndCapture, see above)
-                SAGE_REQUIRE(p->cap_id[slot] == cap && p->cap_count[slot] > 0,
-                             "pipe: inside a stream capture the first `depth` submits must find their workspaces free: join everything "
-                             "submitted before, begin the capture, and pass segment_start (sage_pipe_submit_many) / call sage_pipe_reset");
-                if (hipStreamUpdateCaptureDependencies(p->st[RS], p->cap_nodes[slot], (size_t)p->cap_count[slot], hipStreamAddCaptureDependencies) != hipSuccess) {
-                    sage_set_error("pipe: hipStreamUpdateCaptureDependencies failed");
-                    return SAGE_ELAUNCH;
-                }
-            } else {
-                SAGE_REQUIRE(p->cap_id[slot] == 0, "pipe: this slot's last batch was submitted inside a stream capture: call sage_pipe_reset "
-                                                   "(after synchronising) before submitting eagerly again");
-                if (int rc = wait_on(p, RS, RL, slot, cap != 0)) return rc;
+    // Every role: wait on the producer, launch the role's stages with the hand-off event as their tail, record it unless it rode.
+    //   S: outer + inner sample.  Needs the slot's previous batch to have left layer 2 (its last block zeroes the counters).
+    //   G: the layer-1 gather (nothing to launch when layer 1 is a one-launch layer; D then waits on S through G's stream order).
+    //      A profiled submit's two caller-owned timing events (d.gev) become the gather launch's OWN start / stop events.
+    //   D: the contraction (or the whole fused layer 1).
+    //   L: layer 2; afterwards the workspace is clean again.
+    const struct { int producer, stages, consumer; bool takes_out; } stage[4] = {
+        {RL, SAGE_STAGE_SAMPLE_OUTER | SAGE_STAGE_SAMPLE_INNER, RG, false},
+        {RS, SAGE_STAGE_GATHER1, g_consumer, false},
+        {RG, SAGE_STAGE_CONTRACT1, RL, false},
+        {d_empty ? RG : RD, SAGE_STAGE_LAYER2, RS, true}};
+    const auto& s = stage[r];
+    if (r == RD && d_empty) return SAGE_OK;
+    if (r != RS) {
+        if (int rc = wait_on(p, r, s.producer, slot, cap != 0)) return rc;
+    } else if (!d.fresh && p->st[RS] != p->st[RL]) {      // the workspace-release edge L(b - depth) -> S(b)
+        if (cap != 0) {
+            // captured: the release edge as an explicit node dependency (an event wait here crashes hipStreamEndCapture, see above)
+            SAGE_REQUIRE(p->cap_id[slot] == cap && p->cap_count[slot] > 0,
+                         "pipe: inside a stream capture the first `depth` submits must find their workspaces free: join everything "
+                         "submitted before, begin the capture, and pass segment_start (sage_pipe_submit_many) / call sage_pipe_reset");
+            if (hipStreamUpdateCaptureDependencies(p->st[RS], p->cap_nodes[slot], (size_t)p->cap_count[slot], hipStreamAddCaptureDependencies) != hipSuccess) {
+                sage_set_error("pipe: hipStreamUpdateCaptureDependencies failed");
+                return SAGE_ELAUNCH;
             }
+        } else {
+            SAGE_REQUIRE(p->cap_id[slot] == 0, "pipe: this slot's last batch was submitted inside a stream capture: call sage_pipe_reset "
+                                               "(after synchronising) before submitting eagerly again");
+            if (int rc = wait_on(p, RS, RL, slot)) return rc;
         }
-#ifndef SAGE_PIPE_SKIP_S   // diagnostic builds only (experiments/ab_build.sh).  _G and _D may be skipped alone (stale data downstream); _S and _L
-                           // only together with everything else ("events only"): the samplers fill and layer 2 wipes the frontier hash, and
-                           // one without the other leaves a full table behind (an outer sampler probing it took 67 ms per batch)
-        if (int rc = sage_forward2_launch_stages(m, ws, p->ws_bytes, d.seeds, p->batch, d.key, nullptr, 0,
-                                                 SAGE_STAGE_SAMPLE_OUTER | SAGE_STAGE_SAMPLE_INNER, p->st[RS], tail(RS, p->st[RG] != p->st[RS])))
-            return rc;
-        if (tail(RS, p->st[RG] != p->st[RS])) return SAGE_OK;
-#endif
-        return record(p, RS, slot, p->st[RG] != p->st[RS]);
-    case RG:
-        // G: the layer-1 gather (nothing to launch when layer 1 is a one-launch layer; D then waits on S through G's stream order)
-        if (int rc = wait_on(p, RG, RS, slot, cap != 0)) return rc;
-#ifndef SAGE_PIPE_SKIP_G   // diagnostic builds (experiments/ab_build.sh): the pipeline without one of its stages' kernels, stale data downstream
-        {
-            // profiled submit: the two caller-owned timing events become the gather launch's OWN start / stop events (sage_gather.hip)
-            const sage_ext_launch_t x{d.gev[0], d.gev[1]};
-            if (d.gev[0] && d.gev[1]) sage_ext_launch = &x;
-            const int rc = sage_forward2_launch_stages(m, ws, p->ws_bytes, d.seeds, p->batch, d.key, nullptr, 0, SAGE_STAGE_GATHER1, p->st[RG],
-                                                       tail(RG, p->st[g_consumer] != p->st[RG]));
-            sage_ext_launch = nullptr;
-            if (rc) return rc;
-            if (tail(RG, p->st[g_consumer] != p->st[RG])) return SAGE_OK;
-        }
-#endif
-        return record(p, RG, slot, p->st[g_consumer] != p->st[RG]);
-    case RD:
-        // D: the contraction (or the whole fused layer 1)
-        if (d_empty) return SAGE_OK;
-        if (int rc = wait_on(p, RD, RG, slot, cap != 0)) return rc;
-#ifndef SAGE_PIPE_SKIP_D
-        if (int rc = sage_forward2_launch_stages(m, ws, p->ws_bytes, d.seeds, p->batch, d.key, nullptr, 0, SAGE_STAGE_CONTRACT1, p->st[RD],
-                                                 tail(RD, p->st[RL] != p->st[RD])))
-            return rc;
-        if (tail(RD, p->st[RL] != p->st[RD])) return SAGE_OK;
-#endif
-        return record(p, RD, slot, p->st[RL] != p->st[RD]);
-    default:
-        // L: layer 2; afterwards the workspace is clean again
-        if (int rc = wait_on(p, RL, d_empty ? RG : RD, slot, cap != 0)) return rc;
-#ifndef SAGE_PIPE_SKIP_L
-        if (int rc = sage_forward2_launch_stages(m, ws, p->ws_bytes, d.seeds, p->batch, d.key, d.out, d.ldo, SAGE_STAGE_LAYER2, p->st[RL],
-                                                 tail(RL, p->st[RS] != p->st[RL])))
-            return rc;
-        if (tail(RL, p->st[RS] != p->st[RL])) return SAGE_OK;
-#endif
-        return record(p, RL, slot, p->st[RS] != p->st[RL]);
     }
+    const bool needed = p->st[s.consumer] != p->st[r];
+    // Diagnostic builds only (experiments/ab_build.sh): the pipeline without one of its stages' kernels.  _G and _D may be skipped alone
+    // (stale data downstream); _S and _L only together with everything else ("events only"): the samplers fill and layer 2 wipes the
+    // frontier hash, and one without the other leaves a full table behind (an outer sampler probing it took 67 ms per batch)
+    bool skip = false;
+#ifdef SAGE_PIPE_SKIP_S
+    skip |= r == RS;
+#endif
+#ifdef SAGE_PIPE_SKIP_G
+    skip |= r == RG;
+#endif
+#ifdef SAGE_PIPE_SKIP_D
+    skip |= r == RD;
+#endif
+#ifdef SAGE_PIPE_SKIP_L
+    skip |= r == RL;
+#endif
+    if (!skip) {
+        void* const t = tail(r, needed);
+        if (int rc = sage_forward2_launch_stages(m, ws, p->ws_bytes, d.seeds, p->batch, d.key, s.takes_out ? d.out : nullptr,
+                                                 s.takes_out ? d.ldo : 0, s.stages, p->st[r], t, d.gev))
+            return rc;
+        if (t) return SAGE_OK;
+    }
+    return record(p, r, slot, needed);
 }
 
 // ---- host enqueue threads ------------------------------------------------------------------------------------------------
@@ -565,7 +553,7 @@ extern "C" int sage_pipe_submit(sage_pipe_t* p, const int32_t* seeds, uint64_t k
     return submit_one(p, seeds, key, out, ldo, p->submitted < (uint64_t)p->depth);
 }
 
-// The same with two caller-owned hipEvent_t recorded on stream G right before and right after the layer-1 gather launch
+// The same with two caller-owned hipEvent_t that the layer-1 gather launch on stream G carries as its own start / stop events
 // (bench.py: the dominant kernel's duration inside the running pipeline).
 extern "C" int sage_pipe_submit_profiled(sage_pipe_t* p, const int32_t* seeds, uint64_t key, float* out, int64_t ldo, void* const* gather_events) {
     SAGE_REQUIRE(p && seeds && out && gather_events, "pipe_submit_profiled: NULL argument");

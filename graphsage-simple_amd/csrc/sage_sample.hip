@@ -130,7 +130,7 @@ SampleLaunch pick_by_fanout(int k) {
 int sage_check_frontier(const sage_frontier_t* f, int64_t inserts) { return check_frontier(f, inserts); }
 
 // Internal launcher shared with sage_forward.hip (sage_sample_t: sage_internal.h)
-int sage_launch_sample(const sage_sample_t& s, hipStream_t st) {
+int sage_launch_sample(const sage_sample_t& s, hipStream_t st, sage_launch_events_t* ev) {
     if (s.n == 0) return SAGE_OK;
     const sage_model_t* qm = s.queue_model;
     const BatchSrc bs{qm ? qm->queue : nullptr, qm ? qm->queue_cursor : nullptr, qm ? qm->queue_len : 0, s.nodes_from_batch, s.nodes_copy,
@@ -143,9 +143,9 @@ int sage_launch_sample(const sage_sample_t& s, hipStream_t st) {
         fd = FrontierDev{f->keys, f->rows, (uint32_t)f->capacity - 1u, f->nodes, f->count, f->max_nodes, s.frontier_row_off};
     const SampleLaunch L = s.frontier ? pick_by_fanout<true, true>(s.k) : pick_by_fanout<true, false>(s.k);
     const int32_t* none = nullptr;
-    SAGE_LAUNCH_TAIL(L.kernel, dim3(sage_cdiv(s.n, L.nodes_per_block)), dim3(L.threads), 0, st, s.rowptr, s.col, s.nodes, s.n, s.n_dev, s.k,
-                     (uint32_t)s.seed, (uint32_t)(s.seed >> 32), s.tag, s.tag_self_rows, s.tag_self, none, none, s.nbr, s.cnt, s.any_nonempty, fd,
-                     s.frontier ? s.insert_self : 0, s.frontier ? s.nbr_slot : nullptr, s.frontier ? s.self_slot : nullptr, bs, s.n_off, rj);
+    sage_launch(L.kernel, dim3(sage_cdiv(s.n, L.nodes_per_block)), dim3(L.threads), 0, st, ev, s.rowptr, s.col, s.nodes, s.n, s.n_dev, s.k,
+                (uint32_t)s.seed, (uint32_t)(s.seed >> 32), s.tag, s.tag_self_rows, s.tag_self, none, none, s.nbr, s.cnt, s.any_nonempty, fd,
+                s.frontier ? s.insert_self : 0, s.frontier ? s.nbr_slot : nullptr, s.frontier ? s.self_slot : nullptr, bs, s.n_off, rj);
     SAGE_CHECK_LAUNCH("sample_kernel");
     return SAGE_OK;
 }
@@ -225,9 +225,9 @@ extern "C" int sage_frontier_insert(const int32_t* nbr, const int32_t* cnt, int3
     const int64_t* no64 = nullptr;
     const int32_t* no32 = nullptr;
     const SampleLaunch L = pick_by_fanout<false, true>(k);
-    SAGE_LAUNCH_TAIL(L.kernel, dim3(sage_cdiv(n, L.nodes_per_block)), dim3(L.threads), 0, (hipStream_t)stream, no64, no32, self_nodes, n, n_dev, k,
-                     0u, 0u, 0u, 0, 0u, nbr, cnt, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, fd, self_nodes ? 1 : 0, nbr_slot,
-                     self_slot, BatchSrc{nullptr, nullptr, 0, 0, nullptr, nullptr, 0}, 0, ResolveJob{});
+    hipLaunchKernelGGL(L.kernel, dim3(sage_cdiv(n, L.nodes_per_block)), dim3(L.threads), 0, (hipStream_t)stream, no64, no32, self_nodes, n, n_dev, k,
+                       0u, 0u, 0u, 0, 0u, nbr, cnt, (int32_t*)nullptr, (int32_t*)nullptr, (int32_t*)nullptr, fd, self_nodes ? 1 : 0, nbr_slot,
+                       self_slot, BatchSrc{nullptr, nullptr, 0, 0, nullptr, nullptr, 0}, 0, ResolveJob{});
     SAGE_CHECK_LAUNCH("frontier_insert_kernel");
     return SAGE_OK;
 }

@@ -494,7 +494,8 @@ int sage_pipe_destroy(sage_pipe_t* p);
 int sage_pipe_update_weights(sage_pipe_t* p, const float* w1, const float* w2, const void* w1_prepared);
 /* One batch: seeds int32[batch] and out float[batch, h2] must stay valid until the batch has left stream L. */
 int sage_pipe_submit(sage_pipe_t* p, const int32_t* seeds, uint64_t key, float* out, int64_t ldo);
-/* sage_pipe_submit + two caller-owned hipEvent_t (gather_events[0], [1]) recorded on stream G around the layer-1 gather. */
+/* sage_pipe_submit + two caller-owned hipEvent_t (gather_events[0], [1]) that the layer-1 gather launch on stream G carries as its own
+ * start / stop events (column-sliced and phase-sliced layer 1; left unrecorded where the gather stage launches nothing). */
 int sage_pipe_submit_profiled(sage_pipe_t* p, const int32_t* seeds, uint64_t key, float* out, int64_t ldo,
                               void* const* gather_events);
 /* n batches from one host loop: batch i reads seeds + i*seed_stride (elements), keys_host[i] (HOST array) and
