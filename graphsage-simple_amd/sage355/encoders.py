@@ -52,6 +52,8 @@ one ``random.sample`` per node -- a program that interleaves its own draws from
 call as the reference does.
 """
 import collections
+import dataclasses
+import os
 import random
 import weakref
 
@@ -69,10 +71,27 @@ SIGMOID_INITIALIZERS = ("node_degree", "shared", "pagerank")   # encoders.py:58
 
 _CSR_CACHE_MAX = 8            # adjacency objects kept (LRU): both layers of a model share one, a process holds a few models
 _CSR_CHECK_MAX_NODES = 200_000  # adjacencies up to this many keys are re-fingerprinted (periodically, below); larger ones are frozen
-_csr_cache = collections.OrderedDict()
-
-
 _CSR_RECHECK_EVERY = 64       # forwards between two full fingerprints of a cached adjacency
+_csr_cache = collections.OrderedDict()         # id(adj_lists) -> _CsrEntry
+
+
+@dataclasses.dataclass
+class _CsrEntry:
+    adj_lists: object             # the adjacency itself: an id() can be reused
+    num_nodes_hint: int
+    rowptr: torch.Tensor
+    col: torch.Tensor
+    deg_host: np.ndarray          # the CSR's degrees, for the per-call probe
+    fingerprint: object           # None: too large to fingerprint
+    key_count: int                # len(adj_lists) when last validated
+    calls: int = 0
+
+
+@dataclasses.dataclass
+class _DevCopy:                   # Encoder._dev_cache: the device tensor the forward reads in place of one of the caller's
+    key: object                   # what the caller's tensor was when `tensor` was written (None: stale); the Parameter's address for host=False
+    tensor: torch.Tensor
+    host: bool = True             # a copy of a host tensor; False: the Parameter's own device storage, detached
 
 
 def _fingerprint(adj_lists):
@@ -105,6 +124,10 @@ def invalidate_adjacency(adj_lists=None):
         _csr_cache.pop(id(adj_lists), None)
 
 
+def _probe_nodes(nodes):         # the batch's ids, unless reading them would take a device round trip
+    return nodes if isinstance(nodes, (list, tuple, np.ndarray)) else None
+
+
 def _probe_ok(adj_lists, deg_host, probe_nodes):
     """Cheap per-call signal: the set sizes of up to 64 of the batch's own nodes still equal the cached CSR's degrees."""
     if probe_nodes is None:
@@ -125,29 +148,22 @@ def _device_csr(adj_lists, num_nodes_hint, device, probe_nodes=None):
     The reference re-reads the dict on every call; here the conversion is cached and revalidated: every call by the key count and
     by the set sizes of a few of the batch's own nodes (`probe_nodes`), every _CSR_RECHECK_EVERY-th call (or every call under
     SAGE_ADJ_STRICT=1) by a fingerprint."""
-    import os
     key = id(adj_lists)
     hit = _csr_cache.get(key)
-    if hit is not None and hit[0] is adj_lists and hit[4] == num_nodes_hint:
+    if hit is not None and hit.adj_lists is adj_lists and hit.num_nodes_hint == num_nodes_hint:
         # every call: O(1) + O(64) -- a changed key count (new nodes; also the empty sets the reference's defaultdict inserts on a miss)
         # or a changed set size among the batch's own nodes triggers the full fingerprint at once; otherwise it is recomputed every
         # _CSR_RECHECK_EVERY-th call (it walks every set in Python: ~0.3 ms at Cora's size, twice per forward, was a third of a
         # 256-seed training step)
-        state = hit[5]
-        state[0] += 1
+        hit.calls += 1
         strict = os.environ.get("SAGE_ADJ_STRICT", "0") == "1"
-        probe = _probe_ok(adj_lists, hit[6], probe_nodes)
-        if probe and not strict and len(adj_lists) == state[1] and state[0] % _CSR_RECHECK_EVERY != 0:
-            _csr_cache.move_to_end(key)
-            return hit[1], hit[2]
-        if probe and hit[3] is not None and hit[3] == _fingerprint(adj_lists):
-            state[1] = len(adj_lists)
-            _csr_cache.move_to_end(key)
-            return hit[1], hit[2]
-        if probe and hit[3] is None and not strict:          # too large to fingerprint: frozen at first use (probe and key count aside)
-            state[1] = len(adj_lists)
-            _csr_cache.move_to_end(key)
-            return hit[1], hit[2]
+        if _probe_ok(adj_lists, hit.deg_host, probe_nodes):
+            unchecked = not strict and len(adj_lists) == hit.key_count and hit.calls % _CSR_RECHECK_EVERY != 0
+            # no fingerprint: too large for one, frozen at first use (probe and key count aside)
+            if unchecked or (not strict if hit.fingerprint is None else hit.fingerprint == _fingerprint(adj_lists)):
+                hit.key_count = len(adj_lists)
+                _csr_cache.move_to_end(key)
+                return hit.rowptr, hit.col
     fp = _fingerprint(adj_lists)
     g = csr_from_adj_lists(adj_lists, None)
     if num_nodes_hint and g.num_nodes < num_nodes_hint:
@@ -157,8 +173,7 @@ def _device_csr(adj_lists, num_nodes_hint, device, probe_nodes=None):
     rowptr, col = g.to(device)
     if col.numel() == 0:
         col = torch.zeros(1, dtype=torch.int32, device=device)
-    deg_host = np.diff(g.rowptr)
-    _csr_cache[key] = (adj_lists, rowptr, col, fp, num_nodes_hint, [0, len(adj_lists)], deg_host)
+    _csr_cache[key] = _CsrEntry(adj_lists, num_nodes_hint, rowptr, col, np.diff(g.rowptr), fp, len(adj_lists))
     _csr_cache.move_to_end(key)
     while len(_csr_cache) > _CSR_CACHE_MAX:
         _csr_cache.popitem(last=False)
@@ -177,7 +192,6 @@ def _cap_host_threads_once():
     if _threads_capped:
         return
     _threads_capped = True
-    import os
     if os.environ.get("SAGE_KEEP_TORCH_THREADS", "0") == "1":
         return
     usable = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
@@ -231,10 +245,9 @@ class Encoder(nn.Module):
             return t
         key = (tag, t.data_ptr(), t._version, tuple(t.shape))
         hit = self._dev_cache.get(tag)
-        if hit is None or hit[0] != key:
-            hit = (key, t.detach().to("cuda", torch.float32).contiguous())
-            self._dev_cache[tag] = hit
-        return hit[1]
+        if hit is None or hit.key != key:
+            hit = self._dev_cache[tag] = _DevCopy(key, t.detach().to("cuda", torch.float32).contiguous())
+        return hit.tensor
 
     def _pair(self):
         """This Encoder and its base model, when that is an Encoder."""
@@ -257,8 +270,8 @@ class Encoder(nn.Module):
         Either Encoder of the pair may be called."""
         for enc in self._pair():
             hit = enc._dev_cache.get("table")
-            if hit is not None and enc._is_table() and tuple(hit[1].shape) == tuple(enc.features.weight.shape):
-                hit[1].copy_(enc.features.weight.detach())
+            if hit is not None and enc._is_table() and tuple(hit.tensor.shape) == tuple(enc.features.weight.shape):
+                hit.tensor.copy_(enc.features.weight.detach())
         for eng in self._engines():
             eng.refresh_table()
 
@@ -269,8 +282,8 @@ class Encoder(nn.Module):
         for enc in self._pair():
             enc._dev_cache.pop("weight", None)
             hit = enc._dev_cache.get("engine_w")
-            if hit is not None and hit[0] == "host":
-                hit[1] = None                      # the next _engine_weight copies the host Parameter into the same device buffer
+            if hit is not None and hit.host:
+                hit.key = None                     # the next _engine_weight copies the host Parameter into the same device buffer
         for eng in self._engines():
             eng.invalidate_weights()
 
@@ -288,24 +301,22 @@ class Encoder(nn.Module):
     def _agg_self_loop(self):
         return bool(getattr(self.aggregator, "gcn", False))
 
-    def _can_fuse_two_hop(self):
+    def _is_two_hop_stack(self, max_fanout):
+        """This Encoder over a table-backed base Encoder, both mean aggregators of one kind, with fanouts in [1, max_fanout]."""
         base = getattr(self, "base_model", None)
         return (self.fuse_base_model and isinstance(base, Encoder) and base._is_table()
                 and isinstance(self.aggregator, MeanAggregator) and isinstance(base.aggregator, MeanAggregator)
                 and self.gcn == base.gcn and self._agg_self_loop() == base._agg_self_loop()
                 and self.num_sample is not None and base.num_sample is not None
-                and 1 <= self.num_sample <= native.MAX_FANOUT and 1 <= base.num_sample <= native.MAX_FANOUT)
+                and 1 <= self.num_sample <= max_fanout and 1 <= base.num_sample <= max_fanout)
+
+    def _can_fuse_two_hop(self):
+        return self._is_two_hop_stack(native.MAX_FANOUT)
 
     def _can_two_hop_ops(self):
         """The stack _can_fuse_two_hop describes, with a fanout the engine's samplers do not take (above native.MAX_FANOUT, up to
         native.MAX_FANOUT_WIDE): it runs from the public operators (twohop_ops.two_hop_forward)."""
-        base = getattr(self, "base_model", None)
-        return (self.fuse_base_model and isinstance(base, Encoder) and base._is_table()
-                and isinstance(self.aggregator, MeanAggregator) and isinstance(base.aggregator, MeanAggregator)
-                and self.gcn == base.gcn and self._agg_self_loop() == base._agg_self_loop()
-                and self.num_sample is not None and base.num_sample is not None
-                and 1 <= self.num_sample <= native.MAX_FANOUT_WIDE and 1 <= base.num_sample <= native.MAX_FANOUT_WIDE
-                and max(self.num_sample, base.num_sample) > native.MAX_FANOUT)
+        return self._is_two_hop_stack(native.MAX_FANOUT_WIDE) and max(self.num_sample, self.base_model.num_sample) > native.MAX_FANOUT
 
     # ------------------------------------------------------------------ forward
     def forward(self, nodes):
@@ -341,19 +352,17 @@ class Encoder(nn.Module):
         w = self.weight
         hit = self._dev_cache.get(tag)
         if w.is_cuda:
-            if hit is None or hit[0] != "device" or hit[1] != w.data_ptr():
-                hit = ["device", w.data_ptr(), w.detach()]          # shares storage AND version counter with the Parameter
-                self._dev_cache[tag] = hit
-            return hit[2], False
+            if hit is None or hit.host or hit.key != w.data_ptr():
+                hit = self._dev_cache[tag] = _DevCopy(w.data_ptr(), w.detach(), host=False)      # shares storage AND version counter
+            return hit.tensor, False
         key = (w.data_ptr(), w._version, tuple(w.shape))
-        if hit is None or hit[0] != "host" or hit[2].shape != w.shape:
-            hit = ["host", None, torch.empty(w.shape, dtype=torch.float32, device="cuda")]
-            self._dev_cache[tag] = hit
-        refreshed = hit[1] != key or torch.is_grad_enabled()   # while training, never trust the key: `.data` writes do not move it
+        if hit is None or not hit.host or hit.tensor.shape != w.shape:
+            hit = self._dev_cache[tag] = _DevCopy(None, torch.empty(w.shape, dtype=torch.float32, device="cuda"))
+        refreshed = hit.key != key or torch.is_grad_enabled()   # while training, never trust the key: `.data` writes do not move it
         if refreshed:
-            hit[2].copy_(w.detach(), non_blocking=True)
-            hit[1] = key
-        return hit[2], refreshed
+            hit.tensor.copy_(w.detach(), non_blocking=True)
+            hit.key = key
+        return hit.tensor, refreshed
 
     def _forward_two_hop(self, nodes, training=False):
         """Both layers as one C call (sage_forward2).  Under grad mode the same call is one autograd node (autograd._TwoHop)
@@ -363,7 +372,7 @@ class Encoder(nn.Module):
         dev = torch.device("cuda")
         table = base._on_device(base.features.weight, "table")
         n = table.shape[0]
-        probe = nodes if isinstance(nodes, (list, tuple, np.ndarray)) else None      # a device tensor is not read back for this
+        probe = _probe_nodes(nodes)
         rp1, c1 = _device_csr(base.adj_lists, n, dev, probe)
         rp2, c2 = (rp1, c1) if self.adj_lists is base.adj_lists else _device_csr(self.adj_lists, n, dev, probe)
         (w1, r1), (w2, r2) = base._engine_weight("engine_w"), self._engine_weight("engine_w")
@@ -398,7 +407,7 @@ class Encoder(nn.Module):
         dev = torch.device("cuda")
         table = base._table_dev()
         n = table.shape[0]
-        probe = nodes if isinstance(nodes, (list, tuple, np.ndarray)) else None
+        probe = _probe_nodes(nodes)
         rp1, c1 = _device_csr(base.adj_lists, n, dev, probe)
         rp2, c2 = (rp1, c1) if self.adj_lists is base.adj_lists else _device_csr(self.adj_lists, n, dev, probe)
         ids = ops.as_ids(nodes, dev, n)
@@ -410,7 +419,7 @@ class Encoder(nn.Module):
         """One layer over a raw feature table (encoders.py:47-62 with features = nn.Embedding)."""
         dev = torch.device("cuda")
         table = self._table_dev()
-        rowptr, col = _device_csr(self.adj_lists, table.shape[0], dev, nodes if isinstance(nodes, (list, tuple, np.ndarray)) else None)
+        rowptr, col = _device_csr(self.adj_lists, table.shape[0], dev, _probe_nodes(nodes))
         ids = ops.as_ids(nodes, dev, table.shape[0])
         any_nonempty = torch.zeros(1, dtype=torch.int32, device=dev)
         nbr, cnt, _, _ = ops.sample_neighbors_any(rowptr, col, ids, self.num_sample, random.getrandbits(64), ops.TAG_INNER,

@@ -6,6 +6,10 @@ CSR adjacency, the fp32 feature table and both weight matrices stay in HBM, and
 `forward` enqueues sample -> frontier -> sample -> layer 1 -> layer 2 on the
 current stream without a host round trip (sage_forward2, include/sage355.h).
 """
+import ctypes
+import os
+from operator import attrgetter
+
 import torch
 
 from . import native
@@ -44,16 +48,109 @@ def pretransform_table(table, w1, rows_per_call=1 << 18):
     return y, eye                      # skipped and the column-sliced gather applies the activation and writes h1 itself
 
 
-class _Shared:
-    """What an engine and its siblings share about the caller's tensors: the caller's table behind a private copy (relabelled and / or
-    zero-padded; None when the engine reads the caller's table itself) with the version counter it was last copied at, the zero-padded
-    weight copies with the key they were made under, and the epoch that invalidate_weights() moves."""
+class _TableCopies:
+    """The feature table as the kernels read it, one object per engine and its siblings and the only writer of: `src`, the caller's
+    tensor; `table` / `ld`, the row-major working table -- `src` itself, or a private copy when the rows are renumbered (`degrees`:
+    internal node i is the caller's node_order[i], descending degree, stable; new_of_old inverts it) or the 16-B-per-lane kernels
+    cannot take `src` (width or leading dimension no multiple of 4 floats, base not 16-byte aligned: zero-padded, pads never
+    written); `sliced`, the optional slice-major copy of `table`.  Each copy has ONE stamp, the version counter of what it was
+    derived from, and is rewritten IN PLACE (role pipelines and captured graphs hold its address) on the current stream of the
+    engine that notices: engines that share it on other streams must be ordered behind that by the caller (RolePipeline: join ->
+    update -> fork).  Plain tensor work, on any device.
 
-    def __init__(self, src):
-        self.src = src
-        self.version = src._version if src is not None else None
-        self.weights_epoch = 0
-        self.w1p = self.w2p = self.wpad_key = None
+    Slice-major copy: float[d0 / W][N][W] (W = 32 floats = 128-byte slices by default) for the column-sliced layer-1 gather, so that
+    the XCD that owns a slice reads ONE contiguous array -- consecutive hub rows' slices share DRAM pages and L2 sets -- instead of
+    128 bytes out of every KiB.  Same-box A/B at config 3, gcn encoder: row-major 65.6 us per forward, slice-major 256-B slices
+    62.8, 128-B slices + one destination row per lane group 60.6 (gather alone 42.5 -> 37.5 us); config 4 (2^23 nodes) 96.0 ->
+    86.2; caller's node order 73.3 -> 61-64.  The concat encoder gets SLOWER with it (90 -> 96 us: its pacemaker is the two-pass
+    contraction, which a more aggressive gather beside it slows down), so "auto" = gcn encoder only.  Costs a second copy of the
+    table in HBM (1 GB of 288 at config 3); the row-major one stays for whole-row consumers (the concat encoder's own rows, the
+    backward, read-back).  slice_major: "auto" / True / False; SAGE_TABLE_SLICED = 0: never, 1: "auto" as above, 2: "auto" includes
+    the concat encoder (A/B); SAGE_TABLE_SLICE_FLOATS = 32 / 64 / 128 picks W.  Both are read once, here."""
+
+    def __init__(self, table, ld, num_nodes, degrees=None, slice_major="auto", concat=False):
+        self.src, self.d0 = table, table.shape[1]
+        self.node_order = self.new_of_old = None
+        if degrees is not None:
+            self.node_order = torch.sort(degrees, descending=True, stable=True).indices
+            self.new_of_old = torch.empty_like(self.node_order, dtype=torch.int32)
+            self.new_of_old[self.node_order] = torch.arange(len(degrees), dtype=torch.int32, device=degrees.device)
+        d0p = -(-self.d0 // 4) * 4
+        if degrees is not None or d0p != self.d0 or ld % 4 != 0 or table.data_ptr() % 16 != 0:
+            rows = len(degrees) if degrees is not None else table.shape[0]
+            self.table, self.ld, self.version = torch.zeros((rows, d0p), dtype=torch.float32, device=table.device), d0p, None
+            self.sync()
+        else:
+            self.table, self.ld, self.version = table, ld, table._version
+        env = os.environ.get("SAGE_TABLE_SLICED", "1")
+        w = self.slice_floats = int(os.environ.get("SAGE_TABLE_SLICE_FLOATS", "32"))
+        # whole slices, at least two of them, of rows that lie back to back, one per node
+        self.want_sliced = (slice_major is True or (slice_major == "auto" and (env == "2" or (not concat and env != "0")))) and (
+            w in (32, 64, 128) and d0p % w == 0 and d0p >= 2 * w and self.ld == d0p and self.table.shape[0] == num_nodes)
+        self.sliced = self.sliced_version = None
+
+    def version_key(self):
+        return self.src._version
+
+    def sync(self, force=False):
+        """Re-derive the private row-major copy from the caller's table when its version counter has moved since the last copy,
+        or always (force).  An integer compare when nothing changed; a no-op when the working table IS the caller's."""
+        if self.table is self.src or (not force and self.src._version == self.version):
+            return
+        with torch.no_grad():
+            self.table[:, :self.d0].copy_(self.src if self.node_order is None else self.src[self.node_order])
+        self.version = self.src._version
+
+    def slice_major(self, force=False):
+        """The slice-major copy (None: not wanted, or this shape has none): built at the first request, refreshed when the working
+        table's version counter has moved since, or always (force).  Every requester gets the same tensor."""
+        if self.want_sliced and (force or self.sliced_version != self.table._version):
+            rows, w = self.table.shape[0], self.slice_floats
+            with torch.no_grad():
+                src = self.table.view(rows, -1, w).permute(1, 0, 2)
+                if self.sliced is None:
+                    self.sliced = src.contiguous()
+                else:
+                    self.sliced.copy_(src)
+            self.sliced_version = self.table._version
+        return self.sliced
+
+
+class _WeightCopies:
+    """The weight matrices as the kernels read them, one object per engine family: the caller's w1 [h1, m * d0] / w2 [h2, m * h1]
+    themselves (m = 2 chunks for the concat encoder), or, when d0 or h1 is no multiple of 4 floats (Cora's 1433 raw features, the
+    reference's default 50-wide layer 1, model.py:543), copies with every chunk and h1 zero-padded to one, rewritten in place when
+    `version_key()` moves.  Zero weight rows / columns make the pad inert: relu(0) = 0, and sigmoid's 0.5 meets a zero column of W2.
+    `epoch` is what invalidate() moves, for writes that the tensors' version counters do not see; the engines key their bf16
+    planes with it too.  Same stream rule as _TableCopies."""
+
+    def __init__(self, w1, w2, d0, concat=False):
+        self.w1, self.w2, self.d0, self.h1, self.chunks = w1, w2, d0, w1.shape[0], 2 if concat else 1
+        self.d0p, self.h1p = -(-d0 // 4) * 4, -(-self.h1 // 4) * 4
+        self.padded = (self.d0p != d0) or (self.h1p != self.h1)
+        self.epoch, self.w1p, self.w2p, self.key = 0, None, None, None
+
+    def version_key(self):
+        return (self.w1.data_ptr(), self.w1._version, self.w2.data_ptr(), self.w2._version, self.epoch)
+
+    def invalidate(self):
+        self.epoch += 1
+
+    def tensors(self):
+        if not self.padded:
+            return self.w1, self.w2
+        key = self.version_key()
+        if key != self.key:
+            m, d0, h1, d0p, h1p = self.chunks, self.d0, self.h1, self.d0p, self.h1p
+            if self.w1p is None:
+                self.w1p = torch.zeros((h1p, m * d0p), dtype=torch.float32, device=self.w1.device)
+                self.w2p = torch.zeros((self.w2.shape[0], m * h1p), dtype=torch.float32, device=self.w1.device)
+            with torch.no_grad():
+                for c in range(m):
+                    self.w1p[:h1, c * d0p: c * d0p + d0] = self.w1[:, c * d0: (c + 1) * d0]
+                    self.w2p[:, c * h1p: c * h1p + h1] = self.w2[:, c * h1: (c + 1) * h1]
+            self.key = key
+        return self.w1p, self.w2p
 
 
 class TwoHopEngine:
@@ -64,8 +161,9 @@ class TwoHopEngine:
         enc2.adj_lists when it differs (injected pre-sampled sets), default the same.
         w1 [h1, d0 | 2*d0], w2 [h2, h1 | 2*h1]: the Encoders' `weight` Parameters
         (referenced, not copied: an optimizer step is seen by the next forward).
-        table: referenced too.  When the engine works on a private copy of it (relabel="degree", padded widths) the copy is
-        re-derived in place whenever the table's version counter moves; see refresh_table() for writes that do not move it."""
+        table: referenced too.  What the kernels read instead of the caller's tensors (renumbered / zero-padded / slice-major table
+        copies, zero-padded weights) belongs to one _TableCopies and one _WeightCopies, built here and shared with siblings: re-derived
+        in place whenever the caller's version counters move; refresh_table() / invalidate_weights() for writes that do not move them."""
         _need_gpu()
         self.rowptr1 = _chk(rowptr, torch.int64, "rowptr", 1)
         self.col1 = _chk(col, torch.int32, "col", 1)
@@ -73,56 +171,30 @@ class TwoHopEngine:
         self.col2 = self.col1 if col_outer is None else _chk(col_outer, torch.int32, "col_outer", 1)
         if self.rowptr2.shape[0] != self.rowptr1.shape[0]:
             raise native.SageError("inner and outer CSR must cover the same node ids")
-        self.table, self.table_ld = _row_major(table, "table")         # the caller's tensor itself (_row_major checks, never copies)
-        # relabel="degree": work on a copy of graph and table renumbered by descending degree, so that the rows gathered
-        # most often are neighbours in memory (config 3: gather 46 -> 40 us).  The outer-hop kernel translates the seeds
-        # (model.seed_map), so the caller keeps its ids and outputs stay in the caller's seed order; ids in intermediates()
-        # are the INTERNAL ones (self.node_order[i] = caller's id of internal node i).
-        # The device sampler is keyed by node id, so the sampled sets differ from the unrelabelled engine's (same law).
-        self.node_order = self._new_of_old = None
+        table, ld = _row_major(table, "table")         # the caller's tensor itself (_row_major checks, never copies)
         if relabel not in (None, "degree"):
             raise native.SageError("relabel must be None or 'degree'")
-        if _parent is not None:              # a sibling: the parent's renumbering and private table copies, shared (sibling())
-            self.node_order, self._new_of_old = _parent.node_order, _parent._new_of_old
-            self.table, self.table_ld = _parent.table, _parent.table_ld
-        elif relabel == "degree":
-            self._relabel_by_degree()
         self.num_nodes = self.rowptr1.shape[0] - 1
-        if self.table.shape[0] < self.num_nodes:
-            raise native.SageError(f"table has {self.table.shape[0]} rows for {self.num_nodes} nodes")
-        self.w1, self.w2 = w1, w2
-        self.d0 = table.shape[1]
-        self.h1, self.h2 = w1.shape[0], w2.shape[0]
+        if table.shape[0] < self.num_nodes:
+            raise native.SageError(f"table has {table.shape[0]} rows for {self.num_nodes} nodes")
+        self.d0, self.h1, self.h2 = table.shape[1], w1.shape[0], w2.shape[0]
         mult = 2 if concat else 1
         if tuple(w1.shape) != (self.h1, mult * self.d0) or tuple(w2.shape) != (self.h2, mult * self.h1):
             raise native.SageError(f"weight shapes {tuple(w1.shape)}, {tuple(w2.shape)} do not fit d0={self.d0}, concat={concat}")
-        # The 16-B-per-lane kernels want row widths that are multiples of 4 floats.  Cora's 1433 raw features and the
-        # reference's default 50-wide layer 1 (model.py:543) are not: the engine then works on zero-padded copies
-        # (table and weights re-derived in place whenever the caller's version counters move, _sync_table / _weights).
-        # Zero weight rows / columns make the pad inert: relu(0) = 0, and sigmoid's 0.5 meets a zero column of W2.
-        self.d0p, self.h1p = -(-self.d0 // 4) * 4, -(-self.h1 // 4) * 4
-        self._padded = (self.d0p != self.d0) or (self.h1p != self.h1)
-        if _parent is None and (self.d0p != self.d0 or self.table_ld % 4 != 0 or self.table.data_ptr() % 16 != 0):
-            padded = torch.zeros((self.table.shape[0], self.d0p), dtype=torch.float32, device=self.table.device)
-            padded[:, :self.d0] = self.table
-            self.table, self.table_ld = padded, self.d0p
-        # siblings share one _Shared: a refresh through any engine of a pipe reaches every one of them
-        self._shared = _parent._shared if _parent is not None else _Shared(table if self.table is not table else None)
-        # Slice-major second copy of the table for the column-sliced layer-1 gather: float[d0 / W][N][W] (W = 32 floats = 128-byte
-        # slices by default), so that the XCD that owns a slice reads ONE contiguous array -- consecutive hub rows' slices share DRAM
-        # pages and L2 sets -- instead of 128 bytes out of every KiB.  With it the 128-byte slices that round 2 measured SLOWER on the
-        # row-major table (fewer bytes past L2, 171 vs 214 MB, but 3.7 TB/s granules) are faster: same-box A/B at config 3, gcn encoder:
-        # row-major 65.6 us per forward, slice-major 256-B slices 62.8, 128-B slices + one destination row per lane group 60.6
-        # (gather alone 42.5 -> 37.5 us); config 4 (2^23 nodes) 96.0 -> 86.2; caller's node order 73.3 -> 61-64.  The concat encoder
-        # gets SLOWER with it (90 -> 96 us: its pacemaker is the two-pass contraction, which a more aggressive gather beside it
-        # slows down), so "auto" = gcn encoder only.  Costs a second copy of the table in HBM (1 GB of 288 at config 3); the row-major
-        # one stays for whole-row consumers (the concat encoder's own rows, the backward, read-back).
-        # slice_major: "auto" / True / False; SAGE_TABLE_SLICED=0 disables, SAGE_TABLE_SLICE_FLOATS = 32 / 64 / 128 picks W.
-        import os
-        self._table_sliced = _parent._table_sliced if _parent is not None else None
-        self._table_sliced_version = self.table._version
-        _sl = os.environ.get("SAGE_TABLE_SLICED", "1")              # 0: never, 1: "auto" as above, 2: "auto" includes the concat encoder (A/B)
-        self._want_sliced = slice_major is True or (slice_major == "auto" and (_sl == "2" or (not concat and _sl != "0")))
+        if _parent is not None:              # a sibling: the parent's owners themselves (sibling())
+            self._tables, self._wcopies = _parent._tables, _parent._wcopies
+        else:
+            # relabel="degree": work on a copy of graph and table renumbered by descending degree, so that the rows gathered
+            # most often are neighbours in memory (config 3: gather 46 -> 40 us).  The outer-hop kernel translates the seeds
+            # (model.seed_map), so the caller keeps its ids and outputs stay in the caller's seed order; ids in intermediates()
+            # are the INTERNAL ones (self.node_order[i] = caller's id of internal node i).
+            # The device sampler is keyed by node id, so the sampled sets differ from the unrelabelled engine's (same law).
+            deg = self.rowptr1[1:] - self.rowptr1[:-1] if relabel == "degree" else None
+            self._tables = _TableCopies(table, ld, self.num_nodes, deg, slice_major, concat)
+            if relabel == "degree":
+                self._renumber_graph()
+            self._wcopies = _WeightCopies(w1, w2, self.d0, concat)
+        self.d0p, self.h1p = self._wcopies.d0p, self._wcopies.h1p
         self._w1prep = self._w1prep_key = None
         self.prepare_weights = bool(prepare_weights)
         self.k1, self.k2 = int(k1), int(k2)
@@ -130,28 +202,24 @@ class TwoHopEngine:
         self.act1, self.act2 = int(act1), int(act2)
         self.nan_empty, self.fused = bool(nan_empty), bool(fused)
         self.device = self.table.device
-        self.max_batch = 0
-        self.workspace = None
-        self.layout = native.WsLayout()
-        self._model_key = None
-        self._model_c = None
-        self._model_q = None
-        self._queue = None
-        self._cursor = None
-        self._graph = None
-        self._last_batch = 0
+        self.max_batch, self.workspace, self.layout, self._last_batch, self._queue_batch = 0, None, native.WsLayout(), 0, 0
+        self._model_key = self._model_c = self._model_q = None
+        self._queue = self._cursor = self._graph = self._queue_seeds = self._graph_out = None      # set_queue / capture
         self.keep_means = False              # True: every forward leaves the layer-1 means in the workspace (training: backward_weights reads them)
         self._kept_means = False             # ... and whether the LAST forward did
         self.generation = 0                  # forwards run so far: a backward checks that the workspace still holds ITS forward
         self._bwd = None                     # scratch of backward_weights (allocated on first use)
         self._reserve(max_batch)
 
-    def _relabel_by_degree(self):
-        n = self.rowptr1.shape[0] - 1
-        deg = self.rowptr1[1:] - self.rowptr1[:-1]
-        order = torch.sort(deg, descending=True, stable=True).indices           # internal -> caller's id
-        new_of_old = torch.empty_like(order)
-        new_of_old[order] = torch.arange(n, device=order.device)
+    # the owners' fields that callers read through the engine (bench.py, train.py, tests); read-only here
+    table, table_ld = property(attrgetter("_tables.table")), property(attrgetter("_tables.ld"))
+    node_order, _new_of_old = property(attrgetter("_tables.node_order")), property(attrgetter("_tables.new_of_old"))
+    _table_sliced, _slice_floats = property(attrgetter("_tables.sliced")), property(attrgetter("_tables.slice_floats"))
+    w1, w2, _padded = property(attrgetter("_wcopies.w1")), property(attrgetter("_wcopies.w2")), property(attrgetter("_wcopies.padded"))
+
+    def _renumber_graph(self):
+        """Both CSRs in the internal ids of relabel="degree" (the order itself is _TableCopies'), rows sorted."""
+        n, order, new_of_old = self.num_nodes, self.node_order, self._new_of_old.long()
 
         def renumber(rowptr, col):
             d = rowptr[1:] - rowptr[:-1]
@@ -162,57 +230,30 @@ class TwoHopEngine:
             return rp, (key % n).to(torch.int32)
 
         same = self.rowptr2 is self.rowptr1 and self.col2 is self.col1
-        rp1, c1 = renumber(self.rowptr1, self.col1)
-        if same:
-            rp2, c2 = rp1, c1
-        else:
-            rp2, c2 = renumber(self.rowptr2, self.col2)
-        self.rowptr1, self.col1, self.rowptr2, self.col2 = rp1, c1, rp2, c2
-        self.table = self.table[order].contiguous()
-        self.table_ld = self.table.shape[1]
-        self.node_order, self._new_of_old = order, new_of_old.to(torch.int32)
+        self.rowptr1, self.col1 = renumber(self.rowptr1, self.col1)
+        self.rowptr2, self.col2 = (self.rowptr1, self.col1) if same else renumber(self.rowptr2, self.col2)
 
     def sibling(self):
-        """Another engine over the SAME device graph / table / weights (shared, not copied) with a workspace of its own:
-        what every additional mini-batch in flight needs.  The private copies (renumbered / zero-padded table, slice-major copy,
-        zero-padded weights) are shared too, so a refresh through any one engine reaches all of them."""
-        src = self._shared.src if self._shared.src is not None else self.table
-        return TwoHopEngine(self.rowptr1, self.col1, src, self.w1, self.w2, self.k1, self.k2, concat=self.concat,
+        """Another engine over the SAME device graph / table / weights (shared, not copied) with a workspace, bf16 weight planes and
+        model struct of its own: what every additional mini-batch in flight needs.  It holds this engine's _TableCopies and
+        _WeightCopies themselves: whichever engine notices an update re-derives the copies once, for all of them."""
+        return TwoHopEngine(self.rowptr1, self.col1, self._tables.src, self.w1, self.w2, self.k1, self.k2, concat=self.concat,
                             agg_self_loop=self.agg_self_loop, act1=self.act1, act2=self.act2, nan_empty=self.nan_empty, fused=self.fused,
                             max_batch=self.max_batch, rowptr_outer=self.rowptr2, col_outer=self.col2, relabel=None,
-                            prepare_weights=self.prepare_weights, slice_major=self._table_sliced is not None, _parent=self)
-
-    def _seeds_in(self, seeds):
-        """Seeds cross the boundary in the CALLER's ids; with relabel="degree" the outer-hop kernel translates them
-        (model.seed_map), inside the forward."""
-        return seeds
+                            prepare_weights=self.prepare_weights, _parent=self)
 
     def _weights(self):
         """The weight tensors the kernels read: the caller's own, or zero-padded copies kept in step with them."""
-        if not self._padded:
-            return self.w1, self.w2
-        s = self._shared
-        key = (self.w1.data_ptr(), self.w1._version, self.w2.data_ptr(), self.w2._version, s.weights_epoch)
-        if key != s.wpad_key:
-            m = 2 if self.concat else 1
-            if s.w1p is None:
-                s.w1p = torch.zeros((self.h1p, m * self.d0p), dtype=torch.float32, device=self.device)
-                s.w2p = torch.zeros((self.h2, m * self.h1p), dtype=torch.float32, device=self.device)
-            with torch.no_grad():                # in place: the pointers a pipe or a captured graph holds stay valid
-                for c in range(m):
-                    s.w1p[:self.h1, c * self.d0p: c * self.d0p + self.d0] = self.w1[:, c * self.d0: (c + 1) * self.d0]
-                    s.w2p[:, c * self.h1p: c * self.h1p + self.h1] = self.w2[:, c * self.h1: (c + 1) * self.h1]
-            s.wpad_key = key
-        return s.w1p, s.w2p
+        return self._wcopies.tensors()
 
     def invalidate_weights(self):
         """The weights were written in a way that does not move their version counters (`.data`, a collective, a replayed hipGraph):
-        forget every cached form of them (zero-padded copies, bf16 planes, the C model struct), for this engine and its siblings; the
-        next forward rebuilds them, in place, from the tensors as they are NOW.  In-place writes that move the version counters
-        (an optimizer step, `w.add_(...)` under no_grad) need no call: the next forward notices them.  Between replays of a captured
-        graph use refresh_weights() instead."""
-        self._shared.weights_epoch += 1
-        self._w1prep_key = self._model_key = None
+        move the weights epoch that the shared zero-padded copies and every engine's own bf16 planes are keyed with; the next forward
+        of this engine or a sibling rebuilds what it reads, in place, from the tensors as they are NOW.  In-place writes that move the
+        version counters (an optimizer step, `w.add_(...)` under no_grad) need no call: the next forward notices them.  Between
+        replays of a captured graph use refresh_weights() instead."""
+        self._wcopies.invalidate()
+        self._model_key = None
 
     def refresh_weights(self):
         """Re-read the caller's weights NOW, whatever wrote them, into the zero-padded copies and the bf16 planes, in place: the call to
@@ -222,12 +263,12 @@ class TwoHopEngine:
 
     def _prepare_w1(self, w1):
         """enc1.weight split into bf16 planes in the contraction kernel's register order (sage_prepare_weights), redone
-        whenever the weight tensor or its version counter changes; None when this layer shape has no prepared form."""
+        whenever the weight tensor, its version counter or the weights epoch changes; None when this layer shape has no prepared form."""
         L = native.lib()
         need = L.sage_prepared_weight_bytes(self.d0p, self.h1p, int(self.concat))
         if need == 0 or not self.prepare_weights:
             return None
-        key = (w1.data_ptr(), w1._version, self._shared.weights_epoch)
+        key = (w1.data_ptr(), w1._version, self._wcopies.epoch)
         if self._w1prep is None or self._w1prep.numel() != need:
             self._w1prep = torch.empty(need, dtype=torch.uint8, device=self.device)
             self._w1prep_key = None
@@ -237,53 +278,14 @@ class TwoHopEngine:
             self._w1prep_key = key
         return self._w1prep
 
-    def _slice_table(self):
-        """Build (or refresh, if the table was written in place since) the slice-major copy -- only when layer 1 runs as the
-        column-sliced gather with 256-byte slices of whole 64-float pieces."""
-        import os
-        w = int(os.environ.get("SAGE_TABLE_SLICE_FLOATS", "32"))         # floats per slice: 32 (128 B, default) / 64 / 128
-        if getattr(self, "_slice_floats", None) != w:
-            self._model_key = None           # the model struct carries the slice width (a sibling's first one was built before it was known)
-        self._slice_floats = w
-        ok = (self._want_sliced and bool(self.layout.layer1_split) and w in (32, 64, 128) and self.d0p % w == 0 and self.d0p >= 2 * w
-              and self.table_ld == self.d0p and self.table.shape[0] == self.num_nodes)
-        if not ok:
-            self._table_sliced = None
-            return
-        if self._table_sliced is None or self._table_sliced_version != self.table._version:
-            n_rows = self.table.shape[0]
-            src = self.table.view(n_rows, self.d0p // w, w).permute(1, 0, 2)
-            if self._table_sliced is not None and tuple(self._table_sliced.shape) == tuple(src.shape):
-                # refreshed IN PLACE: a role pipeline built over this engine copied the buffer's pointer at sage_pipe_create
-                # (ADVICE r3: a new tensor per rebuild left the pipe reading a stale, later a freed, copy)
-                self._table_sliced.copy_(src)
-            else:
-                self._table_sliced = src.contiguous()
-                self._model_key = None
-            self._table_sliced_version = self.table._version
-
-    def _sync_table(self, force=False):
-        """Re-derive the private table copy (renumbered and / or zero-padded) from the caller's table, IN PLACE (role pipelines and
-        captured graphs hold its pointer), when the caller's version counter has moved since the last copy, or always (force).
-        An integer compare when nothing changed; a no-op for an engine that reads the caller's table itself."""
-        s = self._shared
-        if s.src is None or (not force and s.src._version == s.version):
-            return
-        with torch.no_grad():
-            rows = s.src if self.node_order is None else s.src[self.node_order]
-            self.table[:, :self.d0].copy_(rows)          # the pad columns are never written: they stay zero
-        s.version = s.src._version
-
     def refresh_table(self):
         """The table was written in a way that does not move its version counter (`.data`, a collective, a replayed hipGraph): re-read
-        it into the engine's private copies -- the renumbered / zero-padded copy and the slice-major one -- in place, on the current
-        stream (pointers held by role pipelines and captured graphs stay valid), for this engine and its siblings.  In-place writes
-        that move the version counter (`table[rows] = x`) need no call before a forward; before a REPLAY of a captured graph call this
-        after any table write."""
-        self._sync_table(force=True)
-        self._table_sliced_version = None
-        if self.layout.total_bytes:
-            self._slice_table()
+        it into the shared table copies (renumbered / zero-padded, and the slice-major one where it exists) in place, on the current
+        stream: held pointers stay valid; siblings on other streams must be ordered behind this call.  In-place writes that move the
+        version counter (`table[rows] = x`) need no call before a forward; before a REPLAY of a captured graph call this after any."""
+        self._tables.sync(force=True)
+        if self._tables.sliced is not None:
+            self._tables.slice_major(force=True)
 
     def _wants_means(self):
         """Does this forward have to leave the layer-1 means in the workspace (sage_model_t.keep_means)?  Yes for an engine that trains
@@ -292,19 +294,21 @@ class TwoHopEngine:
         return bool(self.keep_means or (torch.is_grad_enabled() and (self.w1.requires_grad or self.w2.requires_grad)))
 
     def _model(self, queued=False, keep_means=False):
-        m = self._model_cached(queued)
+        """The C model struct over the copies as they are NOW (brought up to date here), rebuilt only when an address in it moved."""
+        self._tables.sync()
+        # layer 1 of THIS engine's layout decides whether its struct names the slice-major copy (no layout yet: not split)
+        sliced = self._tables.slice_major() if self.layout.layer1_split else None
+        w1, w2 = self._weights()
+        prep = self._prepare_w1(w1.detach())
+        key = (w1.data_ptr(), w2.data_ptr(), self._queue.data_ptr() if self._queue is not None else 0, prep.data_ptr() if prep is not None else 0,
+               sliced.data_ptr() if sliced is not None else 0)
+        if self._model_key != key:
+            self._build_model(key, w1, w2, prep, sliced)
+        m = self._model_q if queued else self._model_c
         m.keep_means = int(bool(keep_means))
         return m
 
-    def _model_cached(self, queued=False):
-        self._sync_table()
-        if self.layout.total_bytes:          # the layout is known (after the first _reserve)
-            self._slice_table()
-        w1, w2 = self._weights()
-        prep = self._prepare_w1(w1.detach())
-        key = (w1.data_ptr(), w2.data_ptr(), self._queue.data_ptr() if self._queue is not None else 0, prep.data_ptr() if prep is not None else 0)
-        if self._model_key == key:
-            return self._model_q if queued else self._model_c
+    def _build_model(self, key, w1, w2, prep, sliced):
         _row_major(w1.detach(), "w1")
         _row_major(w2.detach(), "w2")
         if not (w1.is_contiguous() and w2.is_contiguous()):
@@ -316,8 +320,8 @@ class TwoHopEngine:
             int(self.max_batch))
         self._model_c.w1_prepared = prep.data_ptr() if prep is not None else None
         self._model_c.seed_map = self._new_of_old.data_ptr() if self._new_of_old is not None else None
-        self._model_c.table_sliced = self._table_sliced.data_ptr() if self._table_sliced is not None else None
-        self._model_c.table_slice_floats = getattr(self, "_slice_floats", 64)
+        self._model_c.table_sliced = sliced.data_ptr() if sliced is not None else None
+        self._model_c.table_slice_floats = self._slice_floats
         self._model_c.w1_is_identity = 1 if (getattr(self.w1, "_sage_identity", False) and not self.concat and not self._padded) else 0
         self._model_q = None
         if self._queue is not None:
@@ -326,7 +330,6 @@ class TwoHopEngine:
             self._model_q.queue_len = self._queue.shape[0]
             self._model_q.queue_cursor = self._cursor.data_ptr()
         self._model_key = key
-        return self._model_q if queued else self._model_c
 
     # ---- device-side batch queue + hipGraph replay (no per-batch host work) ----
     def set_queue(self, seeds, rng_seeds):
@@ -340,7 +343,6 @@ class TwoHopEngine:
             raise native.SageError("set_queue: one sampler key per batch")
         if seeds.numel() and (int(seeds.min()) < 0 or int(seeds.max()) >= self.num_nodes):     # one sync, outside any timed loop
             raise native.SageError(f"set_queue: seed id outside [0, {self.num_nodes})")
-        seeds = self._seeds_in(seeds).contiguous()
         self._reserve(b)
         desc = torch.empty((s, 2), dtype=torch.int64)
         desc[:, 0] = seeds.data_ptr() + torch.arange(s, dtype=torch.int64) * (b * 4)
@@ -420,7 +422,6 @@ class TwoHopEngine:
         stage_events: optional (c_void_p * 8) of hipEvent_t recorded around the four stages."""
         if not (isinstance(seeds, torch.Tensor) and seeds.is_cuda and seeds.dtype == torch.int32 and seeds.is_contiguous()):
             seeds = as_ids(seeds, self.device, self.num_nodes)
-        seeds = self._seeds_in(seeds)
         b = seeds.shape[0]
         if b > self.max_batch:
             self._reserve(b)
@@ -466,18 +467,14 @@ class TwoHopEngine:
                          "any": torch.ones(1, dtype=torch.int32, device=dev)}
         sc = self._bwd
         first = b if self.concat else 0
-        k1, k2, h1p, d0p = self.k1, self.k2, self.h1p, self.d0p
+        k2, h1p, d0p = self.k2, self.h1p, self.d0p
         # rows of layer 1 = first + frontier size, kept on the device (counters[8] is the read-back copy the forward's last block leaves)
-        torch.add(self._view(L.counters, 16, torch.int32)[8:9], first, out=sc["nlive"])
+        ws = self._ws_views()
+        torch.add(ws("counters")[8:9], first, out=sc["nlive"])
         grad_out = grad_out.contiguous()
         w1p, w2p = self._weights()
-        h1 = self._view(L.h1, L.max_s1 * h1p, torch.float32).view(L.max_s1, h1p)
-        row2 = self._view(L.row2, b * k2, torch.int32).view(b, k2)
-        cnt2 = self._view(L.cnt2, b, torch.int32)
-        self_row2 = self._view(L.self_row2, b, torch.int32) if self.agg_self_loop else None
-        nbr1 = self._view(L.nbr1, L.max_s1 * k1, torch.int32).view(L.max_s1, k1)
-        cnt1 = self._view(L.cnt1, L.max_s1, torch.int32)
-        s1_nodes = self._view(L.s1_nodes, L.max_s1, torch.int32)
+        h1, row2, cnt2, nbr1, cnt1, s1_nodes = ws("h1"), ws("row2"), ws("cnt2"), ws("nbr1"), ws("cnt1"), ws("s1_nodes")
+        self_row2 = ws("self_row2") if self.agg_self_loop else None
         def scratch(name, nbytes):
             t = sc.get(name)
             if t is None or t.numel() < nbytes:
@@ -505,7 +502,7 @@ class TwoHopEngine:
             self_row1 = s1_nodes if self.agg_self_loop else None
             if L.layer1_split and self._kept_means:
                 # the split layer (sliced gather + contraction) left the means of this very forward in the workspace: no second gather
-                agg1 = self._view(L.agg1, L.max_s1 * d0p, torch.float32).view(L.max_s1, d0p)
+                agg1 = ws("agg1")
             else:
                 if sc["agg1"] is None:
                     sc["agg1"] = torch.zeros(L.max_s1, d0p, device=dev)
@@ -530,27 +527,32 @@ class TwoHopEngine:
         itemsize = torch.empty(0, dtype=dtype).element_size()
         return self.workspace[off: off + count * itemsize].view(dtype)
 
+    def _ws_views(self):
+        """field -> typed view of that field of the workspace, for the LAST forward's batch: the one table of layout field -> dtype,
+        shape that backward_weights() and intermediates() read the workspace through."""
+        L, b, i32, f32 = self.layout, self._last_batch, torch.int32, torch.float32
+        fields = {"counters": (i32, (16,)), "s1_nodes": (i32, (L.max_s1,)), "nbr2": (i32, (b, self.k2)), "cnt2": (i32, (b,)),
+                  "row2": (i32, (b, self.k2)), "self_row2": (i32, (b,)), "nbr1": (i32, (L.max_s1, self.k1)), "cnt1": (i32, (L.max_s1,)),
+                  "h1": (f32, (L.max_s1, self.h1p)), "agg1": (f32, (L.max_s1, self.d0p))}
+
+        def view(field):
+            dtype, shape = fields[field]
+            return self._view(getattr(L, field), torch.Size(shape).numel(), dtype).view(shape)
+        return view
+
     def intermediates(self):
         """Sampled sets and layer-1 state of the LAST forward (synchronises)."""
-        L, b = self.layout, self._last_batch
+        ws = self._ws_views()
         torch.cuda.synchronize()
-        counters = self._view(L.counters, 16, torch.int32).cpu()
-        first = b if self.concat else 0
-        n1 = first + int(counters[8])          # [8..15]: the counters as the last forward left them
-        s1 = self._view(L.s1_nodes, L.max_s1, torch.int32)[:n1]
+        first = self._last_batch if self.concat else 0
+        n1 = first + int(ws("counters").cpu()[8])          # [8..15]: the counters as the last forward left them
         return {
-            "n_s1": n1, "first_frontier_row": first, "s1_nodes": s1,
-            "nbr2": self._view(L.nbr2, b * self.k2, torch.int32).view(b, self.k2),
-            "cnt2": self._view(L.cnt2, b, torch.int32),
-            "row2": self._view(L.row2, b * self.k2, torch.int32).view(b, self.k2),
-            "nbr1": self._view(L.nbr1, L.max_s1 * self.k1, torch.int32).view(L.max_s1, self.k1)[:n1],
-            "cnt1": self._view(L.cnt1, L.max_s1, torch.int32)[:n1],
-            "h1": self._view(L.h1, L.max_s1 * self.h1p, torch.float32).view(L.max_s1, self.h1p)[:n1, :self.h1],
+            "n_s1": n1, "first_frontier_row": first, "s1_nodes": ws("s1_nodes")[:n1],
+            "nbr2": ws("nbr2"), "cnt2": ws("cnt2"), "row2": ws("row2"), "nbr1": ws("nbr1")[:n1], "cnt1": ws("cnt1")[:n1],
+            "h1": ws("h1")[:n1, :self.h1],
             # the layer-1 means: only a split layer 1 writes them, and only when the forward was asked to keep them (keep_means)
-            "agg1": (self._view(L.agg1, L.max_s1 * self.d0p, torch.float32).view(L.max_s1, self.d0p)[:n1, :self.d0]
-                     if (L.layer1_split and self._kept_means) else None),
+            "agg1": ws("agg1")[:n1, :self.d0] if (self.layout.layer1_split and self._kept_means) else None,
         }
-
 
 
 _PROCESS_ROLE_STREAMS = {}          # (device, distinct role letters, priorities) -> the role streams of the process's first such pipeline
@@ -565,11 +567,11 @@ class RolePipeline:
     "SGDL" = four streams, "SGDD" = D and L share one, "SSSS" = one stream (= sage_forward2's launch order).
     `priorities`: per distinct stream, 0 = default, -1 = high (HIP stream priority; the latency-bound roles).
     The reference has no counterpart (model.py:240-252 is one batch at a time on the host)."""
+    _h = None          # the native pipe; a class default because __del__ also meets a pipe whose __init__ failed or never ran
 
     def __init__(self, rowptr, col, table, w1, w2, k1, k2, batch, depth=4, roles="SGDL", priorities=None, streams=None, threads=None,
                  window=None, **engine_kwargs):
-        import ctypes
-        import os
+        self._broken, self._cap_stream = False, None
         if depth < 1 or depth > native.PIPE_MAX_DEPTH:
             raise native.SageError(f"RolePipeline: depth must be in [1, {native.PIPE_MAX_DEPTH}]")
         if len(roles) != 4:
@@ -600,7 +602,6 @@ class RolePipeline:
         ws = (ctypes.c_void_p * depth)(*[e.workspace.data_ptr() for e in self.engines])
         st = (ctypes.c_void_p * 4)(*[s.cuda_stream for s in self.role_streams])
         self._h = ctypes.c_void_p()
-        self._wkey = None
         native.check(native.lib().sage_pipe_create(e0._model(), self.batch, depth, ws, e0.workspace.numel(), st, ctypes.byref(self._h)),
                      "pipe_create")
         self._wkey = self._weights_key()
@@ -630,24 +631,24 @@ class RolePipeline:
     def flush(self):
         """Every submitted batch has been ENQUEUED on the role streams (host enqueue threads; a no-op without them).  Call it
         before synchronising the device or the role streams yourself; join() / synchronize() do."""
-        rc = native.lib().sage_pipe_flush(self._h)
+        self._check(native.lib().sage_pipe_flush(self._h), "pipe_flush")
+
+    def _check(self, rc, what):
         if rc != 0:
-            self._broken = rc == native.ELAUNCH
-            native.check(rc, "pipe_flush")
+            self._broken = rc == native.ELAUNCH      # argument errors are raised before anything is enqueued: the pipe stays usable
+            native.check(rc, what)
 
     def _check_usable(self):
         # a submit that failed between two of its enqueues leaves a batch half-way through the role streams, its workspace dirty and
         # its hand-off events unrecorded: later batches on that slot would wait for ever or sample into a full frontier table
-        if getattr(self, "_broken", False):
+        if self._broken:
             raise native.SageError("RolePipeline: an earlier submit failed half-way; synchronise, drop this pipe and create a new one")
 
     def _weights_key(self):
         """The CALLER's tensors' version counters (not those of the engine's private copies, which only move once they are rebuilt) and
         the weights epoch: integers, no side effects -- nothing is rewritten before the pipe has been joined."""
         e0 = self.engines[0]
-        s = e0._shared
-        table = s.src if s.src is not None else e0.table
-        return (e0.w1.data_ptr(), e0.w2.data_ptr(), e0.w1._version, e0.w2._version, table._version, s.weights_epoch)
+        return e0._wcopies.version_key(), e0._tables.version_key()
 
     def _sync_weights(self):
         """Weights or table written in place since the last submit (version counters): re-prepare the weight planes / re-derive the
@@ -675,12 +676,11 @@ class RolePipeline:
         self._sync_weights()
 
     def __del__(self):
-        h = getattr(self, "_h", None)
-        if h:
+        if self._h:
             try:
-                native.lib().sage_pipe_flush(h)
+                native.lib().sage_pipe_flush(self._h)
                 torch.cuda.synchronize()
-                native.lib().sage_pipe_destroy(h)
+                native.lib().sage_pipe_destroy(self._h)
             except Exception:
                 pass
             self._h = None
@@ -708,11 +708,8 @@ class RolePipeline:
         """submit() with two hipEvent_t (a ctypes c_void_p * 2) recorded on stream G around the layer-1 gather."""
         self._sync_weights()
         self._check_usable()
-        rc = native.lib().sage_pipe_submit_profiled(self._h, seeds.data_ptr(), int(key) & 0xFFFFFFFFFFFFFFFF, out.data_ptr(),
-                                                    out.stride(0), gather_events)
-        if rc != 0:
-            self._broken = rc == native.ELAUNCH
-            native.check(rc, "pipe_submit_profiled")
+        self._check(native.lib().sage_pipe_submit_profiled(self._h, seeds.data_ptr(), int(key) & 0xFFFFFFFFFFFFFFFF, out.data_ptr(),
+                                                           out.stride(0), gather_events), "pipe_submit_profiled")
 
     def submit(self, seeds, key, out):
         """One batch: seeds int32 [batch] device tensor, out [batch, h2] fp32 device tensor (both must stay alive
@@ -724,15 +721,12 @@ class RolePipeline:
             raise native.SageError("RolePipeline.submit: `out` must be a [batch, h2] fp32 device tensor with unit inner stride")
         self._check_usable()
         self._sync_weights()
-        rc = native.lib().sage_pipe_submit(self._h, seeds.data_ptr(), int(key) & 0xFFFFFFFFFFFFFFFF, out.data_ptr(), out.stride(0))
-        if rc != 0:
-            self._broken = rc == native.ELAUNCH      # argument errors are raised before anything is enqueued: the pipe stays usable
-            native.check(rc, "pipe_submit")
+        self._check(native.lib().sage_pipe_submit(self._h, seeds.data_ptr(), int(key) & 0xFFFFFFFFFFFFFFFF, out.data_ptr(), out.stride(0)),
+                    "pipe_submit")
 
     def submit_many(self, seeds, keys, out, segment_start=False):
         """seeds int32 [n, batch] (device, contiguous), keys: n sampler keys, out [slots, batch, h2] with slots >= depth
         (batch i lands in out[i % slots]) -- ONE host call enqueues all n batches."""
-        import ctypes
         if not (isinstance(seeds, torch.Tensor) and seeds.is_cuda and seeds.dtype == torch.int32 and seeds.is_contiguous()
                 and seeds.dim() == 2 and seeds.shape[1] == self.batch):
             raise native.SageError("RolePipeline.submit_many: seeds must be a contiguous int32 device tensor [n, batch]")
@@ -745,11 +739,8 @@ class RolePipeline:
         self._sync_weights()
         karr = (ctypes.c_uint64 * n)(*[int(k) & 0xFFFFFFFFFFFFFFFF for k in keys])
         self._check_usable()
-        rc = native.lib().sage_pipe_submit_many(self._h, seeds.data_ptr(), self.batch, karr, n, out.data_ptr(), out.stride(1),
-                                                out.stride(0), out.shape[0], 1 if segment_start else 0)
-        if rc != 0:
-            self._broken = rc == native.ELAUNCH
-            native.check(rc, "pipe_submit_many")
+        self._check(native.lib().sage_pipe_submit_many(self._h, seeds.data_ptr(), self.batch, karr, n, out.data_ptr(), out.stride(1),
+                                                       out.stride(0), out.shape[0], 1 if segment_start else 0), "pipe_submit_many")
 
     def reset(self):
         """Forget every submit (after synchronising): the next `depth` submits find their workspaces free."""
@@ -765,8 +756,7 @@ class RolePipeline:
         self._sync_weights()
         self._check_usable()
         if stream is None:
-            stream = getattr(self, "_cap_stream", None) or torch.cuda.Stream(device=self.device)
-            self._cap_stream = stream
+            stream = self._cap_stream = self._cap_stream or torch.cuda.Stream(device=self.device)
         self.flush()
         torch.cuda.synchronize()
         was_threaded = self.threads

@@ -311,3 +311,39 @@ def test_update_reaches_the_drop_in_encoders(cuda, update):
     assert not _same(want, before), "the update changed nothing"
     assert _same(after, want), "output differs from freshly built modules on the updated tensors" + (" (= the stale output)" if _same(after, before) else "")
     assert _pads_are_zero(enc2._engine)
+
+
+def test_a_sibling_made_before_the_first_forward_shares_the_slice_major_copy():
+    """The smallest split layer 1 (512 seeds x fanout 15 + 512 = the 8192 frontier rows of sage_forward2_layout's threshold, d0 = 64):
+    whether a sibling's layer 1 reads the slice-major copy must not depend on whether it was created before or after the parent's
+    first forward, and after a table write the copy is refreshed once, in place, by whichever engine runs first."""
+    graph = rmat_graph(12, 60_000, seed=3)
+    d0, h1, h2, b, k1, k2 = 64, 32, 32, 512, 10, 15
+    gen = torch.Generator().manual_seed(12)
+    table = torch.randn(graph.num_nodes, d0, generator=gen).to(DEV)
+    w1 = (torch.randn(h1, d0, generator=gen) / np.sqrt(d0)).to(DEV)
+    w2 = (torch.randn(h2, h1, generator=gen) / np.sqrt(h1)).to(DEV)
+    rng = np.random.default_rng(12)
+    cand = np.nonzero(graph.degrees() > 0)[0]
+    seeds = torch.from_numpy(rng.choice(cand, b, replace=False).astype(np.int32)).to(DEV)
+    rowptr, col = graph.to(DEV)
+    eng = TwoHopEngine(rowptr, col, table, w1, w2, k1, k2, max_batch=b)
+    sib = eng.sibling()                                # before any forward
+    assert eng.layout.layer1_split == 1 and sib.layout.layer1_split == 1
+    before = eng.forward(seeds, seed=KEY).clone()
+    sib_out = sib.forward(seeds, seed=KEY).clone()
+    assert eng._table_sliced is not None and sib._table_sliced is eng._table_sliced
+    ptr = eng._table_sliced.data_ptr()
+    assert eng._model().table_sliced == ptr and sib._model().table_sliced == ptr
+    assert torch.equal(sib_out, before)
+    rows = torch.from_numpy(rng.choice(cand, 256, replace=False).astype(np.int64)).to(DEV)
+    table[rows] = (torch.randn(len(rows), d0, generator=gen) * 2).to(DEV)
+    sib_after = sib.forward(seeds, seed=KEY).clone()    # the sibling notices and refreshes the shared copy ...
+    stamp = eng._tables.sliced_version
+    eng_after = eng.forward(seeds, seed=KEY).clone()    # ... the parent finds it up to date
+    assert eng._tables.sliced_version == stamp == table._version
+    want = TwoHopEngine(rowptr, col, table, w1, w2, k1, k2, max_batch=b).forward(seeds, seed=KEY)
+    assert not torch.equal(want, before), "the update changed nothing: it cannot tell a fresh copy from a stale one"
+    assert torch.equal(sib_after, want) and torch.equal(eng_after, want)
+    assert eng._table_sliced.data_ptr() == ptr and sib._table_sliced is eng._table_sliced
+    assert eng._model().table_sliced == ptr and sib._model().table_sliced == ptr
