@@ -1,0 +1,299 @@
+// csr_mean backward: the adjoint of sage_csr_mean(nodes = NULL, n = num_nodes) with respect to `table` (include/sage355.h).
+//
+// The forward's row v is (1 / c_v) * (sum of table rows of v's entries [+ table[v] by the set-union rule]); so table row u
+// receives w_x * grad_out[x] once per entry u of row x, plus w_u * grad_out[u] if u joined its own mean.  The entries that
+// name u are row u of the TRANSPOSED CSR, which the caller builds once per graph: the sum is then the forward's computation on
+// the transposed graph -- same split of long rows into chunks of SAGE_CSR_MEAN_CHUNK entries, same launches, same fall-back
+// when the item list is too small -- with a weight per entry and no final division.  No float atomics.
+//
+// Launches, all on the caller's stream, no host round trip:
+//   a. fill     found[v] := 0                                             (self_loop only)
+//   b. scan     one wave per 512 entries of the FORWARD col[]: found[v] := 1 where row v holds v.  Cut by entries, not by
+//               rows, so a hub costs its chunks' waves what any other 512 entries cost; the row of an entry is found by a
+//               bisection of rowptr inside the rows the wave's 512 entries span.  Racing stores all store 1.   (self_loop only)
+//   c. weight   per node: flag[v] := extra_v (in place of found), w[v] := c_v > 0 ? 1.0f / (float)c_v : 0
+//   1-3. count, carry, expand on the transposed rows (sage_csr_common.h)
+//   4. chunk    one wave per item: partials[item] := the chunk's weighted sum
+//   5. rows     one wave per row: short rows summed in place; long rows = their partials in chunk order; self term; store
+//
+// Arithmetic of a row (its bits depend on nothing else): p_c = fma(w_x, g_x, ...fma(w_x0, g_x0, 0)) over chunk c's entries in
+// stored order; S = 0 + p_0 + p_1 + ...; S = fma(w_u, g_u, S) if extra_u; grad_table[r] = S.  Every term is ONE fma, in the
+// chunk pass and in the fall-back alike (sum_weighted is the only place that forms a term).
+#include "sage_csr_common.h"
+
+namespace {
+
+struct BwdLayout {
+    size_t off, carry, item_row, partials, weight, flag, total;
+    int64_t cap;       // item entries (= partial rows) the workspace holds
+    int64_t nblocks;   // count-kernel blocks
+};
+
+bool bwd_layout(int64_t num_nodes, int32_t n, int64_t max_edges, int32_t dim, BwdLayout* L) {
+    if (num_nodes < 0 || num_nodes >= (1ll << 31) || n < 0 || max_edges < 0 || dim < 1) return false;
+    L->cap = csr_item_cap(n, max_edges);
+    if (L->cap >= (1ll << 31)) return false;
+    L->nblocks = ((int64_t)n + kCountTile - 1) / kCountTile;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = align256(off + std::max<size_t>(bytes, 1)); return o; };
+    L->off = take((size_t)n * 8);
+    L->carry = take((size_t)(L->nblocks + 1) * 8);
+    L->item_row = take((size_t)L->cap * 4);
+    L->partials = take((size_t)L->cap * (size_t)dim * 4);
+    L->weight = take((size_t)num_nodes * 4);
+    L->flag = take((size_t)num_nodes * 4);
+    L->total = off;
+    return true;
+}
+
+__device__ inline void vfma(float4& a, float s, const float4& b) {
+    a.x = __builtin_fmaf(s, b.x, a.x); a.y = __builtin_fmaf(s, b.y, a.y); a.z = __builtin_fmaf(s, b.z, a.z); a.w = __builtin_fmaf(s, b.w, a.w);
+}
+__device__ inline void vfma(float& a, float s, const float& b) { a = __builtin_fmaf(s, b, a); }
+
+// The largest r in [lo, hi] with rowptr[r] <= x (lo if there is none).  At most 32 steps whatever rowptr holds; r stays in [lo, hi].
+__device__ inline int32_t row_of(const int64_t* __restrict__ rowptr, int32_t lo, int32_t hi, int64_t x) {
+    for (int it = 0; it < 32 && lo < hi; ++it) {
+        const int32_t mid = lo + (hi - lo + 1) / 2;
+        if (rowptr[mid] <= x) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// b. found[v] := 1 for every node v that is an entry of its own forward row
+__global__ __launch_bounds__(256) void bwd_self_scan_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col,
+                                                            int64_t num_nodes, int32_t* __restrict__ found) {
+    const int lane = sage_lane();
+    const int64_t wave = (int64_t)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const int64_t nwaves = (int64_t)((gridDim.x * blockDim.x) >> 6);
+    const int64_t total = rowptr[num_nodes];
+    const int32_t last = (int32_t)num_nodes - 1;
+    for (int64_t s0 = wave * kChunk; s0 < total; s0 += nwaves * kChunk) {
+        const int64_t s1 = min(s0 + kChunk, total);
+        const int32_t r_lo = __builtin_amdgcn_readfirstlane(row_of(rowptr, 0, last, s0));
+        const int32_t r_hi = __builtin_amdgcn_readfirstlane(row_of(rowptr, r_lo, last, s1 - 1));
+        for (int64_t e = s0 + lane; e < s1; e += kWave) {
+            const int32_t r = row_of(rowptr, r_lo, r_hi, e);
+            if (col[e] == r) found[r] = 1;
+        }
+    }
+}
+
+// c. flag[v] := extra_v (it held found[v]; not read without self_loop), w[v] := the forward's 1 / count
+__global__ __launch_bounds__(256) void bwd_weight_kernel(const int64_t* __restrict__ rowptr, int64_t num_nodes, int self_loop,
+                                                         int32_t* __restrict__ flag, float* __restrict__ w) {
+    const int64_t v = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (v >= num_nodes) return;
+    const int64_t total = rowptr[num_nodes];
+    int32_t node;
+    int64_t b, e;
+    row_span(rowptr, num_nodes, nullptr, (int)v, total, node, b, e);
+    const int extra = (self_loop && flag[v] == 0) ? 1 : 0;
+    const int64_t c = (e - b) + extra;
+    flag[v] = extra;
+    w[v] = c > 0 ? 1.0f / (float)c : 0.f;
+}
+
+// acc = fma(w[x], grad_out[x], acc) over x = col_t[b..e) in stored order (the forward's sum_edges with a weight: ids AND weights
+// broadcast by readlane, 8 rows in flight).  b, e wave-uniform.  Ids are clamped into [0, last_row].
+template <int VEC>
+__device__ inline void sum_weighted(const int32_t* __restrict__ col_t, int64_t b, int64_t e, const float* __restrict__ w,
+                                    const float* __restrict__ g, int64_t ldg, int last_row, int c0, bool ok,
+                                    typename VecT<VEC>::type& acc) {
+    using V = typename VecT<VEC>::type;
+    const int lane = sage_lane();
+    for (int64_t base = b; base < e; base += kWave) {
+        const int m = (int)min((int64_t)kWave, e - base);
+        const int raw = (lane < m) ? col_t[base + lane] : 0;
+        const int myid = min(max(raw, 0), last_row);     // never read outside grad_out / w
+        const int mywt = (lane < m) ? __float_as_int(w[myid]) : 0;
+        for (int j0 = 0; j0 < m; j0 += 8) {
+            V t[8];
+            float wt[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int j = min(j0 + u, m - 1);
+                const int id = __builtin_amdgcn_readlane(myid, j);
+                wt[u] = __int_as_float(__builtin_amdgcn_readlane(mywt, j));
+                if (ok) t[u] = *reinterpret_cast<const V*>(g + (int64_t)id * ldg + c0);
+                else vfill(t[u], 0.f);
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (j0 + u < m) vfma(acc, wt[u], t[u]);
+        }
+    }
+}
+
+// 4. one wave per item (row, chunk): partials[item] := the chunk's weighted sum
+template <int VEC>
+__global__ __launch_bounds__(256) void bwd_chunk_kernel(const int64_t* __restrict__ rowptr_t, const int32_t* __restrict__ col_t,
+                                                        int64_t num_nodes, const int32_t* __restrict__ nodes, int n,
+                                                        const float* __restrict__ w, const float* __restrict__ g, int64_t ldg, int dim,
+                                                        const int64_t* __restrict__ off, const int64_t* __restrict__ carry, int nb,
+                                                        int64_t cap, const int32_t* __restrict__ item_row, float* __restrict__ partials) {
+    using V = typename VecT<VEC>::type;
+    const int lane = sage_lane();
+    const int64_t wave = (int64_t)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const int64_t nwaves = (int64_t)((gridDim.x * blockDim.x) >> 6);
+    const int64_t items = min(carry[nb], cap);
+    const int64_t total = rowptr_t[num_nodes];
+    const int last_row = (int)num_nodes - 1;
+    for (int64_t i = wave; i < items; i += nwaves) {
+        // as in the forward: an entry counts only if it names a row whose chunk range fits the workspace and holds i
+        const int r = __builtin_amdgcn_readfirstlane(item_row[i]);
+        if (r < 0 || r >= n) continue;
+        int32_t v;
+        int64_t b, e;
+        row_span(rowptr_t, num_nodes, nodes, r, total, v, b, e);
+        b = uniform64(b);
+        e = uniform64(e);
+        const int64_t k = long_chunks(e - b), o = uniform64(off[r]);
+        if (k == 0 || o + k > cap || i < o || i >= o + k) continue;
+        const int64_t cb = b + (i - o) * kChunk;
+        const int64_t ce = min(cb + kChunk, e);
+        for (int cbk = 0; cbk < dim; cbk += kWave * VEC) {
+            const int c0 = cbk + lane * VEC;
+            const bool ok = c0 < dim;
+            V acc;
+            vfill(acc, 0.f);
+            sum_weighted<VEC>(col_t, cb, ce, w, g, ldg, last_row, c0, ok, acc);
+            if (ok) *reinterpret_cast<V*>(partials + i * dim + c0) = acc;
+        }
+    }
+}
+
+// 5. one wave per row of grad_table
+template <int VEC>
+__global__ __launch_bounds__(256) void bwd_row_kernel(const int64_t* __restrict__ rowptr_t, const int32_t* __restrict__ col_t,
+                                                      int64_t num_nodes, const int32_t* __restrict__ nodes, int n,
+                                                      const float* __restrict__ w, const int32_t* __restrict__ flag,
+                                                      const float* __restrict__ g, int64_t ldg, int dim,
+                                                      const int64_t* __restrict__ off, int64_t cap, const float* __restrict__ partials,
+                                                      float* __restrict__ grad_table, int64_t ldgt) {
+    using V = typename VecT<VEC>::type;
+    const int lane = sage_lane();
+    const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const int nwaves = (int)((gridDim.x * blockDim.x) >> 6);
+    const int last_row = (int)num_nodes - 1;
+    const int64_t total = rowptr_t[num_nodes];
+    for (int r = wave; r < n; r += nwaves) {
+        int32_t u;
+        int64_t b, e;
+        row_span(rowptr_t, num_nodes, nodes, r, total, u, b, e);
+        u = __builtin_amdgcn_readfirstlane(u);
+        b = uniform64(b);
+        e = uniform64(e);
+        const int64_t k = long_chunks(e - b);
+        const int64_t o = k > 0 ? uniform64(off[r]) : 0;
+        const bool split = k > 0 && o + k <= cap;        // the chunk pass summed this row's chunks
+        const bool extra = u >= 0 && __builtin_amdgcn_readfirstlane(flag[max(u, 0)]) != 0;
+        const float wu = extra ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(w[u]))) : 0.f;
+        for (int cb = 0; cb < dim; cb += kWave * VEC) {
+            const int c0 = cb + lane * VEC;
+            const bool ok = c0 < dim;
+            V s;
+            vfill(s, 0.f);
+            if (split) {
+                if (ok)
+                    for (int64_t c = 0; c < k; ++c) vadd(s, *reinterpret_cast<const V*>(partials + (o + c) * dim + c0));
+            } else if (k == 0) {
+                sum_weighted<VEC>(col_t, b, e, w, g, ldg, last_row, c0, ok, s);
+            } else {                                      // long row without workspace room: the chunk pass's sums, here
+                for (int64_t c = 0; c < k; ++c) {
+                    V p;
+                    vfill(p, 0.f);
+                    sum_weighted<VEC>(col_t, b + c * kChunk, min(b + (c + 1) * kChunk, e), w, g, ldg, last_row, c0, ok, p);
+                    vadd(s, p);
+                }
+            }
+            if (ok) {
+                if (extra) vfma(s, wu, *reinterpret_cast<const V*>(g + (int64_t)u * ldg + c0));   // the self term, last
+                *reinterpret_cast<V*>(grad_table + (int64_t)r * ldgt + c0) = s;
+            }
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" size_t sage_csr_mean_backward_workspace_bytes(int64_t num_nodes, int32_t n, int64_t max_edges, int32_t dim) {
+    BwdLayout L;
+    return bwd_layout(num_nodes, n, max_edges, dim, &L) ? L.total : 0;
+}
+
+extern "C" int sage_csr_mean_backward(const int64_t* rowptr, const int32_t* col, const int64_t* rowptr_t, const int32_t* col_t,
+                                      int64_t num_nodes, const int32_t* nodes, int32_t n, int64_t max_edges, const float* grad_out,
+                                      int64_t ldg, int32_t dim, int32_t self_loop, float* grad_table, int64_t ldgt, void* workspace,
+                                      size_t workspace_bytes, sage_stream_t stream) {
+    // shapes first, then pointers: a bad shape is reported as such whatever the pointers are
+    SAGE_REQUIRE(num_nodes >= 0 && num_nodes < (1ll << 31), "csr_mean_backward: num_nodes = %lld", (long long)num_nodes);
+    SAGE_REQUIRE(n >= 0 && (nodes || n <= num_nodes), "csr_mean_backward: n = %d rows for %lld nodes without a node list", n,
+                 (long long)num_nodes);
+    SAGE_REQUIRE(max_edges >= 0, "csr_mean_backward: max_edges = %lld", (long long)max_edges);
+    SAGE_REQUIRE(dim >= 1 && ldg >= dim && ldgt >= dim, "csr_mean_backward: dim = %d, ldg = %lld, ldgt = %lld", dim, (long long)ldg,
+                 (long long)ldgt);
+    SAGE_REQUIRE(self_loop == 0 || self_loop == 1, "csr_mean_backward: self_loop = %d", self_loop);
+    SAGE_REQUIRE(rowptr && col && rowptr_t && col_t && grad_out && grad_table, "csr_mean_backward: NULL array");
+    BwdLayout L;
+    SAGE_REQUIRE(bwd_layout(num_nodes, n, max_edges, dim, &L), "csr_mean_backward: n = %d, max_edges = %lld, dim = %d out of range", n,
+                 (long long)max_edges, dim);
+    if (workspace_bytes < L.total || !workspace) {
+        sage_set_error("csr_mean_backward: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
+        return SAGE_ENOSPACE;
+    }
+    SAGE_REQUIRE(sage_aligned(workspace, 256), "csr_mean_backward: workspace not 256-byte aligned");
+    if (n == 0) return SAGE_OK;
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    int64_t* off = (int64_t*)(ws + L.off);
+    int64_t* carry = (int64_t*)(ws + L.carry);
+    int32_t* item_row = (int32_t*)(ws + L.item_row);
+    float* partials = (float*)(ws + L.partials);
+    float* w = (float*)(ws + L.weight);
+    int32_t* flag = (int32_t*)(ws + L.flag);
+    const int nb = (int)L.nblocks;
+
+    // the weights of the forward's rows.  num_nodes >= 1 here: n > 0 rows without a node list need it, and with one and no nodes
+    // every row is empty -- the kernels below then read neither w nor flag
+    if (num_nodes > 0) {
+        if (self_loop) {
+            const int rc = sage_fill_u32(flag, 0u, (size_t)num_nodes, st);
+            if (rc != SAGE_OK) return rc;
+            const int blocks = (int)std::min<int64_t>(std::max<int64_t>((max_edges / kChunk + 4) / 4, 1), kNumCU * 8);
+            hipLaunchKernelGGL(bwd_self_scan_kernel, dim3(blocks), dim3(256), 0, st, rowptr, col, num_nodes, flag);
+            SAGE_CHECK_LAUNCH("bwd_self_scan_kernel");
+        }
+        hipLaunchKernelGGL(bwd_weight_kernel, dim3(sage_cdiv(num_nodes, 256)), dim3(256), 0, st, rowptr, num_nodes, (int)self_loop, flag, w);
+        SAGE_CHECK_LAUNCH("bwd_weight_kernel");
+    }
+
+    hipLaunchKernelGGL(csr_count_kernel, dim3(nb), dim3(kCountThreads), 0, st, rowptr_t, num_nodes, nodes, n, off, carry);
+    SAGE_CHECK_LAUNCH("csr_count_kernel");
+    hipLaunchKernelGGL(csr_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, carry, nb);
+    SAGE_CHECK_LAUNCH("csr_carry_kernel");
+    hipLaunchKernelGGL(csr_expand_kernel, dim3(sage_cdiv(n, 256)), dim3(256), 0, st, rowptr_t, num_nodes, nodes, n, off, carry, L.cap, item_row);
+    SAGE_CHECK_LAUNCH("csr_expand_kernel");
+
+    const bool vec4 = (dim % 4 == 0) && (ldg % 4 == 0) && (ldgt % 4 == 0) && sage_aligned(grad_out, 16) && sage_aligned(grad_table, 16);
+    if (L.cap > 0) {
+        const int blocks = (int)std::min<int64_t>((L.cap + 3) / 4, kNumCU * 8);
+        if (vec4)
+            hipLaunchKernelGGL(bwd_chunk_kernel<4>, dim3(blocks), dim3(256), 0, st, rowptr_t, col_t, num_nodes, nodes, n, w, grad_out, ldg, dim,
+                               off, carry, nb, L.cap, item_row, partials);
+        else
+            hipLaunchKernelGGL(bwd_chunk_kernel<1>, dim3(blocks), dim3(256), 0, st, rowptr_t, col_t, num_nodes, nodes, n, w, grad_out, ldg, dim,
+                               off, carry, nb, L.cap, item_row, partials);
+        SAGE_CHECK_LAUNCH("bwd_chunk_kernel");
+    }
+    const int blocks = std::min(sage_cdiv(n, 4), kNumCU * 8);
+    if (vec4)
+        hipLaunchKernelGGL(bwd_row_kernel<4>, dim3(blocks), dim3(256), 0, st, rowptr_t, col_t, num_nodes, nodes, n, w, flag, grad_out, ldg, dim,
+                           off, L.cap, partials, grad_table, ldgt);
+    else
+        hipLaunchKernelGGL(bwd_row_kernel<1>, dim3(blocks), dim3(256), 0, st, rowptr_t, col_t, num_nodes, nodes, n, w, flag, grad_out, ldg, dim,
+                           off, L.cap, partials, grad_table, ldgt);
+    SAGE_CHECK_LAUNCH("bwd_row_kernel");
+    return SAGE_OK;
+}

@@ -2,7 +2,7 @@
 
 The reference gets its gradients from stock autograd through mm / div / cat /
 relu; here each operator carries its own backward kernel
-(include/sage355.h: sage_linear_act_backward, sage_gather_mean_backward).
+(include/sage355.h: sage_linear_act_backward, sage_gather_mean_backward, sage_csr_mean_backward).
 """
 import torch
 
@@ -30,6 +30,29 @@ class _GatherMean(torch.autograd.Function):
             native.stream_handle())
         native.check(rc, "gather_mean_backward")
         return grad_table, None, None, None, None, None
+
+
+class _CsrMean(torch.autograd.Function):
+    """The whole-graph full-neighbourhood mean (ops.csr_mean over every node) and its adjoint (ops.csr_mean_backward)."""
+
+    @staticmethod
+    def forward(ctx, table, rowptr, col, rowptr_t, col_t, self_loop, any_nonempty):
+        out = ops.csr_mean(rowptr, col, table, self_loop=self_loop, any_nonempty=any_nonempty)
+        ctx.save_for_backward(rowptr, col, rowptr_t, col_t)
+        ctx.self_loop, ctx.table_rows = self_loop, table.shape[0]
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        rowptr, col, rowptr_t, col_t = ctx.saved_tensors
+        n = rowptr.shape[0] - 1
+        grad_out = grad_out.contiguous()
+        if ctx.table_rows == n:
+            grad_table = torch.empty((n, grad_out.shape[1]), dtype=torch.float32, device=grad_out.device)
+        else:                                             # rows at or past num_nodes belong to no node: zero gradient
+            grad_table = torch.zeros((ctx.table_rows, grad_out.shape[1]), dtype=torch.float32, device=grad_out.device)
+        ops.csr_mean_backward(rowptr, col, rowptr_t, col_t, grad_out, self_loop=ctx.self_loop, out=grad_table[:n])
+        return grad_table, None, None, None, None, None, None
 
 
 class _LinearAct(torch.autograd.Function):
@@ -113,6 +136,20 @@ def gather_mean(table, nbr, cnt, any_nonempty=None, slot_rows=None, self_row=Non
     if torch.is_grad_enabled() and table.requires_grad:
         return _GatherMean.apply(table, nbr, cnt, any_nonempty, slot_rows, self_row)
     return ops.gather_mean(table.detach(), nbr, cnt, slot_rows=slot_rows, self_row=self_row, any_nonempty=any_nonempty)
+
+
+def csr_mean(rowptr, col, table, transpose=None, self_loop=False, any_nonempty=None, nodes=None):
+    """ops.csr_mean, differentiable with respect to `table` in its whole-graph form (row r = node r).  transpose: the pair
+    ops.csr_transpose(rowptr, col) gives; built here if absent (a sort of the edges: build it once per graph and pass it).
+    Rows of the table at or past num_nodes get a zero gradient.  With `nodes` and a table that requires grad this raises: a
+    row subset with duplicates would need a scatter through duplicate rows; differentiate the whole graph and index the result.
+    Without grad mode, or with a table that needs no gradient, it is ops.csr_mean unchanged."""
+    if not (torch.is_grad_enabled() and table.requires_grad):
+        return ops.csr_mean(rowptr, col, table.detach(), nodes=nodes, self_loop=self_loop, any_nonempty=any_nonempty)
+    if nodes is not None:
+        raise native.SageError("autograd.csr_mean: the differentiable form is the whole-graph one (nodes=None)")
+    rowptr_t, col_t = ops.csr_transpose(rowptr, col) if transpose is None else transpose
+    return _CsrMean.apply(table, rowptr, col, rowptr_t, col_t, bool(self_loop), any_nonempty)
 
 
 def linear_act(agg, weight, act, self_tab=None, self_index=None):

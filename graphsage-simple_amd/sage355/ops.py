@@ -319,6 +319,83 @@ def csr_mean(rowptr, col, table, nodes=None, self_loop=False, any_nonempty=None,
     return out
 
 
+def csr_transpose(rowptr, col):
+    """(rowptr_t int64 [N + 1], col_t int32 [E]) of a CSR over N = len(rowptr) - 1 nodes: for every entry (v -> u) row u of the
+    transpose holds one entry v, in ascending v (duplicates kept) -- what csr_mean_backward sums over.  Torch ops (a stable sort by
+    destination, bincount, cumsum) on the tensors' own device, CPU or GPU; built once per graph.  An id outside [0, N) raises:
+    the differentiable path needs ids inside the graph (one check here, at build time)."""
+    if not isinstance(rowptr, torch.Tensor) or not isinstance(col, torch.Tensor) or rowptr.dim() != 1 or col.dim() != 1:
+        raise native.SageError("csr_transpose: rowptr and col must be 1-d tensors")
+    n = rowptr.shape[0] - 1
+    if n < 0:
+        raise native.SageError("csr_transpose: rowptr is empty")
+    rp = rowptr.to(torch.int64)
+    e = int(rp[-1]) if n > 0 else 0
+    if e < 0 or e > col.numel() or int(rp[0]) != 0 or (n > 0 and bool((rp[1:] < rp[:-1]).any())):
+        raise native.SageError("csr_transpose: rowptr is not a row pointer array of col")
+    dst = col[:e].to(torch.int64)
+    if e > 0:
+        lo, hi = int(dst.min()), int(dst.max())
+        if lo < 0 or hi >= n:
+            raise native.SageError(f"csr_transpose: id {lo if lo < 0 else hi} outside [0, {n})")
+    src = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=col.device), rp[1:] - rp[:-1])
+    order = torch.sort(dst, stable=True).indices                 # sources are ascending already: stable keeps them so inside a row
+    col_t = src[order].to(torch.int32)
+    rowptr_t = torch.zeros(n + 1, dtype=torch.int64, device=col.device)
+    if n > 0:
+        rowptr_t[1:] = torch.cumsum(torch.bincount(dst, minlength=n), 0)
+    return rowptr_t, col_t
+
+
+def csr_mean_backward_workspace_bytes(num_nodes, n, max_edges, dim):
+    """Bytes of the workspace sage_csr_mean_backward needs (host arithmetic; 0 = shape out of range)."""
+    return int(native.lib().sage_csr_mean_backward_workspace_bytes(int(num_nodes), int(n), int(max_edges), int(dim)))
+
+
+def csr_mean_backward(rowptr, col, rowptr_t, col_t, grad_out, nodes=None, self_loop=False, out=None, max_edges=None, workspace=None):
+    """The adjoint of csr_mean(rowptr, col, table) (every node) with respect to `table`: [n, dim], row r the gradient of table
+    row nodes[r] (row r without `nodes`).  (rowptr_t, col_t) = csr_transpose(rowptr, col).  grad_out [num_nodes, dim], by node id.
+    The result is stored, not accumulated.  max_edges: upper bound on the entries of the selected transposed rows, default
+    len(col_t) (exact for distinct rows; a smaller bound only costs speed).  workspace: a uint8 device tensor to reuse."""
+    _need_gpu()
+    _chk(rowptr, torch.int64, "rowptr", 1)
+    _chk(col, torch.int32, "col", 1)
+    _chk(rowptr_t, torch.int64, "rowptr_t", 1)
+    _chk(col_t, torch.int32, "col_t", 1)
+    grad_out, ldg = _row_major(grad_out, "grad_out")
+    num_nodes = rowptr.shape[0] - 1
+    if num_nodes < 0:
+        raise native.SageError("csr_mean_backward: rowptr is empty")
+    if rowptr_t.shape[0] != rowptr.shape[0] or col_t.numel() != col.numel():
+        raise native.SageError("csr_mean_backward: the transpose does not have the graph's shape")
+    if grad_out.shape[0] < num_nodes:
+        raise native.SageError(f"csr_mean_backward: grad_out has {grad_out.shape[0]} rows for {num_nodes} nodes")
+    if nodes is not None:
+        _chk(nodes, torch.int32, "nodes", 1)
+    n = num_nodes if nodes is None else nodes.shape[0]
+    dim = grad_out.shape[1]
+    if out is None:
+        out = torch.empty((n, dim), dtype=torch.float32, device=grad_out.device)
+    out, ldgt = _row_major(out, "out")
+    if out.shape[0] < n or out.shape[1] != dim:
+        raise native.SageError(f"csr_mean_backward: out is {tuple(out.shape)}, expected ({n}, {dim})")
+    if n == 0:
+        return out
+    if col.numel() == 0:                                  # an empty tensor may have no storage address: the kernels read none of it
+        col = col_t = torch.zeros(1, dtype=torch.int32, device=grad_out.device)
+    max_edges = col_t.numel() if max_edges is None else int(max_edges)
+    need = csr_mean_backward_workspace_bytes(num_nodes, n, max_edges, dim)
+    if need == 0:
+        raise native.SageError(f"csr_mean_backward: n = {n}, max_edges = {max_edges}, dim = {dim} out of range")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=grad_out.device)
+    rc = native.lib().sage_csr_mean_backward(native.ptr(rowptr), native.ptr(col), native.ptr(rowptr_t), native.ptr(col_t), num_nodes,
+                                             native.ptr(nodes), n, max_edges, native.ptr(grad_out), ldg, dim, 1 if self_loop else 0,
+                                             native.ptr(out), ldgt, native.ptr(workspace), workspace.numel(), native.stream_handle())
+    native.check(rc, "csr_mean_backward")
+    return out
+
+
 def xent_head_supported(dim, num_classes):
     return bool(native.lib().sage_xent_head_supported(int(dim), int(num_classes)))
 

@@ -184,7 +184,50 @@ int sage_csr_mean(const int64_t* rowptr, const int32_t* col, int64_t num_nodes,
                   float* out, int64_t ldo, void* workspace, size_t workspace_bytes, sage_stream_t stream);
 
 /* ---------------------------------------------------------------------------
- * sage_linear_act -- encoders.py:49-62 without materialising the concat:
+ * sage_csr_mean_backward (additive, ABI 9) -- the adjoint of
+ * sage_csr_mean(nodes = NULL, n = num_nodes) with respect to `table`.  With the
+ * forward's own definitions
+ *     extra_v = self_loop && v is not an entry of its own row   (set union)
+ *     c_v     = deg(v) + extra_v         (entries counted with multiplicity)
+ *     w_v     = c_v > 0 ? 1.0f / (float)c_v : 0         (the forward's float)
+ * it stores
+ *     grad_table[r, :] = sum over the entries e of row u of the TRANSPOSED CSR,
+ *                        in stored order, of w_x * grad_out[x, :], x = col_t[e]
+ *                        + extra_u * w_u * grad_out[u, :]          (added last)
+ *     u = nodes ? nodes[r] : r
+ * grad_out is [num_nodes, dim], indexed by node id, leading dimension ldg.
+ * grad_table is [n, dim], leading dimension ldgt; it is STORED, not
+ * accumulated: the caller zeroes nothing, a row with no terms is exact zeros.
+ * Not written: columns [dim, ldgt) and rows at or past n.  Not read: rows of
+ * grad_out that belong to no term (empty forward rows without a self term;
+ * they may hold NaN).
+ * The caller supplies the transpose (rowptr_t, col_t), built once per graph:
+ * for every entry (v -> u) of the forward CSR row u of the transpose holds one
+ * entry v.  The order inside a row only fixes the bits.  A wrong transpose
+ * gives wrong numbers, never an access out of range: ids from col_t and nodes
+ * and all row pointers are clamped as in the forward.  rowptr / col (the
+ * forward's CSR) give c_v and extra_v.
+ * max_edges bounds the entries of the selected transposed rows and sizes the
+ * workspace; a bound that is too small costs speed only.  Every term is one
+ * fma; rows longer than SAGE_CSR_MEAN_CHUNK entries are cut into chunks summed
+ * by separate waves and added in chunk order.  No float atomics: a row's bits
+ * depend only on its transposed entries, the weights, grad_out and self_loop,
+ * so backward(nodes = S) == backward()[S] bit for bit.
+ * Any dim >= 1, ldg >= dim, ldgt >= dim; 16-byte accesses when dim, ldg, ldgt
+ * are multiples of 4 and both arrays are 16-byte aligned.  n == 0 returns
+ * SAGE_OK without a launch.  Workspace 256-byte aligned; the query returns 0
+ * for a shape out of range.
+ * ------------------------------------------------------------------------- */
+size_t sage_csr_mean_backward_workspace_bytes(int64_t num_nodes, int32_t n, int64_t max_edges, int32_t dim);
+int sage_csr_mean_backward(const int64_t* rowptr, const int32_t* col,
+                           const int64_t* rowptr_t, const int32_t* col_t, int64_t num_nodes,
+                           const int32_t* nodes /* nullable: row r is node r */, int32_t n, int64_t max_edges,
+                           const float* grad_out, int64_t ldg, int32_t dim, int32_t self_loop,
+                           float* grad_table, int64_t ldgt,
+                           void* workspace, size_t workspace_bytes, sage_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * sage_linear_act --encoders.py:49-62 without materialising the concat:
  *     out[r, :] = act( W[:, 0:ds] . self(r) + W[:, ds:ds+dim] . agg[r, :] )
  * self(r) = self_tab[self_index ? self_index[r] : r, 0:dim]; ds = dim when
  * self_tab != NULL (concat encoder, gcn=False) else 0 (gcn=True).
