@@ -54,7 +54,8 @@ const sage_tunables_t& sage_tunables() {
         x.outer_threads = so >= 1024 ? 1024 : so >= 512 ? 512 : 256;
         x.tile16_grid = env_int("SAGE_T16_GRID", 2 * kNumCU, 64, 1024);
         x.sample_fused = env_int("SAGE_SAMPLE_FUSED", 0, 0, 1);
-        x.tile16_waves = env_int("SAGE_T16_WAVES", 8, 8, 16) >= 16 ? 16 : 8;
+        { const int tw = env_int("SAGE_T16_WAVES", 0, 0, 16); x.tile16_waves = tw == 0 ? 0 : tw >= 16 ? 16 : 8; }
+        { const int ti = env_int("SAGE_T16_INFLIGHT", 0, 0, 13); x.tile16_inflight = ti == 0 ? 0 : ti >= 13 ? 13 : 7; }
         x.layer1_fused = env_int("SAGE_LAYER1_FUSED", SAGE_LAYER1_FUSED_DEFAULT, 0, 1);
         x.layer1_phase_per_cu = env_int("SAGE_L1P_PER_CU", 3, 1, 3);
         return x;

@@ -282,7 +282,9 @@ int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes
     // 4. layer 2 on the seeds; its last block zeroes the counters and advances the batch queue
     if (stages & SAGE_STAGE_LAYER2)
         if (int rc = run_stage(SAGE_STAGE_LAYER2, 8, nullptr, [&](sage_launch_events_t* e) {
-                if (fuse2) return sage_launch_layer_fused(table2, lists2, self2, contract2, sfused ? &resolve2 : nullptr, fin, st, e);
+                // in a pipeline this launch runs beside the NEXT batch's layer 1: the block shape follows that kernel's form (sage_fused.hip)
+                if (fuse2) return sage_launch_layer_fused(table2, lists2, self2, contract2, sfused ? &resolve2 : nullptr, fin, st, e,
+                                                          phase1 ? SAGE_BESIDE_ONE_WAVE_LAYER1 : SAGE_BESIDE_ANYTHING);
                 if (int rc = sage_launch_gather_mean(table2, lists2, agg2, m->h1, SAGE_ACT_NONE, st)) return rc;
                 return sage_launch_linear_act(means2, lists2, self2, contract2, fin, st);
             }))

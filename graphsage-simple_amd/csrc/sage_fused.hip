@@ -438,21 +438,43 @@ __global__ __launch_bounds__(WAVES * 64, CONCAT ? SAGE_T16_CONCAT_MIN_WAVES : 4)
     sage_finish_block(a.fin, (int)gridDim.x, fin_regs);
 }
 
-template <int KP, bool CONCAT>
-int launch_tile16(const FusedArgs& a, hipStream_t st, sage_launch_events_t* ev) {
-    // neighbour lists up to NPI x INFLIGHT entries are fetched in one trip: 14 (KP = 128) / 28 (KP = 64).  13 in flight (the
-    // whole 25-entry list of config 3 in ONE trip, 110 VGPRs) is no faster alone and 1.4 us per forward slower with a second
-    // batch in flight than 7 (two trips, 86 VGPRs): the smaller block shares a CU more easily (same-box A/B, 3 x 3 runs)
+// Row loads a lane group keeps in flight per trip.  7 everywhere: lists up to NPI x 7 entries (14 at KP = 128, 28 at KP = 64) are one trip,
+// config 3's 25-entry list two, at 86 VGPRs.  13 (the whole 25-entry list in ONE trip, 124 VGPRs, no scratch) exists for the gcn form with 16 waves.
 #ifndef SAGE_T16_INFLIGHT
 #define SAGE_T16_INFLIGHT 7
 #endif
 #ifndef SAGE_T16_INFLIGHT_CONCAT
 #define SAGE_T16_INFLIGHT_CONCAT 7
 #endif
+constexpr int kTile16InflightOneTrip = 13;
+
+// Which block the small layer gets is a question of what it runs beside (`waves`, `inflight`: sage_launch_layer_fused picks them from the
+// caller's sage_layer_company_t, SAGE_T16_WAVES / SAGE_T16_INFLIGHT override).  Every form sums in the same order and returns the same bits.
+//  * Beside persistent kernels that share their CUs (the column-sliced gather and the contraction of the split layer 1; the concat
+//    encoder): 8 waves, 7 in flight.  The 512-thread block finds room on a CU other batches' kernels already share; a 1024-thread block
+//    waited for whole gathers to drain (1.5 us per forward), and 13 in flight was no faster alone and 1.4 us per forward slower there
+//    (rounds 2-3, same-box A/B).  Re-measured for the concat encoder at config 3, three interleaved repetitions: 100.5-102.7 us per
+//    forward with 8 waves against 105.5-108.2 with 16.
+//  * Beside the one-launch phase-sliced layer 1 (gcn encoder, config 3, same box, three interleaved repetitions, us per forward):
+//    8 waves x 7 in flight 66.5-67.0 (one run 75.7), 16 x 7 64.0-65.6, 8 x 13 65.9-66.8, 16 x 13 62.8-62.9; grid 128 / 256 / 1024
+//    instead of 512 blocks: 67.5-68.7 (16 waves), 66.2-71.2 and 66.5-67.5 (8 waves).  That layer 1 is ONE wave of 736 blocks, three per CU,
+//    holding 480 of a SIMD's 512 VGPRs: a 512-thread block (2 x 88 VGPRs per SIMD) is placed wherever one of its blocks is missing and
+//    keeps a block of the next batch's launch off that CU, a 1024-thread block (4 x 128) needs two of the three gone.  That is the
+//    reasoning the forms were picked for measurement by; the trace of the shipped form does not isolate it, the
+//    A/B is what decides: 62.6-63.6 against 65.4-66.6 for the parent, config 4 87.4-89.5 against 92.7-95.1 (profiles/r09_ab.json).
+template <int KP, bool CONCAT>
+int launch_tile16(const FusedArgs& a, int waves, int inflight, hipStream_t st, sage_launch_events_t* ev) {
     constexpr int INFLIGHT = CONCAT ? SAGE_T16_INFLIGHT_CONCAT : SAGE_T16_INFLIGHT;
     const int tiles = sage_cdiv(a.n, 16);
     const int grid = min(tiles, sage_tunables().tile16_grid);
-    if (sage_tunables().tile16_waves == 8)
+    if constexpr (!CONCAT) {
+        if (waves == 16 && inflight == kTile16InflightOneTrip) {
+            sage_launch(layer_tile16_kernel<KP, false, kTile16InflightOneTrip, 16>, dim3(grid), dim3(1024), 0, st, ev, a);
+            SAGE_CHECK_LAUNCH("layer_tile16_kernel");
+            return SAGE_OK;
+        }
+    }
+    if (waves == 8)
         sage_launch(layer_tile16_kernel<KP, CONCAT, INFLIGHT, 8>, dim3(grid), dim3(512), 0, st, ev, a);
     else
         sage_launch(layer_tile16_kernel<KP, CONCAT, INFLIGHT, 16>, dim3(grid), dim3(1024), 0, st, ev, a);
@@ -491,7 +513,7 @@ int launch(const FusedArgs& a, hipStream_t st, sage_launch_events_t* ev) {
 // bound instead: 16 gathering waves per 32-row tile, and the W slice preloaded into VGPRs BEFORE
 // the gather so the MFMA loop never waits on L2 (a streamed W cost ~1 us per k-step there).
 template <int KP, bool CONCAT>
-int launch_by_rows(const FusedArgs& a, hipStream_t st, sage_launch_events_t* ev) {
+int launch_by_rows(const FusedArgs& a, int tile16_waves, int tile16_inflight, hipStream_t st, sage_launch_events_t* ev) {
     constexpr bool kWide = CONCAT && KP == 256;           // two 256-wide chunks: 32-row tiles to fit LDS
     if (a.n >= 8192) {
         if constexpr (kWide) return launch<KP, 32, 4, true, CONCAT>(a, st, ev);
@@ -505,7 +527,7 @@ int launch_by_rows(const FusedArgs& a, hipStream_t st, sage_launch_events_t* ev)
     if constexpr (KP <= 128 && !CONCAT) return launch<KP, 32, 16, true, CONCAT, 6>(a, st, ev);    // 6 in flight: inside the 128-VGPR budget of a 16-wave block
     else return launch<KP, 32, 8, true, CONCAT>(a, st, ev);
 #else
-    if constexpr (KP <= 128) return launch_tile16<KP, CONCAT>(a, st, ev);
+    if constexpr (KP <= 128) return launch_tile16<KP, CONCAT>(a, tile16_waves, tile16_inflight, st, ev);
     else return launch<KP, 32, 8, true, CONCAT>(a, st, ev);
 #endif
 }
@@ -518,7 +540,8 @@ bool sage_layer_fused_supported(int32_t dim, int32_t out_dim, int32_t concat) {
 }
 
 int sage_launch_layer_fused(const sage_rows_t& src, const sage_lists_t& l, const sage_self_t& self, const sage_contract_t& c,
-                            const sage_slot_resolve_t* resolve, sage_finish_t fin, hipStream_t st, sage_launch_events_t* ev) {
+                            const sage_slot_resolve_t* resolve, sage_finish_t fin, hipStream_t st, sage_launch_events_t* ev,
+                            sage_layer_company_t company) {
     const int32_t dim = src.dim, concat = self.self_tab != nullptr;
     SAGE_REQUIRE(!concat || (self.self_tab == src.table && self.ld_self == src.ld && self.self_rows == src.table_rows),
                  "layer_forward: the fused layer takes a row's own features from the source table");
@@ -533,14 +556,19 @@ int sage_launch_layer_fused(const sage_rows_t& src, const sage_lists_t& l, const
                       self.self_index, src.table, src.ld, (int)src.table_rows, c.weight, c.ldw, c.out_dim, c.act, c.out, c.ldo, l.n_off, fin,
                       resolve ? resolve->wipe_keys : nullptr, resolve ? resolve->rows_out : nullptr, resolve ? resolve->self_rows_out : nullptr};
     const int kp = dim <= 64 ? 64 : dim <= 128 ? 128 : 256;
+    // the tile16 form's block and trip: SAGE_T16_WAVES / SAGE_T16_INFLIGHT when the environment names them, otherwise by what the launch
+    // runs beside (launch_tile16)
+    const bool one_wave = company == SAGE_BESIDE_ONE_WAVE_LAYER1;
+    const int tw = sage_tunables().tile16_waves ? sage_tunables().tile16_waves : one_wave ? 16 : 8;
+    const int ti = sage_tunables().tile16_inflight ? sage_tunables().tile16_inflight : one_wave ? kTile16InflightOneTrip : 7;
     if (!concat) {
-        if (kp == 64) return launch_by_rows<64, false>(a, st, ev);
-        if (kp == 128) return launch_by_rows<128, false>(a, st, ev);
-        return launch_by_rows<256, false>(a, st, ev);
+        if (kp == 64) return launch_by_rows<64, false>(a, tw, ti, st, ev);
+        if (kp == 128) return launch_by_rows<128, false>(a, tw, ti, st, ev);
+        return launch_by_rows<256, false>(a, tw, ti, st, ev);
     }
-    if (kp == 64) return launch_by_rows<64, true>(a, st, ev);
-    if (kp == 128) return launch_by_rows<128, true>(a, st, ev);
-    return launch_by_rows<256, true>(a, st, ev);
+    if (kp == 64) return launch_by_rows<64, true>(a, tw, ti, st, ev);
+    if (kp == 128) return launch_by_rows<128, true>(a, tw, ti, st, ev);
+    return launch_by_rows<256, true>(a, tw, ti, st, ev);
 }
 
 extern "C" int sage_layer_forward_supported(int32_t dim, int32_t out_dim, int32_t concat) {

@@ -124,8 +124,15 @@ int sage_launch_linear_act(const sage_rows_t& agg, const sage_lists_t& rows, con
                            sage_finish_t fin, hipStream_t st);
 
 // Fused layer (sage_fused.hip).  Returns SAGE_EUNSUPPORTED when no instantiation fits.  `self` must name the source table (SAGE_EINVAL).
+// `company`: what other batches run on the chip while this launch does, as far as the caller knows -- it picks the block shape of the
+// small-layer (tile16) form, never the arithmetic: every shape returns the same bits.
+enum sage_layer_company_t {
+    SAGE_BESIDE_ANYTHING = 0,             // unknown, or persistent kernels that share their CUs (column-sliced gather, contraction): 512-thread blocks
+    SAGE_BESIDE_ONE_WAVE_LAYER1 = 1,      // the phase-sliced layer 1 of the next batch, one wave of blocks that fills every CU: 1024-thread blocks
+};
 int sage_launch_layer_fused(const sage_rows_t& src, const sage_lists_t& l, const sage_self_t& self, const sage_contract_t& c,
-                            const sage_slot_resolve_t* resolve, sage_finish_t fin, hipStream_t st, sage_launch_events_t* ev = nullptr);
+                            const sage_slot_resolve_t* resolve, sage_finish_t fin, hipStream_t st, sage_launch_events_t* ev = nullptr,
+                            sage_layer_company_t company = SAGE_BESIDE_ANYTHING);
 bool sage_layer_fused_supported(int32_t dim, int32_t out_dim, int32_t concat);
 int sage_launch_layer_dense(const sage_rows_t& agg, const sage_lists_t& rows, const sage_self_t& self, const sage_contract_t& c,
                             sage_finish_t fin, hipStream_t st, sage_launch_events_t* ev = nullptr);
@@ -180,7 +187,11 @@ struct sage_tunables_t {
     int sample_fused;             // SAGE_SAMPLE_FUSED    1: both hops in one launch when layer 2 is a one-launch layer; 0 (default): two launches
                                   //                      (measured: 24.3 us fused vs 10.3 + 11.4: the inner hop of a block's own winners is
                                   //                      three dependent rounds on 128-256 blocks instead of one round on 1500; pipeline 66.8 vs 66.2 us)
-    int tile16_waves;             // SAGE_T16_WAVES       layer-2 tile16 kernel: 16 (1024-thread blocks) or 8 (512-thread blocks, default: 1.5 us per forward in the pipeline)
+    int tile16_waves;             // SAGE_T16_WAVES       layer-2 tile16 kernel: 16 (1024-thread blocks) or 8 (512-thread blocks); 0 (default, unset) = by the
+                                  //                      launch's company, sage_layer_company_t: 16 beside the one-launch layer 1, 8 otherwise
+    int tile16_inflight;          // SAGE_T16_INFLIGHT    layer-2 tile16 kernel, gcn form with 16 waves: 7 or 13 row loads of a lane group in flight per trip
+                                  //                      (13: the 25-entry list of config 3 in ONE trip); 0 (default, unset) = by the launch's company:
+                                  //                      13 beside the one-launch layer 1, 7 otherwise.  Every other form has 7
     int layer1_fused;             // SAGE_LAYER1_FUSED    1: layer 1 as ONE phase-sliced launch where its conditions hold and nobody needs the means
                                   //                      (sage_layer1_phase.hip); 0: always gather + contraction.  Default: see sage_api.hip
     int layer1_phase_per_cu;      // SAGE_L1P_PER_CU      phase-sliced layer 1: persistent 256-thread blocks per CU (1..3), default 3
