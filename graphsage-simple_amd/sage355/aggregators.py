@@ -14,6 +14,9 @@ reference (aggregators.py)                      here
 60-61  mask.sum / mask.div                      \\
 62-65  features(unique ids)                      > sage_gather_mean (HIP): one wave
 74     mask.mm(embed_matrix)                    /  per row, no mask, no matmul
+68-71  1hot / node_degree: the feature rows     same lookup: index = position of the
+       are one-hots that only INDEX the         first 1 of each row, rows of the
+       trainable self.embed                     trainable self.embed are what is averaged
 
 ``forward`` keeps the reference's exact semantics, including its use of
 Python's global ``random`` stream, which makes it the strict drop-in path: for
@@ -30,6 +33,9 @@ import torch.nn as nn
 from . import autograd, native
 
 
+EMBED_INITIALIZERS = ("1hot", "node_degree")     # aggregators.py:30, 68: the feature rows index a trainable embedding
+
+
 class MeanAggregator(nn.Module):
     """Aggregates a node's embeddings using the mean of its (sampled) neighbours' embeddings."""
 
@@ -44,18 +50,16 @@ class MeanAggregator(nn.Module):
         self.features = features
         self.cuda = cuda          # noqa: shadows nn.Module.cuda exactly as aggregators.py:28 does
         self.gcn = gcn
-        if initializer in ["1hot", "node_degree"]:
-            # aggregators.py:30-31 -- parameter kept for state_dict compatibility; the detour
-            # itself (aggregators.py:68-71) is out of scope
-            self.embed = nn.Embedding(num_nodes, feature_dim)
+        if initializer in EMBED_INITIALIZERS:
+            self.embed = nn.Embedding(num_nodes, feature_dim)      # aggregators.py:30-31: trainable, N(0, 1)
 
     def forward(self, nodes, to_neighs, num_sample=10, initializer="None"):
         """nodes      -- list of nodes in a batch
         to_neighs  -- list of sets, the neighbours of each node
         num_sample -- neighbours to sample; None = use to_neighs as given
+        initializer -- "1hot" / "node_degree": the rows features() returns are one-hots that index self.embed, and the
+                      mean is taken over those embedding rows (aggregators.py:68-71)
         -> FloatTensor [len(nodes), D]"""
-        if initializer in ["1hot", "node_degree"]:
-            raise NotImplementedError("the 1hot/node_degree embedding detour (aggregators.py:68-71) is out of scope")
         if num_sample is not None:
             _sample = random.sample   # the reference's stream (aggregators.py:43)
             samp_neighs = [set(_sample(tuple(to_neigh), num_sample)) if len(to_neigh) >= num_sample else to_neigh
@@ -64,9 +68,27 @@ class MeanAggregator(nn.Module):
             samp_neighs = to_neighs
         if self.gcn:
             samp_neighs = [set(s) | {int(nodes[i])} for i, s in enumerate(samp_neighs)]
-        return self.aggregate(samp_neighs)
+        return self.aggregate(samp_neighs, initializer)
 
-    def aggregate(self, samp_neighs):
+    def _embed_lookup(self, embed_matrix):
+        """aggregators.py:68-71: each feature row's index is the position of its first element equal to 1; the rows of the trainable
+        self.embed at those indices take the feature rows' place.  The reference raises IndexError for a row without a 1."""
+        if not hasattr(self, "embed"):
+            raise native.SageError("this MeanAggregator was built without the 1hot / node_degree initializer: it has no `embed`")
+        if embed_matrix.dim() != 2:
+            raise native.SageError(f"features returned {tuple(embed_matrix.shape)}, expected one one-hot row per id")
+        is_one = embed_matrix.detach() == 1
+        if is_one.shape[0] == 0:
+            first = torch.zeros(0, dtype=torch.int64)
+        elif not bool(is_one.any(1).all()):
+            raise native.SageError("1hot / node_degree: a feature row holds no element equal to 1")
+        else:
+            first = is_one.to(torch.int8).argmax(1)           # of equal maxima argmax returns the first: np.where(a == 1)[0][0]
+        if first.numel() and int(first.max()) >= self.embed.num_embeddings:
+            raise native.SageError(f"1hot / node_degree: index {int(first.max())} outside the embedding's {self.embed.num_embeddings} rows")
+        return self.embed(first.to(self.embed.weight.device))
+
+    def aggregate(self, samp_neighs, initializer="None"):
         """Mean over explicit neighbour sets (aggregators.py:52-74)."""
         n = len(samp_neighs)
         cnt = np.fromiter((len(s) for s in samp_neighs), dtype=np.int64, count=n)
@@ -79,6 +101,8 @@ class MeanAggregator(nn.Module):
         order = np.argsort(unique_nodes, kind="stable")
         inverse = order[np.searchsorted(unique_nodes[order], flat)] if flat.size else np.zeros(0, dtype=np.int64)
         embed_matrix = self.features(self._ids_for_features(unique_nodes))
+        if initializer in EMBED_INITIALIZERS:
+            embed_matrix = self._embed_lookup(embed_matrix)
         dev = torch.device("cuda")
         embed_dev = embed_matrix.to(dev, torch.float32)
         if embed_dev.dim() != 2 or embed_dev.shape[0] != unique_nodes.shape[0]:

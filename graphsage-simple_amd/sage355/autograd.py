@@ -2,7 +2,7 @@
 
 The reference gets its gradients from stock autograd through mm / div / cat /
 relu; here each operator carries its own backward kernel
-(include/sage355.h: sage_linear_act_backward, sage_gather_mean_backward, sage_csr_mean_backward).
+(include/sage355.h: sage_linear_act_backward, sage_gather_mean_backward, sage_csr_mean_backward, sage_csr_sum).
 """
 import torch
 
@@ -53,6 +53,20 @@ class _CsrMean(torch.autograd.Function):
             grad_table = torch.zeros((ctx.table_rows, grad_out.shape[1]), dtype=torch.float32, device=grad_out.device)
         ops.csr_mean_backward(rowptr, col, rowptr_t, col_t, grad_out, self_loop=ctx.self_loop, out=grad_table[:n])
         return grad_table, None, None, None, None, None, None
+
+
+class _EmbedRows(torch.autograd.Function):
+    """weight[index] and its adjoint: row k of the gradient is the sum of the rows that read it (ops.csr_sum over the grouping)."""
+
+    @staticmethod
+    def forward(ctx, weight, index, rowptr_g, col_g):
+        ctx.save_for_backward(rowptr_g, col_g)
+        return weight.index_select(0, index)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        rowptr_g, col_g = ctx.saved_tensors
+        return ops.csr_sum(rowptr_g, col_g, grad_out.contiguous()), None, None, None
 
 
 class _LinearAct(torch.autograd.Function):
@@ -150,6 +164,22 @@ def csr_mean(rowptr, col, table, transpose=None, self_loop=False, any_nonempty=N
         raise native.SageError("autograd.csr_mean: the differentiable form is the whole-graph one (nodes=None)")
     rowptr_t, col_t = ops.csr_transpose(rowptr, col) if transpose is None else transpose
     return _CsrMean.apply(table, rowptr, col, rowptr_t, col_t, bool(self_loop), any_nonempty)
+
+
+def embed_rows(weight, index, groups=None):
+    """weight[index] -> [len(index), dim] (the lookup of aggregators.py:70 for a whole graph), differentiable with respect to
+    `weight` [K, dim] on the device: the backward is ops.csr_sum over groups = ops.group_rows(index, K) -- no float atomics, the
+    same bits every run.  groups is built here if absent (a sort of the index: build it once per graph and pass it).  index:
+    int32 / int64 [N], values in [0, K).  Without grad mode, or with a weight that needs no gradient, it is the plain index_select."""
+    idx = index.long()
+    if not (torch.is_grad_enabled() and weight.requires_grad):
+        return weight.detach().index_select(0, idx)
+    if not weight.is_cuda or weight.dtype != torch.float32 or weight.dim() != 2:
+        raise native.SageError("autograd.embed_rows: weight must be a 2-d fp32 device tensor")
+    rowptr_g, col_g = ops.group_rows(index, weight.shape[0]) if groups is None else groups
+    if rowptr_g.shape[0] != weight.shape[0] + 1 or col_g.shape[0] != index.shape[0]:
+        raise native.SageError("autograd.embed_rows: groups do not have the shape of (weight, index)")
+    return _EmbedRows.apply(weight, idx, rowptr_g, col_g)
 
 
 def linear_act(agg, weight, act, self_tab=None, self_index=None):

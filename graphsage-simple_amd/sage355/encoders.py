@@ -63,7 +63,7 @@ import torch.nn as nn
 from torch.nn import init
 
 from . import autograd, native, ops, twohop_ops
-from .aggregators import MeanAggregator
+from .aggregators import EMBED_INITIALIZERS, MeanAggregator
 from .engine import TwoHopEngine
 from .graph import csr_from_adj_lists
 
@@ -310,6 +310,11 @@ class Encoder(nn.Module):
                 and self.num_sample is not None and base.num_sample is not None
                 and 1 <= self.num_sample <= max_fanout and 1 <= base.num_sample <= max_fanout)
 
+    def _embed_detour(self):
+        """This Encoder or its base model runs the 1hot / node_degree lookup (aggregators.py:68-71): only the aggregator's own
+        forward expresses it -- the table-backed routes would average the one-hot rows themselves."""
+        return any(isinstance(enc.initializer, str) and enc.initializer in EMBED_INITIALIZERS for enc in self._pair())
+
     def _can_fuse_two_hop(self):
         return self._is_two_hop_stack(native.MAX_FANOUT)
 
@@ -333,7 +338,9 @@ class Encoder(nn.Module):
         # frozen table.  A TRAINABLE table (nn.Embedding's default) under grad mode takes the per-operator path below, whose
         # autograd.gather_mean / linear_act do reach the table, as the reference's autograd does.
         table_trains = grad and self._can_fuse_two_hop() and self.base_model.features.weight.requires_grad
-        if self._can_fuse_two_hop() and not table_trains:
+        if self._embed_detour():
+            out = self._forward_generic(nodes)                # the strict path: Python's random.sample, the reference's stream
+        elif self._can_fuse_two_hop() and not table_trains:
             out = self._forward_two_hop(nodes, training)
         elif self._can_two_hop_ops():
             out = self._forward_two_hop_ops(nodes)

@@ -7,6 +7,12 @@ sage_csr_mean and sage_csr_mean_backward add in CSR order, sage_linear_act_backw
 the head adds its 64-row ranges in range order).  The feature table is frozen (model.py:214-215), so the layer-1 mean is a
 constant of the graph and is computed once; a step is one csr_mean at width h1, its backward at width h1, two contractions
 and their backward kernels.  Single process: data-parallel whole-graph training is not provided.
+
+Featureless graphs (the reference's `--initializer 1hot | node_degree`, aggregators.py:30-31, 68-71): layer 1 reads rows of a
+TRAINABLE embedding instead of the table, X = embed[index] with index[v] = v (1hot) or the degree of v (node_degree).  The
+layer-1 mean is then part of every step, its backward is sage_csr_mean_backward at width embed_dim on the inner graph, and the
+embedding's gradient is the sum of the rows of all nodes that share an embedding row: sage_csr_sum over the grouping of the
+index (ops.group_rows), dense and in a fixed order -- still no float atomics, still the same bits every run.
 """
 import time
 
@@ -15,7 +21,7 @@ import torch
 from torch.nn import init
 
 from . import dist, native, ops
-from .native import ACT_RELU, SageError
+from .native import ACT_RELU, ACT_SIGMOID, SageError
 from .train import _sum_over_batch
 
 
@@ -28,30 +34,52 @@ class FullGraphTrainer:
     over all N rows, and a NaN row -- though its own gradient is zero -- would poison every one of them (0 * NaN).  forward() is
     therefore bit-identical to embed_all_nodes(..., nan_empty=False).
 
-    head: "native" -- one sage_xent_head call; "torch" -- the same expressions as stock torch ops (train.EngineTrainer)."""
+    head: "native" -- one sage_xent_head call; "torch" -- the same expressions as stock torch ops (train.EngineTrainer).
+
+    Trainable embedding: embed_index int32 [N] on the device with values in [0, embed_rows), and table=None.  Layer 1 reads
+    X = embed[embed_index] ([N, embed_dim]); self.embed [embed_rows, embed_dim] is drawn N(0, 1) as nn.Embedding's weight is
+    (aggregators.py:31), AFTER w1, w2, w_cls -- one torch seed still gives those three the start the frozen-table trainer gives them --
+    is broadcast with them, is the fourth of parameters() and of grads()'s gradients, and is updated by step().  act1: layer 1's
+    activation, ACT_RELU or ACT_SIGMOID (encoders.py:58 applies the sigmoid for node_degree).  The concat encoder's own row is X[v];
+    the reference's concat form feeds the raw one-hot feature row there instead (encoders.py:51-54), which would need a weight as
+    wide as the one-hot: that form is not provided.  forward() is bit-identical to
+    embed_all_nodes(table=embed[embed_index], act1=act1, nan_empty=False).  When embed_index is arange(N) with embed_rows == N, X is
+    the embedding itself: no copy, and its gradient needs no csr_sum."""
 
     def __init__(self, rowptr, col, table, num_classes, hidden1=50, hidden2=128, gcn=True, lr=0.7, agg_self_loop=False, head="native",
-                 rowptr_outer=None, col_outer=None):
+                 rowptr_outer=None, col_outer=None, embed_index=None, embed_rows=None, embed_dim=None, act1=ACT_RELU):
         if head not in ("torch", "native"):
             raise SageError(f"FullGraphTrainer: head = {head!r}, expected 'torch' or 'native'")
+        if act1 not in (ACT_RELU, ACT_SIGMOID):
+            raise SageError(f"FullGraphTrainer: act1 = {act1!r}, expected ACT_RELU or ACT_SIGMOID")
+        if embed_index is not None and table is not None:
+            raise SageError("FullGraphTrainer: table and embed_index are alternatives: layer 1 reads one of them")
         ops._need_gpu()
         if head == "native" and not ops.xent_head_supported(hidden2, num_classes):
             raise SageError(f"FullGraphTrainer: head='native' has no kernel for hidden2 = {hidden2}, num_classes = {num_classes}")
         ops._chk(rowptr, torch.int64, "rowptr", 1)
         ops._chk(col, torch.int32, "col", 1)
-        table, _ = ops._row_major(table, "table")
+        if embed_index is None:
+            table, _ = ops._row_major(table, "table")
         self.rowptr, self.col = rowptr, col
         self.rowptr2 = rowptr if rowptr_outer is None else ops._chk(rowptr_outer, torch.int64, "rowptr_outer", 1)
         self.col2 = col if col_outer is None else ops._chk(col_outer, torch.int32, "col_outer", 1)
         if self.rowptr2.shape[0] != rowptr.shape[0]:
             raise SageError("inner and outer CSR must cover the same node ids")
         self.n = rowptr.shape[0] - 1
-        if self.n < 1 or table.shape[0] < self.n:
-            raise SageError(f"FullGraphTrainer: table has {table.shape[0]} rows for {self.n} nodes")
-        self.table = table
-        self.head, self.lr, self.concat, self.self_loop = head, float(lr), not gcn, bool(agg_self_loop)
-        dev = table.device
-        d0 = table.shape[1]
+        if embed_index is None:
+            if self.n < 1 or table.shape[0] < self.n:
+                raise SageError(f"FullGraphTrainer: table has {table.shape[0]} rows for {self.n} nodes")
+            dev, d0 = table.device, table.shape[1]
+        else:
+            ops._chk(embed_index, torch.int32, "embed_index", 1)
+            if self.n < 1 or embed_index.shape[0] != self.n:
+                raise SageError(f"FullGraphTrainer: embed_index has {embed_index.shape[0]} entries for {self.n} nodes")
+            if embed_rows is None or embed_dim is None or int(embed_rows) < 1 or int(embed_dim) < 1:
+                raise SageError(f"FullGraphTrainer: embed_rows = {embed_rows!r}, embed_dim = {embed_dim!r}")
+            dev, d0 = embed_index.device, int(embed_dim)
+        self.table, self.embed_index, self.embed, self.dev = table, embed_index, None, dev
+        self.head, self.lr, self.concat, self.self_loop, self.act1 = head, float(lr), not gcn, bool(agg_self_loop), act1
         m = 1 if gcn else 2
         self.d0, self.h1, self.h2 = d0, int(hidden1), int(hidden2)
         self.w1 = torch.empty(hidden1, m * d0, device=dev)
@@ -59,39 +87,59 @@ class FullGraphTrainer:
         self.w_cls = torch.empty(num_classes, hidden2, device=dev)
         for w in (self.w1, self.w2, self.w_cls):
             init.xavier_uniform_(w)
+        if embed_index is not None:
+            self.embed = torch.empty(int(embed_rows), d0, device=dev)
+            init.normal_(self.embed)
         dist.broadcast_params(self.parameters())
         # the transpose of the layer-2 graph: what csr_mean's backward sums over.  Built once (a sort of the edges)
         self.rowptr2_t, self.col2_t = ops.csr_transpose(self.rowptr2, self.col2)
         self._ws = {}
-        self.agg1 = self.h1_out = self.agg2 = self.out = None
-        self.refresh_table()
+        self.agg1 = self.h1_out = self.agg2 = self.out = self.x = None
+        if embed_index is None:
+            self.refresh_table()
+            return
+        # what the embedding's backward sums over, both built once: the transpose of the layer-1 graph (the outer one's when there
+        # is one graph), and the nodes of every embedding row (group_rows refuses an index outside [0, embed_rows))
+        one_graph = self.rowptr2 is rowptr and self.col2 is col
+        self.rowptr_t, self.col_t = (self.rowptr2_t, self.col2_t) if one_graph else ops.csr_transpose(rowptr, col)
+        self.identity = int(embed_rows) == self.n and bool(torch.equal(embed_index, torch.arange(self.n, dtype=torch.int32, device=dev)))
+        self.groups = None if self.identity else ops.group_rows(embed_index, int(embed_rows))
+        self._index64 = None if self.identity else embed_index.long()
 
     def parameters(self):
-        return [self.w1, self.w2, self.w_cls]
+        return [self.w1, self.w2, self.w_cls] + ([self.embed] if self.embed is not None else [])
 
     def _scratch(self, name, nbytes):
         t = self._ws.get(name)
         if t is None or t.numel() < nbytes:
-            t = self._ws[name] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self.table.device)
+            t = self._ws[name] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self.dev)
         return t
 
     def refresh_table(self):
-        """The layer-1 mean of the (frozen) table: computed at construction, and again here after the caller changed the table."""
+        """The layer-1 mean of the (frozen) table: computed at construction, and again here after the caller changed the table.
+        With a trainable embedding there is no table to refresh: the mean is computed by every forward()."""
+        if self.embed is not None:
+            raise SageError("FullGraphTrainer.refresh_table: layer 1 reads a trainable embedding, not a table")
         ws = self._scratch("mean1", ops.csr_mean_workspace_bytes(self.n, self.col.numel(), self.d0))
         self.agg1 = ops.csr_mean(self.rowptr, self.col, self.table, self_loop=self.self_loop, out=self.agg1, workspace=ws)
         return self.agg1
 
     def forward(self):
         """[N, h2] embeddings of every node; agg1, h1 and agg2 stay in the trainer for the backward."""
-        tab = self.table[:self.n]
-        self.h1_out = ops.linear_act(self.agg1, self.w1, ACT_RELU, self_tab=tab if self.concat else None, out=self.h1_out)
+        if self.embed is None:
+            tab = self.table[:self.n]
+        else:
+            tab = self.x = self.embed if self.identity else torch.index_select(self.embed, 0, self._index64, out=self.x)
+            ws = self._scratch("mean1", ops.csr_mean_workspace_bytes(self.n, self.col.numel(), self.d0))
+            self.agg1 = ops.csr_mean(self.rowptr, self.col, tab, self_loop=self.self_loop, out=self.agg1, workspace=ws)
+        self.h1_out = ops.linear_act(self.agg1, self.w1, self.act1, self_tab=tab if self.concat else None, out=self.h1_out)
         ws = self._scratch("mean2", ops.csr_mean_workspace_bytes(self.n, self.col2.numel(), self.h1))
         self.agg2 = ops.csr_mean(self.rowptr2, self.col2, self.h1_out, self_loop=self.self_loop, out=self.agg2, workspace=ws)
         self.out = ops.linear_act(self.agg2, self.w2, ACT_RELU, self_tab=self.h1_out if self.concat else None, out=self.out)
         return self.out
 
-    def _linear_backward(self, self_tab, agg, weight, out, grad_out, need_x, what):
-        """sage_linear_act_backward_ws over all N rows -> (grad_weight, grad_x [N, kw] or None)."""
+    def _linear_backward(self, self_tab, agg, weight, act, out, grad_out, need_x, what):
+        """sage_linear_act_backward_ws over all N rows of a layer with activation `act` -> (grad_weight, grad_x [N, kw] or None)."""
         lib, P = native.lib(), native.ptr
         n, dim = agg.shape
         out_dim, kw = weight.shape
@@ -99,14 +147,15 @@ class FullGraphTrainer:
         g_x = torch.empty(n, kw, device=agg.device) if need_x else None
         ws = self._scratch("dw", lib.sage_linear_act_backward_workspace_bytes(n, dim, int(self_tab is not None), out_dim))
         rc = lib.sage_linear_act_backward_ws(P(self_tab), self_tab.stride(0) if self_tab is not None else 0, None, P(agg), agg.stride(0), dim,
-                                             P(weight), weight.stride(0), out_dim, ACT_RELU, P(out), out.stride(0), P(grad_out),
+                                             P(weight), weight.stride(0), out_dim, int(act), P(out), out.stride(0), P(grad_out),
                                              grad_out.stride(0), n, None, P(g_w), g_w.stride(0), P(g_x), kw, None,
                                              P(ws), ws.numel(), native.stream_handle())
         native.check(rc, what)
         return g_w, g_x
 
     def grads(self, train_ids, labels):
-        """loss (device scalar) and the gradients of (w1, w2, w_cls) on the training rows; nothing is updated.
+        """loss (device scalar) and the gradients of (w1, w2, w_cls) -- and of embed, fourth, when layer 1 reads a trainable
+        embedding -- on the training rows; nothing is updated.
         train_ids: DISTINCT int32 node ids on the device, labels int64 [len(train_ids)].  The rows' gradients are placed with
         index_copy_ (distinct ids: no two writers), never with an atomic scatter."""
         ops._chk(train_ids, torch.int32, "train_ids", 1)
@@ -129,23 +178,36 @@ class FullGraphTrainer:
             g_cls = _sum_over_batch(g_scores, emb)                           # [C, B] x [B, H2]: reduction over the batch, fixed order
         g_out = torch.zeros_like(out).index_copy_(0, idx, g_emb)
         # layer 2 over all N rows (a row outside the training set adds exact zeros): dW2 and d[h1_self | agg2]
-        g_w2, g_x2 = self._linear_backward(self.h1_out if self.concat else None, self.agg2, self.w2, out, g_out, True, "linear_act_backward (layer 2)")
+        g_w2, g_x2 = self._linear_backward(self.h1_out if self.concat else None, self.agg2, self.w2, ACT_RELU, out, g_out, True, "linear_act_backward (layer 2)")
         ds = self.h1 if self.concat else 0
         ws = self._scratch("mean2_bwd", ops.csr_mean_backward_workspace_bytes(self.n, self.n, self.col2_t.numel(), self.h1))
         g_h1 = ops.csr_mean_backward(self.rowptr2, self.col2, self.rowptr2_t, self.col2_t, g_x2[:, ds:], self_loop=self.self_loop, workspace=ws)
         if self.concat:
             g_h1 += g_x2[:, :ds]                                             # the concat encoder's own-row part
-        # layer 1: only dW1, the table is frozen
-        g_w1, _ = self._linear_backward(self.table[:self.n] if self.concat else None, self.agg1, self.w1, self.h1_out, g_h1, False,
-                                        "linear_act_backward (layer 1)")
-        return loss, (g_w1, g_w2, g_cls)
+        if self.embed is None:                                               # layer 1: only dW1, the table is frozen
+            g_w1, _ = self._linear_backward(self.table[:self.n] if self.concat else None, self.agg1, self.w1, self.act1, self.h1_out, g_h1,
+                                            False, "linear_act_backward (layer 1)")
+            return loss, (g_w1, g_w2, g_cls)
+        # layer 1 with its input's gradient: dW1 and d[X_self | agg1]; the mean's adjoint on the inner graph gives dX
+        g_w1, g_x1 = self._linear_backward(self.x if self.concat else None, self.agg1, self.w1, self.act1, self.h1_out, g_h1, True,
+                                           "linear_act_backward (layer 1)")
+        ds = self.d0 if self.concat else 0
+        ws = self._scratch("mean1_bwd", ops.csr_mean_backward_workspace_bytes(self.n, self.n, self.col_t.numel(), self.d0))
+        g_x = ops.csr_mean_backward(self.rowptr, self.col, self.rowptr_t, self.col_t, g_x1[:, ds:], self_loop=self.self_loop, workspace=ws)
+        if self.concat:
+            g_x += g_x1[:, :ds]                                              # the concat encoder's own-row part
+        if self.identity:
+            return loss, (g_w1, g_w2, g_cls, g_x)
+        # every embedding row collects the rows of the nodes that read it, in ascending node order
+        rowptr_g, col_g = self.groups
+        ws = self._scratch("embed_sum", ops.csr_sum_workspace_bytes(rowptr_g.shape[0] - 1, self.n, self.d0))
+        return loss, (g_w1, g_w2, g_cls, ops.csr_sum(rowptr_g, col_g, g_x, workspace=ws))
 
     def step(self, train_ids, labels):
         """forward + backward + in-place SGD; -> the loss as a device scalar (reading it is the caller's only synchronisation)."""
-        loss, (g1, g2, gc) = self.grads(train_ids, labels)
-        self.w1.add_(g1, alpha=-self.lr)
-        self.w2.add_(g2, alpha=-self.lr)
-        self.w_cls.add_(gc, alpha=-self.lr)
+        loss, g = self.grads(train_ids, labels)
+        for w, gw in zip(self.parameters(), g):
+            w.add_(gw, alpha=-self.lr)
         return loss
 
     def predict(self, ids=None):
@@ -158,21 +220,46 @@ class FullGraphTrainer:
         return ops.xent_head(emb, self.w_cls, grads=False, pred=True)["pred"]
 
 
+def one_hot_index(n, device="cuda"):
+    """(index, K) of the 1hot initializer: node v reads embedding row v, K = n rows."""
+    return torch.arange(int(n), dtype=torch.int32, device=device), int(n)
+
+
+def degree_index(rowptr):
+    """(index, K) of the node_degree initializer (model.py:153-157): node v reads the row of its layer-1 degree len(adj_lists[v])
+    -- its CSR row's length -- and K = max degree + 1.  rowptr: int64 [N + 1], on any device; the index lives beside it."""
+    deg = (rowptr[1:] - rowptr[:-1]).to(torch.int32)
+    return deg.contiguous(), (int(deg.max()) + 1 if deg.numel() else 1)
+
+
 def run_full_graph_training(graph, feat_data, labels, num_classes, seed=1, steps=100, lr=0.7, hidden1=50, hidden2=128, gcn=True,
-                            agg_self_loop=False, head="native"):
+                            agg_self_loop=False, head="native", initializer="None", embed_dim=100):
     """run_model (model.py:184-259) with full neighbourhoods: the same 10 / 10 / 80 split of np.random.permutation
     (model.py:229-235), ONE step per epoch over the whole training set, `steps` epochs.
+    initializer: "None" -- the frozen table feat_data, ReLU at both layers; "1hot" -- a trainable embedding row per node, ReLU;
+    "node_degree" -- a trainable embedding row per degree, SIGMOID at layer 1 (encoders.py:58).  feat_data is not read for the
+    last two and may be None.  embed_dim is the embedding's width; its default is the reference's --feature_dim default.  The
+    reference itself overrides that width for these two initializers with the one-hot's (N and max degree + 1, model.py:209-212)
+    because its loader hands the one-hot in as the feature table: an accident of the loader, not copied here.
     -> dict(f1_micro, f1_macro, mean_step_time, losses, trainer), as train.run_engine_training."""
     from sklearn.metrics import f1_score
+    if initializer not in ("None", "1hot", "node_degree"):
+        raise SageError(f"run_full_graph_training: initializer = {initializer!r}, expected 'None', '1hot' or 'node_degree'")
     dev = torch.device("cuda")
     np.random.seed(seed)
     rowptr, col = graph.to(dev)
-    table = torch.as_tensor(feat_data, dtype=torch.float32).to(dev)
     n = graph.num_nodes
     rand_indices = np.random.permutation(n)
     val = rand_indices[int(0.1 * n):int(0.2 * n)]
     train = rand_indices[int(0.2 * n):]
-    tr = FullGraphTrainer(rowptr, col, table, num_classes, hidden1, hidden2, gcn=gcn, lr=lr, agg_self_loop=agg_self_loop, head=head)
+    if initializer == "None":
+        table = torch.as_tensor(feat_data, dtype=torch.float32).to(dev)
+        tr = FullGraphTrainer(rowptr, col, table, num_classes, hidden1, hidden2, gcn=gcn, lr=lr, agg_self_loop=agg_self_loop, head=head)
+    else:
+        index, k = one_hot_index(n, dev) if initializer == "1hot" else degree_index(rowptr)
+        tr = FullGraphTrainer(rowptr, col, None, num_classes, hidden1, hidden2, gcn=gcn, lr=lr, agg_self_loop=agg_self_loop, head=head,
+                              embed_index=index, embed_rows=k, embed_dim=embed_dim,
+                              act1=ACT_SIGMOID if initializer == "node_degree" else ACT_RELU)
     labels_dev = torch.as_tensor(np.asarray(labels).reshape(-1), dtype=torch.int64).to(dev)
     ids = torch.as_tensor(train.astype(np.int32)).to(dev)
     tgt = labels_dev[ids.long()]

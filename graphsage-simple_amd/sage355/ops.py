@@ -396,6 +396,69 @@ def csr_mean_backward(rowptr, col, rowptr_t, col_t, grad_out, nodes=None, self_l
     return out
 
 
+def group_rows(index, num_groups):
+    """(rowptr_g int64 [K + 1], col_g int32 [N]) of an index [N] with values in [0, K = num_groups): row k of this rectangular
+    CSR holds the positions v with index[v] == k, ascending -- what csr_sum adds up for row k of a shared embedding
+    (aggregators.py:68-71).  Torch ops (a stable sort, bincount, cumsum) on the index's own device, CPU or GPU; built once per
+    graph, like csr_transpose.  A value outside [0, K) raises."""
+    if not isinstance(index, torch.Tensor) or index.dim() != 1 or index.dtype not in (torch.int32, torch.int64):
+        raise native.SageError("group_rows: index must be a 1-d int32 / int64 tensor")
+    k = int(num_groups)
+    if k < 0 or index.numel() >= (1 << 31):
+        raise native.SageError(f"group_rows: num_groups = {k}, {index.numel()} positions")
+    idx = index.to(torch.int64)
+    if idx.numel() > 0:
+        lo, hi = int(idx.min()), int(idx.max())
+        if lo < 0 or hi >= k:
+            raise native.SageError(f"group_rows: index {lo if lo < 0 else hi} outside [0, {k})")
+    col_g = torch.sort(idx, stable=True).indices.to(torch.int32)      # positions are ascending already: stable keeps them so inside a group
+    rowptr_g = torch.zeros(k + 1, dtype=torch.int64, device=index.device)
+    if k > 0:
+        rowptr_g[1:] = torch.cumsum(torch.bincount(idx, minlength=k), 0)
+    return rowptr_g, col_g
+
+
+def csr_sum_workspace_bytes(num_rows, max_edges, dim):
+    """Bytes of the workspace sage_csr_sum needs (host arithmetic; 0 = shape out of range)."""
+    return int(native.lib().sage_csr_sum_workspace_bytes(int(num_rows), int(max_edges), int(dim)))
+
+
+def csr_sum(rowptr, col, table, out=None, max_edges=None, workspace=None):
+    """[K, dim]: row r is the sum of table[col[e]] over row r's entries of the rectangular CSR (rowptr [K + 1], col) in stored
+    order -- with (rowptr, col) = group_rows(index, K) the gradient of an embedding read as embed[index].  The result is stored,
+    not accumulated; an empty row is zeros.  max_edges: upper bound on rowptr[-1], default len(col) (a smaller bound only costs
+    speed).  workspace: a uint8 device tensor to reuse."""
+    _need_gpu()
+    _chk(rowptr, torch.int64, "rowptr", 1)
+    _chk(col, torch.int32, "col", 1)
+    table, ld = _row_major(table, "table")
+    num_rows = rowptr.shape[0] - 1
+    if num_rows < 0:
+        raise native.SageError("csr_sum: rowptr is empty")
+    if table.shape[0] < 1:
+        raise native.SageError("csr_sum: table has no rows")
+    dim = table.shape[1]
+    if out is None:
+        out = torch.empty((num_rows, dim), dtype=torch.float32, device=table.device)
+    out, ldo = _row_major(out, "out")
+    if out.shape[0] < num_rows or out.shape[1] != dim:
+        raise native.SageError(f"csr_sum: out is {tuple(out.shape)}, expected ({num_rows}, {dim})")
+    if num_rows == 0:
+        return out
+    if col.numel() == 0:                                  # an empty tensor may have no storage address: the kernels read none of it
+        col = torch.zeros(1, dtype=torch.int32, device=table.device)
+    max_edges = col.numel() if max_edges is None else int(max_edges)
+    need = csr_sum_workspace_bytes(num_rows, max_edges, dim)
+    if need == 0:
+        raise native.SageError(f"csr_sum: num_rows = {num_rows}, max_edges = {max_edges}, dim = {dim} out of range")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=table.device)
+    rc = native.lib().sage_csr_sum(native.ptr(rowptr), native.ptr(col), num_rows, max_edges, native.ptr(table), table.shape[0], ld, dim,
+                                   native.ptr(out), ldo, native.ptr(workspace), workspace.numel(), native.stream_handle())
+    native.check(rc, "csr_sum")
+    return out
+
+
 def xent_head_supported(dim, num_classes):
     return bool(native.lib().sage_xent_head_supported(int(dim), int(num_classes)))
 

@@ -227,6 +227,38 @@ int sage_csr_mean_backward(const int64_t* rowptr, const int32_t* col,
                            void* workspace, size_t workspace_bytes, sage_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * sage_csr_sum (additive, ABI 9) -- the gradient of a shared embedding row.
+ * aggregators.py:68-71 looks features up in a trainable nn.Embedding: node v
+ * reads row index[v] (its own row for 1hot, its degree's row for node_degree),
+ * so row k's gradient is the sum of grad_X[v] over the nodes v with
+ * index[v] = k.  Over a RECTANGULAR CSR -- num_rows groups, entries that name
+ * rows of a table of table_rows rows; the caller builds it once per graph --
+ *     out[r, :] = sum of table[col[e], :] over e in [rowptr[r], rowptr[r+1]),
+ *                 e ascending
+ * No division, no self term, no NaN rule.  out is [num_rows, dim], leading
+ * dimension ldo; every row is STORED, nothing is accumulated into: an empty row
+ * is exact zeros.  Not written: columns [dim, ldo).
+ * Load balance is sage_csr_mean's: rows longer than SAGE_CSR_MEAN_CHUNK entries
+ * are cut into chunks of that many, summed by separate waves into workspace
+ * partials and added in chunk order.  max_edges bounds rowptr[num_rows] and
+ * sizes the workspace; a bound that is too small costs speed only, the bits
+ * are the same.  No float atomics: a row's bits depend only on its entries and
+ * the table.
+ * A wrong grouping gives wrong numbers, never an access out of range: ids from
+ * col are clamped into the table, row pointers into [0, rowptr[num_rows]] and
+ * made non-decreasing (col holds at least rowptr[num_rows] entries).
+ * Any dim >= 1, ld >= dim, ldo >= dim; 16-byte accesses when dim, ld, ldo are
+ * multiples of 4 and both arrays are 16-byte aligned.  num_rows == 0 returns
+ * SAGE_OK without a launch.  Workspace 256-byte aligned; the query returns 0
+ * for a shape out of range.
+ * ------------------------------------------------------------------------- */
+size_t sage_csr_sum_workspace_bytes(int64_t num_rows, int64_t max_edges, int32_t dim);
+int sage_csr_sum(const int64_t* rowptr, const int32_t* col, int64_t num_rows, int64_t max_edges,
+                 const float* table, int64_t table_rows, int64_t ld, int32_t dim,
+                 float* out, int64_t ldo,
+                 void* workspace, size_t workspace_bytes, sage_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * sage_linear_act --encoders.py:49-62 without materialising the concat:
  *     out[r, :] = act( W[:, 0:ds] . self(r) + W[:, ds:ds+dim] . agg[r, :] )
  * self(r) = self_tab[self_index ? self_index[r] : r, 0:dim]; ds = dim when
