@@ -138,3 +138,273 @@ def usable_cores():
     except Exception:
         pass
     return n
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The split layer 1 (csrc/sage_gather.hip + dense_bf16x3_kernel of csrc/sage_dense.hip): data generators, fp64 references and the
+# two element-wise bars, shared by tests/test_gpu_split_layer1.py (the kernels) and tests/test_split_layer1_host.py (numpy fp32
+# emulations of the kernels' arithmetic, faithful and deliberately broken, on the very same data).
+def gather_form(dim, ld, ldo, n, k, aligned=True):
+    """sage_launch_gather_mean's default dispatch on a row-major table, restated: -> (form, lanes per slice, ids per trip).
+    "sliced": the column-sliced pipelined kernel (16-lane slices; ONE 32-lane slice for rows of at most 128 floats that do not
+    end on a 64-float boundary), U = 2 / 4 / 8 wave-instructions of 64 / lanes ids per trip; "wave4" / "wave1": one wave per
+    row with 16-byte or 4-byte loads, 8 row loads in flight, ids in pages of 64."""
+    vec4 = dim % 4 == 0 and ld % 4 == 0 and ldo % 4 == 0 and aligned
+    if vec4 and k <= 64 and ((dim >= 64 and n >= 8192) or dim > 256):
+        sl = 32 if (dim <= 128 and dim % 64 != 0) else 16
+        per = 64 // sl
+        need = -(-k // per)
+        u = (4 if need <= 4 else 8) if sl == 32 else (2 if need <= 2 else 4 if need <= 4 else 8)
+        return "sliced", sl, per * u
+    return ("wave4" if vec4 else "wave1"), 64, 8
+
+
+def edge_counts(k, trip):
+    """List lengths for a fanout of k: k, 0, 1, k - 1 and one short of, on and one past every multiple of `trip` (and of 64)."""
+    vals = [k, 0, 1, k - 1]
+    for step in (trip, 64):
+        for b in range(step, k + 2, step):
+            vals += [b - 1, b, b + 1]
+    out = []
+    for v in vals:
+        if 0 <= v <= k and v not in out:
+            out.append(v)
+    return out
+
+
+GATHER_HEAVY = 8          # table rows [0, 8) carry 64 x the magnitude of the others; every list ends in one of them
+
+
+def gather_case(n, k, dim, trip, seed):
+    """Hand-made inputs of one gather_mean call (numpy; ids are table rows).
+    cnt cycles through edge_counts(k, trip).  Row r's self row, by (r % L + r // L) % 6 with L list lengths (every length meets every kind): none; a row that is not in the list; list[0]; the
+    last valid entry; an entry in a trip after the first (cycling through the trips); an entry at a position >= 64 where the list
+    is that long (else the entry before the last).  Lists hold distinct ordinary rows and end (last VALID entry) in a heavy row.
+    Values: 10^U(-6, -1) with random signs, 10^U(-1, 0) in a row's last four columns, x 64 in the heavy rows."""
+    rs = np.random.default_rng(seed)
+    pool = max(k + 3, 61)
+    P = GATHER_HEAVY + pool
+    T = P + 2                                                     # + an ordinary and a heavy row that no list holds
+    mag = 10.0 ** rs.uniform(-6, -1, (T, dim))
+    mag[:, max(dim - 4, 0):] = 10.0 ** rs.uniform(-1, 0, (T, min(dim, 4)))
+    mag[:GATHER_HEAVY] *= 64
+    mag[P + 1] *= 64
+    table = (mag * rs.choice([-1.0, 1.0], (T, dim))).astype(np.float32)
+    vals = edge_counts(k, trip)
+    r = np.arange(n)
+    cnt = np.asarray(vals)[r % len(vals)].astype(np.int64)
+    nbr = (np.argsort(rs.random((n, pool)), axis=1)[:, :k] + GATHER_HEAVY).astype(np.int64)
+    has = cnt > 0
+    nbr[r[has], cnt[has] - 1] = r[has] % GATHER_HEAVY
+    mode = (r % len(vals) + r // len(vals)) % 6
+    mode[1:2] = 0                                                 # row 1 (cnt = 0) has no self row: an empty set even when n = 2
+    long = np.nonzero(cnt > 64)[0]
+    mode[long[1::2]] = 5                                          # every second list longer than 64: a self row at a position >= 64
+    ntrip_after = np.maximum((cnt - 1) // trip, 1)
+    pos4 = np.where(cnt > trip, np.minimum((1 + (r // 6) % ntrip_after) * trip + r % trip, cnt - 1), cnt // 2)
+    pos5 = np.where(cnt > 64, 64 + r % np.maximum(cnt - 64, 1), np.maximum(cnt - 2, 0))
+    pos = np.select([mode == 2, mode == 3, mode == 4, mode == 5], [0 * r, np.maximum(cnt - 1, 0), pos4, pos5], 0)
+    absent = P + r % 2
+    self_eff = np.where(mode == 0, -1, np.where((mode == 1) | ~has, absent, nbr[r, np.minimum(pos, k - 1)]))
+    return {"table": table, "nbr": nbr, "cnt": cnt, "self": self_eff.astype(np.int64), "pos": pos, "mode": mode, "trip": trip}
+
+
+def gather_reference(table, nbr, cnt, self_eff, flag):
+    """fp64 mean over the set (list[:cnt] and, unless it is among them, the self row) -> (ref, bar, ceff).  Empty sets: NaN when
+    `flag`, zeros otherwise.  bar = 1.01 (ceff + 2) 2^-24 sum_j |x_j| / ceff per element: an fp32 sum of ceff terms in any order
+    ((ceff - 1) roundings of at most 2^-24 of the sum of magnitudes each) times a rounded reciprocal, rounded (2 more), with 1 %
+    for the second-order terms.  Derived, not measured."""
+    t = np.asarray(table, dtype=np.float64)
+    n, k = nbr.shape
+    tot, mass = np.zeros((n, t.shape[1])), np.zeros((n, t.shape[1]))
+    inlist = np.zeros(n, dtype=bool)
+    for j in range(k):
+        m = j < cnt
+        rows = t[np.clip(nbr[:, j], 0, len(t) - 1)] * m[:, None]
+        tot += rows
+        mass += np.abs(rows)
+        if self_eff is not None:
+            inlist |= m & (nbr[:, j] == self_eff)
+    extra = np.zeros(n, dtype=bool) if self_eff is None else (self_eff >= 0) & ~inlist
+    if extra.any():
+        srow = t[np.clip(self_eff, 0, len(t) - 1)] * extra[:, None]
+        tot += srow
+        mass += np.abs(srow)
+    ceff = cnt + extra
+    d = np.maximum(ceff, 1)[:, None]
+    ref = tot / d
+    ref[ceff == 0] = np.nan if flag else 0.0
+    bar = 1.01 * (ceff[:, None] + 2) * 2.0 ** -24 * mass / d
+    return ref, bar, ceff
+
+
+def gather_miss(got, ref, bar, ceff):
+    """How `got` misses the gather bar: None when it meets it, else a message.  NaN and zero fills of empty sets must coincide
+    exactly; every other element is within its bar."""
+    got = np.asarray(got, dtype=np.float64)
+    if got.shape != ref.shape:
+        return f"shape {got.shape} vs {ref.shape}"
+    if not np.array_equal(np.isnan(got), np.isnan(ref)):
+        return f"NaN pattern differs in rows {np.nonzero((np.isnan(got) != np.isnan(ref)).any(1))[0][:8].tolist()}"
+    empty = ceff == 0
+    if empty.any() and not np.isnan(ref[empty]).any() and np.any(got[empty] != 0.0):
+        return "an empty set is not filled with zeros"
+    fin = ~np.isnan(ref)
+    excess = np.where(fin, np.abs(np.where(fin, got - ref, 0.0)) - bar, -1.0)
+    if np.any(excess > 0):
+        r, c = np.unravel_index(np.argmax(np.where(fin, np.abs(np.where(fin, got - ref, 0.0)) / np.maximum(bar, 1e-300), 0.0)), ref.shape)
+        return (f"row {r} (set of {ceff[r]}) column {c}: |got - ref| = {abs(got[r, c] - ref[r, c]):.3e} > bar {bar[r, c]:.3e} "
+                f"({int((excess > 0).sum())} elements over)")
+    return None
+
+
+def split_graph(rows, k1, concat, self_loop, seed):
+    """A hand-made seed -> frontier graph for `rows` layer-1 rows, whose degrees are at most the fanouts (k1 inner, 64 outer), so the
+    sampler takes whole neighbourhoods.  With an outer fanout of 64 one wavefront samples one seed and the seed's neighbours get
+    consecutive frontier rows in list order; only the order of the seeds' CHUNKS is the device's choice.  So every chunk ends alike --
+    ..., a row that takes the contraction's exact path, a row that carries the largest values -- and whichever chunk comes last, the
+    last layer-1 row and the last 32-row tile are what the test wants them to be.
+    Layer-1 rows: gcn: the frontier, chunks of 64; gcn with the self-loop aggregator: chunks of up to 63 frontier nodes followed by
+    their seed; concat: the seeds in order, then the frontier (one node below 100 rows, a third of the rows above).
+    Nodes: seeds [0, b), frontier [b, b + f), one private node per seed / frontier node, then 72 shared pool nodes.  Inner hop: node
+    v's list is c_v - 1 pool nodes and, last, its private node (under the self-loop aggregator a list of one is [v] itself, and every
+    third longer list holds v in the middle: the set union must not count it twice); c_v cycles through 1, k1, k1 - 1 and the values
+    around every multiple of 8.  `ender`: the nodes whose rows end a chunk (concat without a frontier: the last seed); `huge`: the
+    nodes before them (concat with at most one frontier node: the last seed), with a list of one; `iso`: one node without
+    neighbours, 13 rows into the first chunk (concat: seed 13, or an earlier one), -1 when there are too few rows.
+    `order`: the layer-1 rows with the chunks in seed order."""
+    if concat:
+        f = (0 if rows == 1 else 1) if rows < 100 else rows // 3
+        b = rows - f
+        sizes = [64] * (f // 64) + ([f % 64] if f % 64 else [])
+    elif self_loop:
+        b = -(-rows // 64)
+        f = rows - b
+        sizes = [min(63, max(f - 63 * i, 0)) for i in range(b)]
+    else:
+        f = rows
+        sizes = [64] * (f // 64) + ([f % 64] if f % 64 else [])
+        b = len(sizes)
+    assert len(sizes) <= b and sum(sizes) == f
+    nl = b + f
+    pool0, npool = 2 * nl, 72
+    N = pool0 + npool
+    starts = b + np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+    chunks = [np.arange(starts[i], starts[i] + sizes[i]) for i in range(len(sizes))]
+    ender, huge, mate, order = [], [], {}, []
+    for i, ch in enumerate(chunks):
+        members = list(ch) + ([i] if self_loop else [])
+        order += members
+        if members:
+            ender.append(int(members[-1]))
+            mate[int(members[-1])] = int(members[-2]) if len(members) >= 2 else -1
+            if len(members) >= 2:
+                huge.append(int(members[-2]))
+    if concat:
+        order = list(range(b)) + order
+        if f == 0:
+            ender.append(b - 1)
+            mate[b - 1] = -1
+        elif f == 1 and b >= 2:
+            huge.append(b - 1)
+            mate[ender[-1]] = b - 1
+    iso = -1
+    if rows >= 3:
+        if concat:
+            iso = min(13, b - 2) if b >= 3 else -1
+        elif sizes[0] >= 16:
+            iso = int(chunks[0][13])
+        elif sizes[0] >= 3:
+            iso = int(chunks[0][0])
+    vals = [v for v in edge_counts(k1, 8) if v >= 1]
+    deg = np.zeros(N, dtype=np.int64)
+    deg[:nl] = np.asarray(vals)[(np.arange(nl) * 5 + seed) % len(vals)]
+    deg[huge] = 1
+    if iso >= 0:
+        deg[iso] = 0
+    rowptr_in = np.zeros(N + 1, dtype=np.int64)
+    rowptr_in[1:] = np.cumsum(deg)
+    col_in = np.zeros(int(rowptr_in[-1]), dtype=np.int32)
+    v = np.repeat(np.arange(nl), deg[:nl])
+    j = np.arange(len(col_in)) - rowptr_in[v]
+    col_in[:] = pool0 + (v * 7 + j) % npool                      # distinct for j < 72
+    last = j == deg[v] - 1
+    src = nl + np.arange(nl)
+    if self_loop:
+        src[deg[:nl] == 1] = np.nonzero(deg[:nl] == 1)[0]
+        mid = (j == deg[v] // 2) & (v % 3 == 0) & (deg[v] >= 3)
+        col_in[mid] = v[mid]
+    col_in[last] = src[v[last]]
+    od = np.zeros(N, dtype=np.int64)
+    od[:len(sizes)] = sizes
+    rowptr_out = np.zeros(N + 1, dtype=np.int64)
+    rowptr_out[1:] = np.cumsum(od)
+    col_out = (b + np.arange(f)).astype(np.int32)
+    return {"num_nodes": N, "rowptr_in": rowptr_in, "col_in": col_in, "rowptr_out": rowptr_out, "col_out": col_out, "deg": deg,
+            "src": src, "iso": iso, "nl": nl, "b": b, "f": f, "ender": ender, "huge": huge, "mate": mate,
+            "order": np.asarray(order, dtype=np.int64)}
+
+
+def split_lists(g, s1_nodes, k1):
+    """The padded inner-hop lists of layer-1 rows `s1_nodes` of split_graph `g`, in CSR order: what a sampler that takes whole
+    neighbourhoods leaves (as sets).  -> (nbr1 [rows, k1], cnt1 [rows])"""
+    s1 = np.asarray(s1_nodes, dtype=np.int64)
+    cnt1 = g["deg"][s1]
+    nbr1 = np.zeros((len(s1), k1), dtype=np.int64)
+    for j in range(k1):
+        m = j < cnt1
+        nbr1[m, j] = g["col_in"][g["rowptr_in"][s1[m]] + j]
+    return nbr1, cnt1
+
+
+def split_data(g, d0, h1, concat, seed):
+    """Table [N, d0] and W1 [h1, m d0] for split_graph `g`.  Values 10^U(-2, 0) with random signs; the last four columns of the
+    table and of each K chunk of W1 x 16 (the last four K columns carry the largest products), the rows that end a list x 4, the
+    `ender` nodes' list-ending rows x 8 x the list's length more (and, concat, their own rows x 8), W1's last output row x 8.
+    The `huge` nodes get a 3e38 entry in column 1 -- concat: of their own table row; gcn: of the row that IS their one-entry list --
+    so that their rows alone take the contraction's exact path (that K column of W1 is divided by 64: no product overflows).
+    -> (table, w1)"""
+    rs = np.random.default_rng(seed)
+    N, nl = g["num_nodes"], g["nl"]
+    m = 2 if concat else 1
+    table = 10.0 ** rs.uniform(-2, 0, (N, d0)) * rs.choice([-1.0, 1.0], (N, d0))
+    table[:, d0 - 4:] *= 16
+    table[np.unique(g["src"])] *= 4
+    for e in g["ender"]:
+        table[g["src"][e]] *= 8 * max(int(g["deg"][e]), 1)
+        if concat and g["src"][e] != e:
+            table[e] *= 8
+    w1 = rs.standard_normal((h1, m * d0)) / np.sqrt(m * d0)
+    for c in range(m):
+        w1[:, (c + 1) * d0 - 4: (c + 1) * d0] *= 16
+    w1[-1] *= 8
+    for h in g["huge"]:
+        table[h if concat else g["src"][h], 1] = 3.0e38
+    w1[:, 1 if concat else (m - 1) * d0 + 1] /= 64
+    return table.astype(np.float32), w1.astype(np.float32)
+
+
+def contraction_units(got, x, w):
+    """|got - x . w^T| per element in units of 2^-23 sum_k |x_k||w_k| (x, w: what the kernel was given, fp32), against fp64.
+    Rows of x that hold a NaN are NaN rows of the reference.  -> (units [n, h], ref)"""
+    x64, w64 = np.asarray(x, dtype=np.float64), np.asarray(w, dtype=np.float64)
+    nanrow = np.isnan(x64).any(1)
+    xz = np.where(nanrow[:, None], 0.0, x64)
+    ref = xz @ w64.T
+    scale = 2.0 ** -23 * (np.abs(xz) @ np.abs(w64).T)
+    units = np.abs(np.asarray(got, dtype=np.float64) - ref) / np.maximum(scale, 1e-300)
+    ref[nanrow] = np.nan
+    units[nanrow] = 0.0
+    return units, ref
+
+
+def contraction_bar(x, w, concat):
+    """The bar of the split-bf16 contraction in units of 2^-23 sum_k |x_k||w_k|.  K <= 512: the project's own figures for this
+    kernel (tests/test_gpu_round2.py: 4 for the gcn encoder, 6 for concat); deeper K (nobody has measured the multi-pass kernel): 6.
+    Or twice what torch's fp32 mm leaves on the same data on the CPU, whichever is larger -- the torch-fp32 yardstick, not derived.
+    -> (bar, torch's own figure)"""
+    fin = ~np.isnan(np.asarray(x)).any(1)
+    xf, wf = torch.from_numpy(np.ascontiguousarray(np.asarray(x, dtype=np.float32)[fin])), torch.from_numpy(np.asarray(w, dtype=np.float32))
+    e_torch = float(contraction_units((xf @ wf.t()).numpy(), xf.numpy(), wf.numpy())[0].max()) if fin.any() else 0.0
+    base = (6.0 if concat else 4.0) if x.shape[1] <= 512 else 6.0
+    return max(base, 2.0 * e_torch), e_torch
