@@ -1,7 +1,9 @@
 """Where does layer 2 run relative to the one-launch layer 1?  Reads a rocprofv3 --kernel-trace CSV of bench.py (gcn encoder, layer 1 as
 one phase-sliced launch: stage D is empty), numbers the kernels of every kind in order (= batch index) and reports, over the steady part
 of the timed region: the period, every kernel's in-pipeline duration, when L(b) starts relative to G(b)'s end and to G(b+1)'s start,
-and the gap between consecutive layer-1 launches.  dep_trace.py is the same for the split layer 1 (five kernels per batch).
+and the gap between consecutive layer-1 launches.  Layer 1 may alternate over two streams (SAGE_PIPE_G_ALT=1): its launches are numbered by
+start time whatever queue they ran in, the queues they used are listed, and the time two of them ran side by side is reported (the gap
+between consecutive launches is then negative).  dep_trace.py is the same for the split layer 1 (five kernels per batch).
     python experiments/l2_placement_trace.py <trace dir> [batches of the analysed phase to skip at each end]"""
 import collections
 import csv
@@ -28,7 +30,7 @@ rows = []
 for r in csv.DictReader(open(f)):
     k = kind(r["Kernel_Name"])
     if k:
-        rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), k))
+        rows.append((int(r["Start_Timestamp"]), int(r["End_Timestamp"]), k, r.get("Queue_Id", "?")))
 rows.sort()
 phases = [[rows[0]]]
 last = rows[0][1]
@@ -42,8 +44,10 @@ cands = [ph for ph in phases if 100 * 4 <= len(ph) <= 1000 * 4]
 p = cands[-1] if cands else max(phases, key=len)
 print("phases (kernels): " + " ".join(str(len(ph)) for ph in phases if len(ph) >= 50))
 by = collections.defaultdict(list)
-for s, e, k in p:
+queues = collections.defaultdict(collections.Counter)
+for s, e, k, q in p:
     by[k].append((s, e))
+    queues[k][q] += 1
 # a phase that also holds the preheat (its batches follow one another as closely) or a stray launch of the engine's set-up: the timed
 # region is what the phase ENDS with, so the kinds are aligned from the end and at most the last 220 batches are looked at
 n = min(220, min(len(v) for v in by.values()))
@@ -66,6 +70,9 @@ print(f"  L(b) start - G(b+1) start{stat(S['L'][lo:hi, 0] - S['G'][lo + 1:hi + 1
 print(f"  L(b) end - G(b+1) start  {stat(S['L'][lo:hi, 1] - S['G'][lo + 1:hi + 1, 0])}")
 print(f"  G(b+1) start - G(b) end  {stat(S['G'][lo + 1:hi + 1, 0] - S['G'][lo:hi, 1])}")
 print(f"  G(b) start - Si(b) end   {stat(S['G'][lo:hi, 0] - S['Si'][lo:hi, 1])}")
+print(f"  G(b) and G(b+1) together {stat(np.maximum(0.0, S['G'][lo:hi, 1] - S['G'][lo + 1:hi + 1, 0]))}")
+print(f"  G end-to-end period      {stat(np.diff(S['G'][lo:hi + 1, 1]))}")
+print("  queues used (whole phase): " + "  ".join(f"{k}: " + ", ".join(f"queue {q} x{c}" for q, c in sorted(queues[k].items())) for k in ("So", "Si", "G", "L")))
 t0 = S["G"][lo, 0]
 print("  timeline of four batches (us from G(b0) start):")
 for b in range(lo, lo + 4):

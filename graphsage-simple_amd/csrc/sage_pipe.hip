@@ -46,6 +46,33 @@
 // completed -- one hipEventQuery) is enqueued whole on stream L, like sage_forward2; the next batch starts on the role streams at once,
 // beside it.  Same kernels, same workspace, same arguments: bit-identical.  Not while capturing (an event query is not capturable);
 // needs four distinct role streams; SAGE_PIPE_EXPRESS=0 turns it off (A/B).
+//
+// Alternating layer-1 streams (round 10, SAGE_PIPE_G_ALT).  When stage D launches nothing (d_empty: the one-launch layer 1, the gather-only
+// form of a pre-transformed table) stream D's hardware queue is open and idle, and every layer 1 sits in stream G's queue, where
+// consecutive launches are 10 us apart (profiles/r09_trace/) although S(b+1) finished long before: a queue starts a dispatch of this
+// footprint only once the one in front has retired completely (experiments/mb_boundary.hip: 8.4 us in one stream, event or no event,
+// none across two streams).  Where the placement is taken, role G's calls for
+// batch b -- the wait on ev[RS][slot], the launch with its tail event ev[RG][slot] (or the record) -- go to st[RG] for even b and to
+// st[RD] for odd b, b being the submit counter since the last reset (pipe_desc::index), so that only the data, not queue order, holds
+// G(b+1) behind G(b).  Events, workspaces, the express lane and the host threads stay as they are: role G's thread feeds both streams,
+// role D's still makes no calls, L still waits on ev[RG][slot].  Never while capturing, never for express batches, only with four
+// distinct role streams; unless the knob says otherwise, only where stream L has a higher priority than both layer-1 streams
+// (alternate_on below has the measurement: without it layer 2 never finds a free CU between two overlapping layer-1 launches).  What relied on "G(b) before G(b+1) by stream order", and why it still holds:
+//   * workspace reuse: G(b + depth) reads and writes G(b)'s workspace; L(b) waits on ev[RG][slot] of G(b), S(b + depth) on L(b),
+//     G(b + depth) on S(b + depth) -- by events, whichever stream either launch took (with an odd depth they take different ones).
+//   * the events themselves: ev[RG][slot] is recorded on whichever stream carried the launch; a wait means the latest record made on
+//     the host before it, and the host order (role threads' counters, or submit_one's loop) is per batch, not per stream.
+//   * join: records and waits on all four role streams, st[RD] included (as before: the loop is over streams, not over busy roles);
+//     a marker recorded on st[RG] behind an odd last batch re-records ev[RG][slot] after L's wait for it was made (flush comes first).
+//   * fork: every role stream waits, st[RD] included, so an odd batch's layer 1 sees the caller's writes like an even one's.
+//   * update_weights / the Python side's weight and table refresh: join -> rewrite on the caller's stream -> update -> fork; join covers
+//     both layer-1 streams (and stream L's tail is behind every layer 1 anyway: L(b) follows G(b) by event and L(b-1) by stream order),
+//     fork orders both behind the rewrite.  The model's pointers are read on the host at enqueue time, after the flush.  An update that
+//     makes stage D non-empty ends the alternation from the next submit on (d_empty is read per submit); D(b) on st[RD] behind an odd
+//     batch's layer 1 there is only stream order between different workspaces.
+//   * flush / reset / destroy / set_threads look at host counters only; reset restarts the batch index at 0 (the caller has synchronised).
+//   * submit_profiled: the two timing events ride on the launch, on whichever stream it takes.
+//   * the run-ahead window counts batches (done[RL], markers on stream L): no stream G in it.
 #include <sched.h>
 #include <stdlib.h>
 
@@ -68,6 +95,8 @@ struct pipe_desc {                                      // one posted batch
     int slot;
     bool fresh;
     bool express;                                       // an IDLE pipeline's batch: all five launches on stream L, no hand-off (see submit_one)
+    bool alt;                                           // role G's calls for this batch go to stream D's idle queue (alternating layer-1 streams)
+    uint64_t index;                                     // the pipe's submit counter at this batch (since the last reset)
     void* gev[2];
 };
 }  // namespace
@@ -82,8 +111,10 @@ struct sage_pipe {
     hipEvent_t ev[4][SAGE_PIPE_MAX_DEPTH];              // [role][slot]: role's work on the slot's batch is enqueued
     hipEvent_t ev_fork;
     bool d_empty;                                       // stage D launches nothing for this model (sage_forward2_contract1_is_empty)
+    bool l_outranks_g;                                  // stream L's priority is above stream G's and stream D's (alternate_on)
     uint64_t submitted;
     int64_t express_count;                              // batches that took the express lane (submitting thread only)
+    int64_t alternate_count;                            // batches whose layer 1 went to stream D's queue (submitting thread only)
     // host enqueue threads
     int device;
     bool threaded;
@@ -127,10 +158,11 @@ static bool query_first() {
     static const bool on = [] { const char* v = getenv("SAGE_PIPE_QUERY"); return !(v && *v == '0'); }();
     return on;
 }
-int wait_on(sage_pipe* p, int consumer, int producer, int slot, bool capturing = false) {
+// `on`: the stream that carries the consumer's calls for this batch when it is not the role's own (alternating layer-1 streams)
+int wait_on(sage_pipe* p, int consumer, int producer, int slot, bool capturing = false, hipStream_t on = nullptr) {
     if (p->st[consumer] == p->st[producer]) return SAGE_OK;          // stream order already says it
     if (!capturing && query_first() && hipEventQuery(p->ev[producer][slot]) == hipSuccess) return SAGE_OK;
-    if (hipStreamWaitEvent(p->st[consumer], p->ev[producer][slot], 0) != hipSuccess) {
+    if (hipStreamWaitEvent(on ? on : p->st[consumer], p->ev[producer][slot], 0) != hipSuccess) {
         sage_set_error("pipe: hipStreamWaitEvent failed");
         return SAGE_ELAUNCH;
     }
@@ -147,9 +179,9 @@ int capture_id(hipStream_t st, unsigned long long* id) {
     if (status != hipStreamCaptureStatusActive) *id = 0;
     return SAGE_OK;
 }
-int record(sage_pipe* p, int role, int slot, bool needed) {
+int record(sage_pipe* p, int role, int slot, bool needed, hipStream_t on = nullptr) {
     if (!needed) return SAGE_OK;
-    if (hipEventRecord(p->ev[role][slot], p->st[role]) != hipSuccess) {
+    if (hipEventRecord(p->ev[role][slot], on ? on : p->st[role]) != hipSuccess) {
         sage_set_error("pipe: hipEventRecord failed");
         return SAGE_ELAUNCH;
     }
@@ -182,6 +214,7 @@ extern "C" int sage_pipe_create(const sage_model_t* m, int32_t batch, int32_t de
     p->ws_bytes = workspace_bytes;
     p->submitted = 0;
     p->express_count = 0;
+    p->alternate_count = 0;
     p->threaded = false;
     p->window = 0;
     p->device = 0;
@@ -194,6 +227,10 @@ extern "C" int sage_pipe_create(const sage_model_t* m, int32_t batch, int32_t de
     for (int r = 0; r < 4; ++r) p->st[r] = (hipStream_t)streams[r];
     for (int r = 0; r < 4; ++r)
         for (int i = 0; i < depth; ++i) p->ev[r][i] = nullptr;
+    int prio[4] = {0, 0, 0, 0};                         // HIP: the lower number is the higher priority
+    bool known = true;
+    for (int r = 0; r < 4; ++r) known &= hipStreamGetPriority(p->st[r], &prio[r]) == hipSuccess;
+    p->l_outranks_g = known && prio[RL] < prio[RG] && prio[RL] < prio[RD];
     p->ev_fork = nullptr;
     if (hipEventCreateWithFlags(&p->ev_fork, kEventFlags) != hipSuccess) {
         sage_set_error("pipe_create: hipEventCreate failed");
@@ -236,6 +273,11 @@ extern "C" int sage_pipe_update_weights(sage_pipe_t* p, const float* w1, const f
     return SAGE_OK;
 }
 
+static bool stage_d_skipped(const sage_pipe* p) {
+    static const bool keep_empty_d = [] { const char* v = getenv("SAGE_PIPE_EMPTY_D"); return v && *v == '1'; }();
+    return !keep_empty_d && p->d_empty;
+}
+
 // Role r's calls for one batch, on role r's stream: wait for the producer's event, launch, record.  `fresh`: no earlier submit of
 // this pipe is outstanding on the slot (a fresh pipe, or the first `depth` submits after the caller joined and synchronised
 // everything before): the workspace-release wait is skipped.  Called for r = S, G, D, L in turn by the caller's thread
@@ -253,8 +295,7 @@ static int role_enqueue(sage_pipe* p, int r, const pipe_desc& d, unsigned long l
     // record are then skipped and L takes the hand-off from G directly -- one stream-to-stream hand-off less per batch.  (The role threads
     // still pass the batch from G's thread to D's to L's on the host, so L's wait is issued after G's record.)  SAGE_PIPE_EMPTY_D=1 keeps the
     // empty hand-off (A/B).
-    static const bool keep_empty_d = [] { const char* v = getenv("SAGE_PIPE_EMPTY_D"); return v && *v == '1'; }();
-    const bool d_empty = !keep_empty_d && p->d_empty;
+    const bool d_empty = stage_d_skipped(p);
     const int g_consumer = d_empty ? RL : RD;             // who takes G's hand-off
     if (d.express) {
         // the pipeline was idle at submit: no release to wait for, nothing to hand over; roles S, G, D have no calls to make
@@ -277,8 +318,10 @@ static int role_enqueue(sage_pipe* p, int r, const pipe_desc& d, unsigned long l
         {d_empty ? RG : RD, SAGE_STAGE_LAYER2, RS, true}};
     const auto& s = stage[r];
     if (r == RD && d_empty) return SAGE_OK;
+    // the stream of this role's calls: its own, or for an odd batch's layer 1 stream D's idle queue (header: alternating layer-1 streams)
+    hipStream_t const on = (r == RG && d.alt) ? p->st[RD] : p->st[r];
     if (r != RS) {
-        if (int rc = wait_on(p, r, s.producer, slot, cap != 0)) return rc;
+        if (int rc = wait_on(p, r, s.producer, slot, cap != 0, on)) return rc;
     } else if (!d.fresh && p->st[RS] != p->st[RL]) {      // the workspace-release edge L(b - depth) -> S(b)
         if (cap != 0) {
             // captured: the release edge as an explicit node dependency (an event wait here crashes hipStreamEndCapture, see above)
@@ -315,11 +358,11 @@ static int role_enqueue(sage_pipe* p, int r, const pipe_desc& d, unsigned long l
     if (!skip) {
         void* const t = tail(r, needed);
         if (int rc = sage_forward2_launch_stages(m, ws, p->ws_bytes, d.seeds, p->batch, d.key, s.takes_out ? d.out : nullptr,
-                                                 s.takes_out ? d.ldo : 0, s.stages, p->st[r], t, d.gev))
+                                                 s.takes_out ? d.ldo : 0, s.stages, on, t, d.gev))
             return rc;
         if (t) return SAGE_OK;
     }
-    return record(p, r, slot, needed);
+    return record(p, r, slot, needed, on);
 }
 
 // ---- host enqueue threads ------------------------------------------------------------------------------------------------
@@ -474,14 +517,33 @@ static bool express_on() {
     static const bool on = [] { const char* v = getenv("SAGE_PIPE_EXPRESS"); return !(v && *v == '0'); }();
     return on;
 }
-static bool pipe_idle(sage_pipe* p) {
-    if (!express_on()) return false;
+static bool distinct_streams(const sage_pipe* p) {
     for (int r = 0; r < 4; ++r)
         for (int q = 0; q < r; ++q)
-            if (p->st[q] == p->st[r]) return false;           // coinciding role streams skip records: nothing to ask
+            if (p->st[q] == p->st[r]) return false;
+    return true;
+}
+static bool pipe_idle(sage_pipe* p) {
+    if (!express_on()) return false;
+    if (!distinct_streams(p)) return false;                   // coinciding role streams skip records: nothing to ask
     if (p->submitted == 0) return true;                       // a new / reset pipe: the caller has synchronised what came before
     if (p->threaded && p->done[RL].load(std::memory_order_acquire) < p->submitted) return false;   // the last batch's record has not been made yet
     return hipEventQuery(p->ev[RL][(p->submitted - 1) % (uint64_t)p->depth]) == hipSuccess;
+}
+
+// Alternating layer-1 streams (header): SAGE_PIPE_G_ALT=0 / 1 turns them off / on, read once.  Unset, the pipe's streams decide
+// (l_outranks_g): the placement pays only where stream L outranks both layer-1 streams.  Measured, one box, interleaved with the parent
+// commit's tree (profiles/r10_ab.json): alternating with equal priorities 67.1-68.4 us per forward against 62.0-64.3 --
+// two layer-1 launches that follow each other without a gap never leave the whole CU free that layer 2's 1024-thread block needs, and
+// layer 2 starts 65 us behind its layer 1 instead of 17; with stream L at high priority 60.3-61.4 against 61.9-62.6, while that
+// priority without the alternation is worth nothing (61.3-62.5).
+static bool alternate_on(const sage_pipe* p) {
+    static const int knob = [] { const char* v = getenv("SAGE_PIPE_G_ALT"); return !v || !*v ? -1 : *v == '1' ? 1 : 0; }();
+    return knob < 0 ? p->l_outranks_g : knob == 1;
+}
+// this batch's layer 1 goes to stream D's queue: an odd batch of a pipe whose stage D launches nothing, eager, not express
+static bool takes_alternate(const sage_pipe* p, const pipe_desc& d, bool capturing) {
+    return alternate_on(p) && !capturing && !d.express && (d.index & 1) && stage_d_skipped(p) && distinct_streams(p);
 }
 
 // One batch through the four role streams.
@@ -492,6 +554,8 @@ static int submit_one(sage_pipe* p, const int32_t* seeds, uint64_t key, float* o
     d.slot = (int)(p->submitted % (uint64_t)p->depth);
     d.fresh = fresh_slot;
     d.express = false;
+    d.alt = false;
+    d.index = p->submitted;
     d.gev[0] = gather_events ? gather_events[0] : nullptr;
     d.gev[1] = gather_events ? gather_events[1] : nullptr;
     const int slot = d.slot;
@@ -500,12 +564,16 @@ static int submit_one(sage_pipe* p, const int32_t* seeds, uint64_t key, float* o
         if (int rc = p->worker_rc.load()) { sage_set_error("pipe: a role thread failed earlier (sage_pipe_flush reports it)"); return rc; }
         d.express = pipe_idle(p);
         p->express_count += d.express ? 1 : 0;
+        d.alt = takes_alternate(p, d, false);
+        p->alternate_count += d.alt ? 1 : 0;
         return post(p, d);
     }
     unsigned long long cap = 0;
     if (int rc = capture_id(p->st[RS], &cap)) return rc;
     d.express = cap == 0 && p->cap_id[slot] == 0 && pipe_idle(p);
     p->express_count += d.express ? 1 : 0;
+    d.alt = takes_alternate(p, d, cap != 0 || p->cap_id[slot] != 0);
+    p->alternate_count += d.alt ? 1 : 0;
     for (int r = 0; r < 4; ++r)
         if (int rc = role_enqueue(p, r, d, cap)) return rc;
     p->cap_id[slot] = 0;
@@ -529,6 +597,7 @@ static int submit_one(sage_pipe* p, const int32_t* seeds, uint64_t key, float* o
 }
 
 extern "C" int64_t sage_pipe_express_count(const sage_pipe_t* p) { return p ? p->express_count : -1; }
+extern "C" int64_t sage_pipe_alternate_count(const sage_pipe_t* p) { return p ? p->alternate_count : -1; }
 
 // Forget every submit: the next `depth` submits find their workspaces free.  The caller has synchronised (or joined) everything
 // submitted before -- e.g. after a stream capture ended, before eager submission resumes on the same pipe.

@@ -565,7 +565,9 @@ class RolePipeline:
     stream; batch b+1 is gathered while batch b is contracted and batch b+2 is sampled, over `depth` workspaces.
     Bit-identical to TwoHopEngine.forward on the same (seeds, key).  `roles` maps the four roles onto streams:
     "SGDL" = four streams, "SGDD" = D and L share one, "SSSS" = one stream (= sage_forward2's launch order).
-    `priorities`: per distinct stream, 0 = default, -1 = high (HIP stream priority; the latency-bound roles).
+    `priorities`: per distinct stream, 0 = default, -1 = high (HIP stream priority); none named and four streams: S and L, the
+    latency-bound roles, are high.  While stage D is empty (the one-launch layer 1) and stream L outranks streams G and D, the native
+    pipe puts every odd batch's layer 1 on stream D's idle queue (`alternate_count`; SAGE_PIPE_G_ALT=0 / 1 forces it off / on).
     The reference has no counterpart (model.py:240-252 is one batch at a time on the host)."""
     _h = None          # the native pipe; a class default because __del__ also meets a pipe whose __init__ failed or never ran
 
@@ -583,7 +585,14 @@ class RolePipeline:
         for ch in roles:
             if ch not in names:
                 names.append(ch)
-        priorities = priorities or {}
+        # No priorities named: with four role streams the latency-bound roles S and L get HIP's high priority.  That is what lets the
+        # native pipe alternate layer 1 over streams G and D while stage D is empty (csrc/sage_pipe.hip, sage_pipe_alternate_count: it
+        # does so where stream L outranks both); name priorities, e.g. {"L": 0}, to have others
+        priorities = dict(priorities or ({"S": -1, "L": -1} if len(names) == 4 else {}))
+        # stream D then carries every odd batch's layer 1, so a priority asked for role G has to reach both of layer 1's streams; a
+        # priority named for D itself stands
+        if os.environ.get("SAGE_PIPE_G_ALT", "") != "0" and len(names) == 4 and "G" in priorities and "D" not in priorities:
+            priorities["D"] = priorities["G"]
         # Which hardware queue a NEW HIP stream lands on is the runtime's choice, and two role streams on one queue serialise (82-105 us per
         # forward instead of 59-90, seen for the second pipeline of a process).  So every pipeline of a process runs on the role streams
         # of the FIRST one with the same (device, role map, priorities) unless the caller hands in streams of its own or asks for new
@@ -693,6 +702,11 @@ class RolePipeline:
     def express_count(self):
         """Batches of this pipe that found it idle and were enqueued whole on stream L (csrc/sage_pipe.hip, "express lane")."""
         return int(native.lib().sage_pipe_express_count(self._h))
+
+    @property
+    def alternate_count(self):
+        """Batches of this pipe whose layer 1 was enqueued on stream D's idle queue (csrc/sage_pipe.hip, SAGE_PIPE_G_ALT=1)."""
+        return int(native.lib().sage_pipe_alternate_count(self._h))
 
     def fork(self, stream=None):
         """Every role stream waits for `stream` (default: the current one): inputs written there are ready."""

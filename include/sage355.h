@@ -569,8 +569,9 @@ int sage_pipe_destroy(sage_pipe_t* p);
 int sage_pipe_update_weights(sage_pipe_t* p, const float* w1, const float* w2, const void* w1_prepared);
 /* One batch: seeds int32[batch] and out float[batch, h2] must stay valid until the batch has left stream L. */
 int sage_pipe_submit(sage_pipe_t* p, const int32_t* seeds, uint64_t key, float* out, int64_t ldo);
-/* sage_pipe_submit + two caller-owned hipEvent_t (gather_events[0], [1]) that the layer-1 gather launch on stream G carries as its own
- * start / stop events (column-sliced and phase-sliced layer 1; left unrecorded where the gather stage launches nothing). */
+/* sage_pipe_submit + two caller-owned hipEvent_t (gather_events[0], [1]) that the layer-1 gather launch carries as its own
+ * start / stop events on whichever stream it takes (stream G, or stream D for an odd batch of the alternating placement below; column-sliced
+ * and phase-sliced layer 1; left unrecorded where the gather stage launches nothing). */
 int sage_pipe_submit_profiled(sage_pipe_t* p, const int32_t* seeds, uint64_t key, float* out, int64_t ldo,
                               void* const* gather_events);
 /* n batches from one host loop: batch i reads seeds + i*seed_stride (elements), keys_host[i] (HOST array) and
@@ -595,6 +596,15 @@ int sage_pipe_flush(sage_pipe_t* p);
  * once).  Same kernels and workspace, bit-identical results; never inside a stream capture; needs four distinct role streams;
  * SAGE_PIPE_EXPRESS=0 (environment, read once) turns it off.  Returns how many batches of this pipe took it so far (-1: NULL pipe). */
 int64_t sage_pipe_express_count(const sage_pipe_t* p);
+/* Alternating layer-1 streams (additive, ABI 9).  While stage D launches nothing (the one-launch layer 1, the gather-only form), role
+ * G's calls for every odd batch -- counted from the last reset -- go to stream D's idle queue instead of stream G's: consecutive
+ * layer-1 launches are then ordered by their data alone and the ~10 us between two launches of one queue close.  Same kernels, events,
+ * workspaces and arguments, bit-identical results; never inside a stream capture or for an express batch; needs four distinct role
+ * streams.  Taken when stream L was created with a HIGHER priority than streams G and D (hipStreamCreateWithPriority; layer 2 must be
+ * able to claim the CUs a retiring layer-1 launch frees before the next launch's blocks do: with equal priorities the placement is
+ * 4-5 us per forward slower, not faster); SAGE_PIPE_G_ALT=0 / 1 (environment, read once) forces it off / on.
+ * Returns how many batches of this pipe had their layer 1 on stream D so far (-1: NULL pipe). */
+int64_t sage_pipe_alternate_count(const sage_pipe_t* p);
 
 /* ---------------------------------------------------------------------------
  * Classifier head (ABI 9): SupervisedGraphSage's scores, CrossEntropyLoss and the three gradients that follow
