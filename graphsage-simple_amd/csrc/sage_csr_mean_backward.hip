@@ -19,6 +19,11 @@
 // Arithmetic of a row (its bits depend on nothing else): p_c = fma(w_x, g_x, ...fma(w_x0, g_x0, 0)) over chunk c's entries in
 // stored order; S = 0 + p_0 + p_1 + ...; S = fma(w_u, g_u, S) if extra_u; grad_table[r] = S.  Every term is ONE fma, in the
 // chunk pass and in the fall-back alike (sum_weighted is the only place that forms a term).
+//
+// GROUPED instantiations (sage_csr_mean_backward_grouped): the gradient of an embedding read as embed[index[v]] through the
+// forward.  The caller's rectangular CSR has one row per EMBEDDING row and lists, for every node that reads it, that node's
+// transposed entries and then the node itself if it joined its own mean.  So the row count (groups) is separate from the source
+// count (nodes) that clamps ids into grad_out and w, and the row kernel's own self term is off: the self entries are in the list.
 #include "sage_csr_common.h"
 
 namespace {
@@ -127,19 +132,20 @@ __device__ inline void sum_weighted(const int32_t* __restrict__ col_t, int64_t b
 }
 
 // 4. one wave per item (row, chunk): partials[item] := the chunk's weighted sum
-template <int VEC>
+template <int VEC, bool GROUPED>
 __global__ __launch_bounds__(256) void bwd_chunk_kernel(const int64_t* __restrict__ rowptr_t, const int32_t* __restrict__ col_t,
                                                         int64_t num_nodes, const int32_t* __restrict__ nodes, int n,
                                                         const float* __restrict__ w, const float* __restrict__ g, int64_t ldg, int dim,
                                                         const int64_t* __restrict__ off, const int64_t* __restrict__ carry, int nb,
-                                                        int64_t cap, const int32_t* __restrict__ item_row, float* __restrict__ partials) {
+                                                        int64_t cap, const int32_t* __restrict__ item_row, float* __restrict__ partials,
+                                                        int64_t num_src) {
     using V = typename VecT<VEC>::type;
     const int lane = sage_lane();
     const int64_t wave = (int64_t)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     const int64_t nwaves = (int64_t)((gridDim.x * blockDim.x) >> 6);
     const int64_t items = min(carry[nb], cap);
     const int64_t total = rowptr_t[num_nodes];
-    const int last_row = (int)num_nodes - 1;
+    const int last_row = (int)(GROUPED ? num_src : num_nodes) - 1;      // GROUPED: num_nodes counts the rows (groups), num_src the nodes
     for (int64_t i = wave; i < items; i += nwaves) {
         // as in the forward: an entry counts only if it names a row whose chunk range fits the workspace and holds i
         const int r = __builtin_amdgcn_readfirstlane(item_row[i]);
@@ -165,18 +171,18 @@ __global__ __launch_bounds__(256) void bwd_chunk_kernel(const int64_t* __restric
 }
 
 // 5. one wave per row of grad_table
-template <int VEC>
+template <int VEC, bool GROUPED>
 __global__ __launch_bounds__(256) void bwd_row_kernel(const int64_t* __restrict__ rowptr_t, const int32_t* __restrict__ col_t,
                                                       int64_t num_nodes, const int32_t* __restrict__ nodes, int n,
                                                       const float* __restrict__ w, const int32_t* __restrict__ flag,
                                                       const float* __restrict__ g, int64_t ldg, int dim,
                                                       const int64_t* __restrict__ off, int64_t cap, const float* __restrict__ partials,
-                                                      float* __restrict__ grad_table, int64_t ldgt) {
+                                                      float* __restrict__ grad_table, int64_t ldgt, int64_t num_src) {
     using V = typename VecT<VEC>::type;
     const int lane = sage_lane();
     const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
     const int nwaves = (int)((gridDim.x * blockDim.x) >> 6);
-    const int last_row = (int)num_nodes - 1;
+    const int last_row = (int)(GROUPED ? num_src : num_nodes) - 1;      // as in bwd_chunk_kernel
     const int64_t total = rowptr_t[num_nodes];
     for (int r = wave; r < n; r += nwaves) {
         int32_t u;
@@ -188,7 +194,7 @@ __global__ __launch_bounds__(256) void bwd_row_kernel(const int64_t* __restrict_
         const int64_t k = long_chunks(e - b);
         const int64_t o = k > 0 ? uniform64(off[r]) : 0;
         const bool split = k > 0 && o + k <= cap;        // the chunk pass summed this row's chunks
-        const bool extra = u >= 0 && __builtin_amdgcn_readfirstlane(flag[max(u, 0)]) != 0;
+        const bool extra = !GROUPED && u >= 0 && __builtin_amdgcn_readfirstlane(flag[max(u, 0)]) != 0;   // GROUPED: the list holds the self entries
         const float wu = extra ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(w[u]))) : 0.f;
         for (int cb = 0; cb < dim; cb += kWave * VEC) {
             const int c0 = cb + lane * VEC;
@@ -223,28 +229,12 @@ extern "C" size_t sage_csr_mean_backward_workspace_bytes(int64_t num_nodes, int3
     return bwd_layout(num_nodes, n, max_edges, dim, &L) ? L.total : 0;
 }
 
-extern "C" int sage_csr_mean_backward(const int64_t* rowptr, const int32_t* col, const int64_t* rowptr_t, const int32_t* col_t,
-                                      int64_t num_nodes, const int32_t* nodes, int32_t n, int64_t max_edges, const float* grad_out,
-                                      int64_t ldg, int32_t dim, int32_t self_loop, float* grad_table, int64_t ldgt, void* workspace,
-                                      size_t workspace_bytes, sage_stream_t stream) {
-    // shapes first, then pointers: a bad shape is reported as such whatever the pointers are
-    SAGE_REQUIRE(num_nodes >= 0 && num_nodes < (1ll << 31), "csr_mean_backward: num_nodes = %lld", (long long)num_nodes);
-    SAGE_REQUIRE(n >= 0 && (nodes || n <= num_nodes), "csr_mean_backward: n = %d rows for %lld nodes without a node list", n,
-                 (long long)num_nodes);
-    SAGE_REQUIRE(max_edges >= 0, "csr_mean_backward: max_edges = %lld", (long long)max_edges);
-    SAGE_REQUIRE(dim >= 1 && ldg >= dim && ldgt >= dim, "csr_mean_backward: dim = %d, ldg = %lld, ldgt = %lld", dim, (long long)ldg,
-                 (long long)ldgt);
-    SAGE_REQUIRE(self_loop == 0 || self_loop == 1, "csr_mean_backward: self_loop = %d", self_loop);
-    SAGE_REQUIRE(rowptr && col && rowptr_t && col_t && grad_out && grad_table, "csr_mean_backward: NULL array");
-    BwdLayout L;
-    SAGE_REQUIRE(bwd_layout(num_nodes, n, max_edges, dim, &L), "csr_mean_backward: n = %d, max_edges = %lld, dim = %d out of range", n,
-                 (long long)max_edges, dim);
-    if (workspace_bytes < L.total || !workspace) {
-        sage_set_error("csr_mean_backward: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
-        return SAGE_ENOSPACE;
-    }
-    SAGE_REQUIRE(sage_aligned(workspace, 256), "csr_mean_backward: workspace not 256-byte aligned");
-    if (n == 0) return SAGE_OK;
+// Launches a-c on the forward CSR, then 1-5 on the rows of (rowptr_t, col_t): the num_nodes transposed rows, or with `grouped` the
+// num_rows rows of the grouped list.  Arguments are validated by the entries.
+static int bwd_launch(const int64_t* rowptr, const int32_t* col, const int64_t* rowptr_t, const int32_t* col_t, int64_t num_nodes,
+                      int64_t num_rows, bool grouped, const int32_t* nodes, int32_t n, int64_t max_edges, const float* grad_out, int64_t ldg,
+                      int32_t dim, int32_t self_loop, float* grad_table, int64_t ldgt, void* workspace, const BwdLayout& L,
+                      sage_stream_t stream) {
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
     int64_t* off = (int64_t*)(ws + L.off);
@@ -269,31 +259,90 @@ extern "C" int sage_csr_mean_backward(const int64_t* rowptr, const int32_t* col,
         SAGE_CHECK_LAUNCH("bwd_weight_kernel");
     }
 
-    hipLaunchKernelGGL(csr_count_kernel, dim3(nb), dim3(kCountThreads), 0, st, rowptr_t, num_nodes, nodes, n, off, carry);
+    hipLaunchKernelGGL(csr_count_kernel, dim3(nb), dim3(kCountThreads), 0, st, rowptr_t, num_rows, nodes, n, off, carry);
     SAGE_CHECK_LAUNCH("csr_count_kernel");
     hipLaunchKernelGGL(csr_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, carry, nb);
     SAGE_CHECK_LAUNCH("csr_carry_kernel");
-    hipLaunchKernelGGL(csr_expand_kernel, dim3(sage_cdiv(n, 256)), dim3(256), 0, st, rowptr_t, num_nodes, nodes, n, off, carry, L.cap, item_row);
+    hipLaunchKernelGGL(csr_expand_kernel, dim3(sage_cdiv(n, 256)), dim3(256), 0, st, rowptr_t, num_rows, nodes, n, off, carry, L.cap, item_row);
     SAGE_CHECK_LAUNCH("csr_expand_kernel");
 
     const bool vec4 = (dim % 4 == 0) && (ldg % 4 == 0) && (ldgt % 4 == 0) && sage_aligned(grad_out, 16) && sage_aligned(grad_table, 16);
     if (L.cap > 0) {
         const int blocks = (int)std::min<int64_t>((L.cap + 3) / 4, kNumCU * 8);
-        if (vec4)
-            hipLaunchKernelGGL(bwd_chunk_kernel<4>, dim3(blocks), dim3(256), 0, st, rowptr_t, col_t, num_nodes, nodes, n, w, grad_out, ldg, dim,
-                               off, carry, nb, L.cap, item_row, partials);
-        else
-            hipLaunchKernelGGL(bwd_chunk_kernel<1>, dim3(blocks), dim3(256), 0, st, rowptr_t, col_t, num_nodes, nodes, n, w, grad_out, ldg, dim,
-                               off, carry, nb, L.cap, item_row, partials);
+#define SAGE_BWD_CHUNK(VEC, GROUPED)                                                                                                    \
+    hipLaunchKernelGGL((bwd_chunk_kernel<VEC, GROUPED>), dim3(blocks), dim3(256), 0, st, rowptr_t, col_t, num_rows, nodes, n, w, grad_out, ldg, \
+                       dim, off, carry, nb, L.cap, item_row, partials, num_nodes)
+        if (grouped) { if (vec4) SAGE_BWD_CHUNK(4, true); else SAGE_BWD_CHUNK(1, true); }
+        else { if (vec4) SAGE_BWD_CHUNK(4, false); else SAGE_BWD_CHUNK(1, false); }
+#undef SAGE_BWD_CHUNK
         SAGE_CHECK_LAUNCH("bwd_chunk_kernel");
     }
     const int blocks = std::min(sage_cdiv(n, 4), kNumCU * 8);
-    if (vec4)
-        hipLaunchKernelGGL(bwd_row_kernel<4>, dim3(blocks), dim3(256), 0, st, rowptr_t, col_t, num_nodes, nodes, n, w, flag, grad_out, ldg, dim,
-                           off, L.cap, partials, grad_table, ldgt);
-    else
-        hipLaunchKernelGGL(bwd_row_kernel<1>, dim3(blocks), dim3(256), 0, st, rowptr_t, col_t, num_nodes, nodes, n, w, flag, grad_out, ldg, dim,
-                           off, L.cap, partials, grad_table, ldgt);
+#define SAGE_BWD_ROW(VEC, GROUPED)                                                                                                        \
+    hipLaunchKernelGGL((bwd_row_kernel<VEC, GROUPED>), dim3(blocks), dim3(256), 0, st, rowptr_t, col_t, num_rows, nodes, n, w, flag, grad_out, ldg, \
+                       dim, off, L.cap, partials, grad_table, ldgt, num_nodes)
+    if (grouped) { if (vec4) SAGE_BWD_ROW(4, true); else SAGE_BWD_ROW(1, true); }
+    else { if (vec4) SAGE_BWD_ROW(4, false); else SAGE_BWD_ROW(1, false); }
+#undef SAGE_BWD_ROW
     SAGE_CHECK_LAUNCH("bwd_row_kernel");
     return SAGE_OK;
+}
+
+extern "C" int sage_csr_mean_backward(const int64_t* rowptr, const int32_t* col, const int64_t* rowptr_t, const int32_t* col_t,
+                                      int64_t num_nodes, const int32_t* nodes, int32_t n, int64_t max_edges, const float* grad_out,
+                                      int64_t ldg, int32_t dim, int32_t self_loop, float* grad_table, int64_t ldgt, void* workspace,
+                                      size_t workspace_bytes, sage_stream_t stream) {
+    // shapes first, then pointers: a bad shape is reported as such whatever the pointers are
+    SAGE_REQUIRE(num_nodes >= 0 && num_nodes < (1ll << 31), "csr_mean_backward: num_nodes = %lld", (long long)num_nodes);
+    SAGE_REQUIRE(n >= 0 && (nodes || n <= num_nodes), "csr_mean_backward: n = %d rows for %lld nodes without a node list", n,
+                 (long long)num_nodes);
+    SAGE_REQUIRE(max_edges >= 0, "csr_mean_backward: max_edges = %lld", (long long)max_edges);
+    SAGE_REQUIRE(dim >= 1 && ldg >= dim && ldgt >= dim, "csr_mean_backward: dim = %d, ldg = %lld, ldgt = %lld", dim, (long long)ldg,
+                 (long long)ldgt);
+    SAGE_REQUIRE(self_loop == 0 || self_loop == 1, "csr_mean_backward: self_loop = %d", self_loop);
+    SAGE_REQUIRE(rowptr && col && rowptr_t && col_t && grad_out && grad_table, "csr_mean_backward: NULL array");
+    BwdLayout L;
+    SAGE_REQUIRE(bwd_layout(num_nodes, n, max_edges, dim, &L), "csr_mean_backward: n = %d, max_edges = %lld, dim = %d out of range", n,
+                 (long long)max_edges, dim);
+    if (workspace_bytes < L.total || !workspace) {
+        sage_set_error("csr_mean_backward: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
+        return SAGE_ENOSPACE;
+    }
+    SAGE_REQUIRE(sage_aligned(workspace, 256), "csr_mean_backward: workspace not 256-byte aligned");
+    if (n == 0) return SAGE_OK;
+    return bwd_launch(rowptr, col, rowptr_t, col_t, num_nodes, num_nodes, false, nodes, n, max_edges, grad_out, ldg, dim, self_loop, grad_table,
+                      ldgt, workspace, L, stream);
+}
+
+extern "C" size_t sage_csr_mean_backward_grouped_workspace_bytes(int64_t num_nodes, int64_t num_groups, int64_t max_edges, int32_t dim) {
+    BwdLayout L;
+    if (num_groups < 0 || num_groups >= (1ll << 31)) return 0;
+    return bwd_layout(num_nodes, (int32_t)num_groups, max_edges, dim, &L) ? L.total : 0;
+}
+
+extern "C" int sage_csr_mean_backward_grouped(const int64_t* rowptr, const int32_t* col, const int64_t* rowptr_gt, const int32_t* col_gt,
+                                              int64_t num_nodes, int64_t num_groups, int64_t max_edges, const float* grad_out, int64_t ldg,
+                                              int32_t dim, int32_t self_loop, float* grad_embed, int64_t ldge, void* workspace,
+                                              size_t workspace_bytes, sage_stream_t stream) {
+    // shapes first, then pointers, then the workspace: sage_csr_mean_backward's order
+    SAGE_REQUIRE(num_nodes >= 0 && num_nodes < (1ll << 31), "csr_mean_backward_grouped: num_nodes = %lld", (long long)num_nodes);
+    SAGE_REQUIRE(num_groups >= 0 && num_groups < (1ll << 31), "csr_mean_backward_grouped: num_groups = %lld", (long long)num_groups);
+    SAGE_REQUIRE(num_groups == 0 || num_nodes >= 1, "csr_mean_backward_grouped: num_nodes = 0 with %lld groups", (long long)num_groups);
+    SAGE_REQUIRE(max_edges >= 0, "csr_mean_backward_grouped: max_edges = %lld", (long long)max_edges);
+    SAGE_REQUIRE(dim >= 1 && ldg >= dim && ldge >= dim, "csr_mean_backward_grouped: dim = %d, ldg = %lld, ldge = %lld", dim, (long long)ldg,
+                 (long long)ldge);
+    SAGE_REQUIRE(self_loop == 0 || self_loop == 1, "csr_mean_backward_grouped: self_loop = %d", self_loop);
+    SAGE_REQUIRE(rowptr && col && rowptr_gt && col_gt && grad_out && grad_embed, "csr_mean_backward_grouped: NULL array");
+    BwdLayout L;
+    SAGE_REQUIRE(bwd_layout(num_nodes, (int32_t)num_groups, max_edges, dim, &L),
+                 "csr_mean_backward_grouped: num_groups = %lld, max_edges = %lld, dim = %d out of range", (long long)num_groups,
+                 (long long)max_edges, dim);
+    if (workspace_bytes < L.total || !workspace) {
+        sage_set_error("csr_mean_backward_grouped: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
+        return SAGE_ENOSPACE;
+    }
+    SAGE_REQUIRE(sage_aligned(workspace, 256), "csr_mean_backward_grouped: workspace not 256-byte aligned");
+    if (num_groups == 0) return SAGE_OK;
+    return bwd_launch(rowptr, col, rowptr_gt, col_gt, num_nodes, num_groups, true, nullptr, (int32_t)num_groups, max_edges, grad_out, ldg, dim,
+                      self_loop, grad_embed, ldge, workspace, L, stream);
 }

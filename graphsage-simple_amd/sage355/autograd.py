@@ -2,7 +2,8 @@
 
 The reference gets its gradients from stock autograd through mm / div / cat /
 relu; here each operator carries its own backward kernel
-(include/sage355.h: sage_linear_act_backward, sage_gather_mean_backward, sage_csr_mean_backward, sage_csr_sum).
+(include/sage355.h: sage_linear_act_backward, sage_gather_mean_backward, sage_csr_mean_backward, sage_csr_sum,
+sage_csr_mean_backward_grouped).
 """
 import torch
 
@@ -53,6 +54,24 @@ class _CsrMean(torch.autograd.Function):
             grad_table = torch.zeros((ctx.table_rows, grad_out.shape[1]), dtype=torch.float32, device=grad_out.device)
         ops.csr_mean_backward(rowptr, col, rowptr_t, col_t, grad_out, self_loop=ctx.self_loop, out=grad_table[:n])
         return grad_table, None, None, None, None, None, None
+
+
+class _CsrMeanIndexed(torch.autograd.Function):
+    """The whole-graph mean of embed[index] (ops.csr_mean(index=...)) and its adjoint with respect to the embedding
+    (ops.csr_mean_backward_grouped): no [N, dim] array in either direction."""
+
+    @staticmethod
+    def forward(ctx, embed, rowptr, col, index, grouped, any_nonempty):
+        out = ops.csr_mean(rowptr, col, embed, self_loop=grouped.self_loop, any_nonempty=any_nonempty, index=index)
+        ctx.save_for_backward(rowptr, col, grouped.rowptr, grouped.col)
+        ctx.self_loop = grouped.self_loop
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        rowptr, col, rowptr_gt, col_gt = ctx.saved_tensors
+        grouped = ops.GroupedTranspose(rowptr_gt, col_gt, ctx.self_loop)
+        return ops.csr_mean_backward_grouped(rowptr, col, grouped, grad_out.contiguous()), None, None, None, None, None
 
 
 class _EmbedRows(torch.autograd.Function):
@@ -152,16 +171,26 @@ def gather_mean(table, nbr, cnt, any_nonempty=None, slot_rows=None, self_row=Non
     return ops.gather_mean(table.detach(), nbr, cnt, slot_rows=slot_rows, self_row=self_row, any_nonempty=any_nonempty)
 
 
-def csr_mean(rowptr, col, table, transpose=None, self_loop=False, any_nonempty=None, nodes=None):
+def csr_mean(rowptr, col, table, transpose=None, self_loop=False, any_nonempty=None, nodes=None, index=None, grouped=None):
     """ops.csr_mean, differentiable with respect to `table` in its whole-graph form (row r = node r).  transpose: the pair
     ops.csr_transpose(rowptr, col) gives; built here if absent (a sort of the edges: build it once per graph and pass it).
     Rows of the table at or past num_nodes get a zero gradient.  With `nodes` and a table that requires grad this raises: a
     row subset with duplicates would need a scatter through duplicate rows; differentiate the whole graph and index the result.
-    Without grad mode, or with a table that needs no gradient, it is ops.csr_mean unchanged."""
+    Without grad mode, or with a table that needs no gradient, it is ops.csr_mean unchanged.
+    index: int32 [N] on the device -- `table` is a [K, dim] embedding read as table[index[v]] (ops.csr_mean(index=...)), and the
+    gradient is the embedding's, [K, dim] (ops.csr_mean_backward_grouped).  grouped: what
+    ops.csr_transpose_grouped(rowptr, col, index, K, self_loop) gives; built here if absent (build it once per graph and pass it).
+    Its flag must be `self_loop`."""
     if not (torch.is_grad_enabled() and table.requires_grad):
-        return ops.csr_mean(rowptr, col, table.detach(), nodes=nodes, self_loop=self_loop, any_nonempty=any_nonempty)
+        return ops.csr_mean(rowptr, col, table.detach(), nodes=nodes, self_loop=self_loop, any_nonempty=any_nonempty, index=index)
     if nodes is not None:
         raise native.SageError("autograd.csr_mean: the differentiable form is the whole-graph one (nodes=None)")
+    if index is not None:
+        if grouped is None:
+            grouped = ops.csr_transpose_grouped(rowptr, col, index, table.shape[0], self_loop)
+        if not isinstance(grouped, ops.GroupedTranspose) or grouped.self_loop != bool(self_loop) or grouped.rowptr.shape[0] != table.shape[0] + 1:
+            raise native.SageError("autograd.csr_mean: grouped was not built for this embedding and this self_loop")
+        return _CsrMeanIndexed.apply(table, rowptr, col, index, grouped, any_nonempty)
     rowptr_t, col_t = ops.csr_transpose(rowptr, col) if transpose is None else transpose
     return _CsrMean.apply(table, rowptr, col, rowptr_t, col_t, bool(self_loop), any_nonempty)
 

@@ -13,6 +13,11 @@ TRAINABLE embedding instead of the table, X = embed[index] with index[v] = v (1h
 layer-1 mean is then part of every step, its backward is sage_csr_mean_backward at width embed_dim on the inner graph, and the
 embedding's gradient is the sum of the rows of all nodes that share an embedding row: sage_csr_sum over the grouping of the
 index (ops.group_rows), dense and in a fixed order -- still no float atomics, still the same bits every run.
+
+fused_embed=True keeps X out of memory: the layer-1 mean reads embed[index[col[e]]] (sage_csr_mean_indexed, the same bits), the
+concat encoder's own row is read through the index, and the embedding's gradient is summed straight onto its rows
+(sage_csr_mean_backward_grouped over ops.csr_transpose_grouped's list) with no [N, embed_dim] gradient of X in between.  That sum
+adds the unfused path's terms in another association: equal to rounding, not to the bit, and as reproducible.
 """
 import time
 
@@ -44,10 +49,15 @@ class FullGraphTrainer:
     the reference's concat form feeds the raw one-hot feature row there instead (encoders.py:51-54), which would need a weight as
     wide as the one-hot: that form is not provided.  forward() is bit-identical to
     embed_all_nodes(table=embed[embed_index], act1=act1, nan_empty=False).  When embed_index is arange(N) with embed_rows == N, X is
-    the embedding itself: no copy, and its gradient needs no csr_sum."""
+    the embedding itself: no copy, and its gradient needs no csr_sum.
+
+    fused_embed (default False; read only with a non-identity embed_index): layer 1 reads the embedding through the index in
+    both directions and X = embed[embed_index] is never built (self.x stays None).  forward(), the loss and the gradients of w2
+    and w_cls keep their bits; the embedding's gradient is the same sum in another association (one flat sequence per embedding
+    row, csr_mean_backward_grouped; for concat plus csr_sum of the own-row part)."""
 
     def __init__(self, rowptr, col, table, num_classes, hidden1=50, hidden2=128, gcn=True, lr=0.7, agg_self_loop=False, head="native",
-                 rowptr_outer=None, col_outer=None, embed_index=None, embed_rows=None, embed_dim=None, act1=ACT_RELU):
+                 rowptr_outer=None, col_outer=None, embed_index=None, embed_rows=None, embed_dim=None, act1=ACT_RELU, fused_embed=False):
         if head not in ("torch", "native"):
             raise SageError(f"FullGraphTrainer: head = {head!r}, expected 'torch' or 'native'")
         if act1 not in (ACT_RELU, ACT_SIGMOID):
@@ -95,6 +105,7 @@ class FullGraphTrainer:
         self.rowptr2_t, self.col2_t = ops.csr_transpose(self.rowptr2, self.col2)
         self._ws = {}
         self.agg1 = self.h1_out = self.agg2 = self.out = self.x = None
+        self.fused = False
         if embed_index is None:
             self.refresh_table()
             return
@@ -104,7 +115,10 @@ class FullGraphTrainer:
         self.rowptr_t, self.col_t = (self.rowptr2_t, self.col2_t) if one_graph else ops.csr_transpose(rowptr, col)
         self.identity = int(embed_rows) == self.n and bool(torch.equal(embed_index, torch.arange(self.n, dtype=torch.int32, device=dev)))
         self.groups = None if self.identity else ops.group_rows(embed_index, int(embed_rows))
-        self._index64 = None if self.identity else embed_index.long()
+        self.fused = bool(fused_embed) and not self.identity
+        self._index64 = None if (self.identity or self.fused) else embed_index.long()
+        # the fused gradient's list: every embedding row's terms in one sequence (built once; it carries self_loop)
+        self.grouped_t = ops.csr_transpose_grouped(rowptr, col, embed_index, int(embed_rows), self.self_loop) if self.fused else None
 
     def parameters(self):
         return [self.w1, self.w2, self.w_cls] + ([self.embed] if self.embed is not None else [])
@@ -126,27 +140,34 @@ class FullGraphTrainer:
 
     def forward(self):
         """[N, h2] embeddings of every node; agg1, h1 and agg2 stay in the trainer for the backward."""
+        self_index = None
         if self.embed is None:
             tab = self.table[:self.n]
+        elif self.fused:                                     # X = embed[embed_index] is read through the index, never built
+            tab, self_index = self.embed, self.embed_index
+            ws = self._scratch("mean1", ops.csr_mean_workspace_bytes(self.n, self.col.numel(), self.d0))
+            self.agg1 = ops.csr_mean(self.rowptr, self.col, tab, self_loop=self.self_loop, out=self.agg1, workspace=ws, index=self_index)
         else:
             tab = self.x = self.embed if self.identity else torch.index_select(self.embed, 0, self._index64, out=self.x)
             ws = self._scratch("mean1", ops.csr_mean_workspace_bytes(self.n, self.col.numel(), self.d0))
             self.agg1 = ops.csr_mean(self.rowptr, self.col, tab, self_loop=self.self_loop, out=self.agg1, workspace=ws)
-        self.h1_out = ops.linear_act(self.agg1, self.w1, self.act1, self_tab=tab if self.concat else None, out=self.h1_out)
+        self.h1_out = ops.linear_act(self.agg1, self.w1, self.act1, self_tab=tab if self.concat else None,
+                                     self_index=self_index if self.concat else None, out=self.h1_out)
         ws = self._scratch("mean2", ops.csr_mean_workspace_bytes(self.n, self.col2.numel(), self.h1))
         self.agg2 = ops.csr_mean(self.rowptr2, self.col2, self.h1_out, self_loop=self.self_loop, out=self.agg2, workspace=ws)
         self.out = ops.linear_act(self.agg2, self.w2, ACT_RELU, self_tab=self.h1_out if self.concat else None, out=self.out)
         return self.out
 
-    def _linear_backward(self, self_tab, agg, weight, act, out, grad_out, need_x, what):
-        """sage_linear_act_backward_ws over all N rows of a layer with activation `act` -> (grad_weight, grad_x [N, kw] or None)."""
+    def _linear_backward(self, self_tab, agg, weight, act, out, grad_out, need_x, what, self_index=None):
+        """sage_linear_act_backward_ws over all N rows of a layer with activation `act` -> (grad_weight, grad_x [N, kw] or None).
+        self_index: row r's own row is self_tab[self_index[r]] (int32 [N], values inside self_tab)."""
         lib, P = native.lib(), native.ptr
         n, dim = agg.shape
         out_dim, kw = weight.shape
         g_w = torch.zeros_like(weight)
         g_x = torch.empty(n, kw, device=agg.device) if need_x else None
         ws = self._scratch("dw", lib.sage_linear_act_backward_workspace_bytes(n, dim, int(self_tab is not None), out_dim))
-        rc = lib.sage_linear_act_backward_ws(P(self_tab), self_tab.stride(0) if self_tab is not None else 0, None, P(agg), agg.stride(0), dim,
+        rc = lib.sage_linear_act_backward_ws(P(self_tab), self_tab.stride(0) if self_tab is not None else 0, P(self_index), P(agg), agg.stride(0), dim,
                                              P(weight), weight.stride(0), out_dim, int(act), P(out), out.stride(0), P(grad_out),
                                              grad_out.stride(0), n, None, P(g_w), g_w.stride(0), P(g_x), kw, None,
                                              P(ws), ws.numel(), native.stream_handle())
@@ -188,6 +209,20 @@ class FullGraphTrainer:
             g_w1, _ = self._linear_backward(self.table[:self.n] if self.concat else None, self.agg1, self.w1, self.act1, self.h1_out, g_h1,
                                             False, "linear_act_backward (layer 1)")
             return loss, (g_w1, g_w2, g_cls)
+        if self.fused:
+            # layer 1 through the index: dW1 and d[X_self | agg1]; every embedding row then sums its terms of the mean's adjoint in
+            # one sequence, and for concat the own-row parts of the nodes that read it (ascending node order) on top
+            g_w1, g_x1 = self._linear_backward(self.embed if self.concat else None, self.agg1, self.w1, self.act1, self.h1_out, g_h1, True,
+                                               "linear_act_backward (layer 1)", self_index=self.embed_index if self.concat else None)
+            ds = self.d0 if self.concat else 0
+            k = self.embed.shape[0]
+            ws = self._scratch("mean1_bwd", ops.csr_mean_backward_grouped_workspace_bytes(self.n, k, self.grouped_t.col.numel(), self.d0))
+            g_embed = ops.csr_mean_backward_grouped(self.rowptr, self.col, self.grouped_t, g_x1[:, ds:], workspace=ws)
+            if self.concat:
+                rowptr_g, col_g = self.groups
+                ws = self._scratch("embed_sum", ops.csr_sum_workspace_bytes(k, self.n, self.d0))
+                g_embed += ops.csr_sum(rowptr_g, col_g, g_x1[:, :ds], workspace=ws)
+            return loss, (g_w1, g_w2, g_cls, g_embed)
         # layer 1 with its input's gradient: dW1 and d[X_self | agg1]; the mean's adjoint on the inner graph gives dX
         g_w1, g_x1 = self._linear_backward(self.x if self.concat else None, self.agg1, self.w1, self.act1, self.h1_out, g_h1, True,
                                            "linear_act_backward (layer 1)")
@@ -233,7 +268,7 @@ def degree_index(rowptr):
 
 
 def run_full_graph_training(graph, feat_data, labels, num_classes, seed=1, steps=100, lr=0.7, hidden1=50, hidden2=128, gcn=True,
-                            agg_self_loop=False, head="native", initializer="None", embed_dim=100):
+                            agg_self_loop=False, head="native", initializer="None", embed_dim=100, fused_embed=False):
     """run_model (model.py:184-259) with full neighbourhoods: the same 10 / 10 / 80 split of np.random.permutation
     (model.py:229-235), ONE step per epoch over the whole training set, `steps` epochs.
     initializer: "None" -- the frozen table feat_data, ReLU at both layers; "1hot" -- a trainable embedding row per node, ReLU;
@@ -241,6 +276,7 @@ def run_full_graph_training(graph, feat_data, labels, num_classes, seed=1, steps
     last two and may be None.  embed_dim is the embedding's width; its default is the reference's --feature_dim default.  The
     reference itself overrides that width for these two initializers with the one-hot's (N and max degree + 1, model.py:209-212)
     because its loader hands the one-hot in as the feature table: an accident of the loader, not copied here.
+    fused_embed: FullGraphTrainer's flag (it changes something for "node_degree" only: the 1hot index is the identity).
     -> dict(f1_micro, f1_macro, mean_step_time, losses, trainer), as train.run_engine_training."""
     from sklearn.metrics import f1_score
     if initializer not in ("None", "1hot", "node_degree"):
@@ -259,7 +295,7 @@ def run_full_graph_training(graph, feat_data, labels, num_classes, seed=1, steps
         index, k = one_hot_index(n, dev) if initializer == "1hot" else degree_index(rowptr)
         tr = FullGraphTrainer(rowptr, col, None, num_classes, hidden1, hidden2, gcn=gcn, lr=lr, agg_self_loop=agg_self_loop, head=head,
                               embed_index=index, embed_rows=k, embed_dim=embed_dim,
-                              act1=ACT_SIGMOID if initializer == "node_degree" else ACT_RELU)
+                              act1=ACT_SIGMOID if initializer == "node_degree" else ACT_RELU, fused_embed=fused_embed)
     labels_dev = torch.as_tensor(np.asarray(labels).reshape(-1), dtype=torch.int64).to(dev)
     ids = torch.as_tensor(train.astype(np.int32)).to(dev)
     tgt = labels_dev[ids.long()]

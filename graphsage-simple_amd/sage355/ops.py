@@ -4,6 +4,8 @@ Each function checks device / dtype / contiguity on the host -- a kernel that
 walks a bad pointer can take the whole GPU node down -- then passes raw device
 pointers to libsage355.  All work is enqueued on torch's current stream.
 """
+import collections
+
 import torch
 
 from . import native
@@ -278,10 +280,13 @@ def csr_mean_workspace_bytes(n, max_edges, dim):
     return int(native.lib().sage_csr_mean_workspace_bytes(int(n), int(max_edges), int(dim)))
 
 
-def csr_mean(rowptr, col, table, nodes=None, self_loop=False, any_nonempty=None, out=None, max_edges=None, workspace=None):
+def csr_mean(rowptr, col, table, nodes=None, self_loop=False, any_nonempty=None, out=None, max_edges=None, workspace=None, index=None):
     """aggregators.py:47-48 (num_sample=None) + 52-74 from the CSR: [n, dim] mean over every neighbour of each node
     (row r is node nodes[r], or node r without `nodes`).  max_edges: upper bound on the edges of the selected rows, default
-    len(col) (exact for distinct rows; a smaller bound only costs speed).  workspace: a uint8 device tensor to reuse."""
+    len(col) (exact for distinct rows; a smaller bound only costs speed).  workspace: a uint8 device tensor to reuse.
+    index: int32 [num_nodes] on the device -- `table` is then a [K, dim] embedding and node v's row is table[index[v]]
+    (aggregators.py:68-71; sage_csr_mean_indexed): the bits of csr_mean(table[index]) without that [num_nodes, dim] array.  An
+    index value outside [0, K) is clamped, not refused: check the index where it is built."""
     _need_gpu()
     _chk(rowptr, torch.int64, "rowptr", 1)
     _chk(col, torch.int32, "col", 1)
@@ -289,7 +294,11 @@ def csr_mean(rowptr, col, table, nodes=None, self_loop=False, any_nonempty=None,
     num_nodes = rowptr.shape[0] - 1
     if num_nodes < 0:
         raise native.SageError("csr_mean: rowptr is empty")
-    if table.shape[0] < max(num_nodes, 1):
+    if index is not None:
+        _chk(index, torch.int32, "index", 1)
+        if index.shape[0] != num_nodes or table.shape[0] < 1:
+            raise native.SageError(f"csr_mean: index has {index.shape[0]} entries for {num_nodes} nodes, the embedding {table.shape[0]} rows")
+    elif table.shape[0] < max(num_nodes, 1):
         raise native.SageError(f"csr_mean: table has {table.shape[0]} rows for {num_nodes} nodes")
     if nodes is not None:
         _chk(nodes, torch.int32, "nodes", 1)
@@ -312,6 +321,15 @@ def csr_mean(rowptr, col, table, nodes=None, self_loop=False, any_nonempty=None,
         raise native.SageError(f"csr_mean: n = {n}, max_edges = {max_edges}, dim = {dim} out of range")
     if workspace is None or workspace.numel() < need:
         workspace = torch.empty(need, dtype=torch.uint8, device=table.device)
+    if index is not None:
+        if index.numel() == 0:
+            index = torch.zeros(1, dtype=torch.int32, device=table.device)
+        rc = native.lib().sage_csr_mean_indexed(native.ptr(rowptr), native.ptr(col), num_nodes, native.ptr(nodes), n, max_edges,
+                                                native.ptr(index), native.ptr(table), table.shape[0], ld, dim, 1 if self_loop else 0,
+                                                native.ptr(any_nonempty), native.ptr(out), ldo, native.ptr(workspace), workspace.numel(),
+                                                native.stream_handle())
+        native.check(rc, "csr_mean_indexed")
+        return out
     rc = native.lib().sage_csr_mean(native.ptr(rowptr), native.ptr(col), num_nodes, native.ptr(nodes), n, max_edges,
                                     native.ptr(table), table.shape[0], ld, dim, 1 if self_loop else 0, native.ptr(any_nonempty),
                                     native.ptr(out), ldo, native.ptr(workspace), workspace.numel(), native.stream_handle())
@@ -393,6 +411,101 @@ def csr_mean_backward(rowptr, col, rowptr_t, col_t, grad_out, nodes=None, self_l
                                              native.ptr(nodes), n, max_edges, native.ptr(grad_out), ldg, dim, 1 if self_loop else 0,
                                              native.ptr(out), ldgt, native.ptr(workspace), workspace.numel(), native.stream_handle())
     native.check(rc, "csr_mean_backward")
+    return out
+
+
+GroupedTranspose = collections.namedtuple("GroupedTranspose", "rowptr col self_loop")
+
+
+def csr_transpose_grouped(rowptr, col, index, num_groups, self_loop=False):
+    """GroupedTranspose(rowptr_gt int64 [K + 1], col_gt int32 [E + S], self_loop) -- what csr_mean_backward_grouped sums over for
+    an embedding [K = num_groups, dim] read as embed[index[v]] through csr_mean(..., index=index).  Row k lists, for every node u
+    with index[u] == k in ascending u, the entries of row u of the transpose (csr_transpose's order) and then u itself if u joins
+    its own mean (self_loop and u not an entry of its own row): S such self entries in all.  Torch ops on the tensors' own device,
+    CPU or GPU (the transpose, then ONE stable sort by (index[owner], owner) of the transposed entries with the self entries
+    appended); built once per graph, like csr_transpose and group_rows.  Raises for an index value outside [0, K), a node id
+    outside the graph and len(index) != N.  The flag travels with the list: the backward cannot be run with another one."""
+    if not isinstance(index, torch.Tensor) or index.dim() != 1 or index.dtype not in (torch.int32, torch.int64):
+        raise native.SageError("csr_transpose_grouped: index must be a 1-d int32 / int64 tensor")
+    rowptr_t, col_t = csr_transpose(rowptr, col)                       # checks rowptr and the ids in col
+    n, k = rowptr.shape[0] - 1, int(num_groups)
+    dev = col_t.device
+    if index.shape[0] != n or index.device != dev:
+        raise native.SageError(f"csr_transpose_grouped: index has {index.shape[0]} entries on {index.device} for {n} nodes on {dev}")
+    if k < 0 or k >= (1 << 31):
+        raise native.SageError(f"csr_transpose_grouped: num_groups = {k}")
+    idx = index.to(torch.int64)
+    if n > 0:
+        lo, hi = int(idx.min()), int(idx.max())
+        if lo < 0 or hi >= k:
+            raise native.SageError(f"csr_transpose_grouped: index {lo if lo < 0 else hi} outside [0, {k})")
+    nodes = torch.arange(n, dtype=torch.int64, device=dev)
+    owner = torch.repeat_interleave(nodes, rowptr_t[1:] - rowptr_t[:-1])           # col_t's rows: ascending already
+    entry = col_t.to(torch.int64)
+    if self_loop and n > 0:
+        own = torch.zeros(n, dtype=torch.bool, device=dev)
+        own[owner[entry == owner]] = True                                           # u is an entry of its own row
+        selfs = nodes[~own]
+        owner, entry = torch.cat([owner, selfs]), torch.cat([entry, selfs])         # appended: stable keeps them last in their node
+    order = torch.sort(idx[owner] * max(n, 1) + owner, stable=True).indices
+    col_gt = entry[order].to(torch.int32)
+    rowptr_gt = torch.zeros(k + 1, dtype=torch.int64, device=dev)
+    if k > 0 and owner.numel() > 0:
+        rowptr_gt[1:] = torch.cumsum(torch.bincount(idx[owner], minlength=k), 0)
+    return GroupedTranspose(rowptr_gt, col_gt, bool(self_loop))
+
+
+def csr_mean_backward_grouped_workspace_bytes(num_nodes, num_groups, max_edges, dim):
+    """Bytes of the workspace sage_csr_mean_backward_grouped needs (host arithmetic; 0 = shape out of range)."""
+    return int(native.lib().sage_csr_mean_backward_grouped_workspace_bytes(int(num_nodes), int(num_groups), int(max_edges), int(dim)))
+
+
+def csr_mean_backward_grouped(rowptr, col, grouped, grad_out, out=None, max_edges=None, workspace=None):
+    """The adjoint of csr_mean(rowptr, col, embed, index=index) (every node) with respect to `embed`: [K, dim], with no
+    [num_nodes, dim] intermediate.  grouped = csr_transpose_grouped(rowptr, col, index, K, self_loop): it carries the flag.
+    grad_out [num_nodes, dim], by node id.  The result is stored, not accumulated; an embedding row nobody reads is zeros.
+    max_edges: upper bound on the list's entries, default len(grouped.col) (a smaller bound only costs speed).  workspace: a
+    uint8 device tensor to reuse."""
+    _need_gpu()
+    if not isinstance(grouped, GroupedTranspose):
+        raise native.SageError("csr_mean_backward_grouped: grouped must be what csr_transpose_grouped returns")
+    _chk(rowptr, torch.int64, "rowptr", 1)
+    _chk(col, torch.int32, "col", 1)
+    rowptr_gt, col_gt = _chk(grouped.rowptr, torch.int64, "grouped.rowptr", 1), _chk(grouped.col, torch.int32, "grouped.col", 1)
+    grad_out, ldg = _row_major(grad_out, "grad_out")
+    num_nodes, k = rowptr.shape[0] - 1, rowptr_gt.shape[0] - 1
+    if num_nodes < 0 or k < 0:
+        raise native.SageError("csr_mean_backward_grouped: a row pointer array is empty")
+    if not col.numel() <= col_gt.numel() <= col.numel() + num_nodes:
+        raise native.SageError("csr_mean_backward_grouped: the grouped list does not have the graph's shape")
+    if grad_out.shape[0] < num_nodes:
+        raise native.SageError(f"csr_mean_backward_grouped: grad_out has {grad_out.shape[0]} rows for {num_nodes} nodes")
+    dim = grad_out.shape[1]
+    if out is None:
+        out = torch.empty((k, dim), dtype=torch.float32, device=grad_out.device)
+    out, ldge = _row_major(out, "out")
+    if out.shape[0] < k or out.shape[1] != dim:
+        raise native.SageError(f"csr_mean_backward_grouped: out is {tuple(out.shape)}, expected ({k}, {dim})")
+    if k == 0:
+        return out
+    if num_nodes == 0:                                    # no node reads any row
+        out[:k].zero_()
+        return out
+    if col.numel() == 0:                                  # an empty tensor may have no storage address: the kernels read none of it
+        col = torch.zeros(1, dtype=torch.int32, device=grad_out.device)
+    if col_gt.numel() == 0:
+        col_gt = torch.zeros(1, dtype=torch.int32, device=grad_out.device)
+    max_edges = grouped.col.numel() if max_edges is None else int(max_edges)
+    need = csr_mean_backward_grouped_workspace_bytes(num_nodes, k, max_edges, dim)
+    if need == 0:
+        raise native.SageError(f"csr_mean_backward_grouped: K = {k}, max_edges = {max_edges}, dim = {dim} out of range")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=grad_out.device)
+    rc = native.lib().sage_csr_mean_backward_grouped(native.ptr(rowptr), native.ptr(col), native.ptr(rowptr_gt), native.ptr(col_gt),
+                                                     num_nodes, k, max_edges, native.ptr(grad_out), ldg, dim, 1 if grouped.self_loop else 0,
+                                                     native.ptr(out), ldge, native.ptr(workspace), workspace.numel(),
+                                                     native.stream_handle())
+    native.check(rc, "csr_mean_backward_grouped")
     return out
 
 

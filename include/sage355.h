@@ -184,6 +184,31 @@ int sage_csr_mean(const int64_t* rowptr, const int32_t* col, int64_t num_nodes,
                   float* out, int64_t ldo, void* workspace, size_t workspace_bytes, sage_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * sage_csr_mean_indexed (additive, ABI 9) -- sage_csr_mean with the lookup of
+ * aggregators.py:68-71 (embed_matrix = self.embed(indices), the 1hot /
+ * node_degree initializers of aggregators.py:30-31) inside the mean: the table
+ * is virtual,
+ *     T[v, :] = embed[clamp(index[clamp(v)]), :],   v a node id,
+ * index int32 [num_nodes], embed [embed_rows, dim] with leading dimension ld,
+ * and the result is sage_csr_mean(table = T, table_rows = num_nodes) BIT FOR
+ * BIT, without T ever being stored: the same chunks of SAGE_CSR_MEAN_CHUNK
+ * edges, the same launches, the same fall-back for a small max_edges, the same
+ * order of additions, the same any_nonempty rule.  Only the address of a row
+ * changes.  The set-union self term ("row v holds v") is decided on NODE ids,
+ * never on index values; the self row is embed[index[v]].
+ * Node ids are clamped into [0, num_nodes) before index[] is read and index
+ * values into [0, embed_rows) before embed[] is read: no read leaves either.
+ * Every other argument, the workspace (sage_csr_mean_workspace_bytes) and the
+ * order of validation are sage_csr_mean's; embed_rows in [1, 2^31).
+ * ------------------------------------------------------------------------- */
+int sage_csr_mean_indexed(const int64_t* rowptr, const int32_t* col, int64_t num_nodes,
+                          const int32_t* nodes /* nullable: row r is node r */, int32_t n, int64_t max_edges,
+                          const int32_t* index /* [num_nodes] */, const float* embed, int64_t embed_rows,
+                          int64_t ld, int32_t dim,
+                          int32_t self_loop, const int32_t* any_nonempty /* nullable */,
+                          float* out, int64_t ldo, void* workspace, size_t workspace_bytes, sage_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * sage_csr_mean_backward (additive, ABI 9) -- the adjoint of
  * sage_csr_mean(nodes = NULL, n = num_nodes) with respect to `table`.  With the
  * forward's own definitions
@@ -225,6 +250,45 @@ int sage_csr_mean_backward(const int64_t* rowptr, const int32_t* col,
                            const float* grad_out, int64_t ldg, int32_t dim, int32_t self_loop,
                            float* grad_table, int64_t ldgt,
                            void* workspace, size_t workspace_bytes, sage_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * sage_csr_mean_backward_grouped (additive, ABI 9) -- the adjoint of
+ * sage_csr_mean_indexed(nodes = NULL, n = num_nodes) with respect to `embed`:
+ * what autograd does behind aggregators.py:68-74 (the scatter of mask.mm's
+ * gradient through self.embed(indices)), for the whole graph and with no
+ * [num_nodes, dim] intermediate.  With w_v, extra_v of sage_csr_mean_backward,
+ * embedding row k receives ONE flat sequence of terms: for every node u with
+ * index[u] == k, in ascending u, the entries x of row u of the transposed CSR
+ * in stored order, each as fma(w_x, grad_out[x, :], acc), then u itself if
+ * extra_u.  The caller supplies that sequence as a RECTANGULAR CSR
+ * (rowptr_gt [num_groups + 1], col_gt: node ids, self entries included), built
+ * once per graph for one self_loop; self_loop here only enters the weights
+ * and must be the flag the list was built with.
+ *     grad_embed[k, :] = sum over e in [rowptr_gt[k], rowptr_gt[k+1]), e
+ *                        ascending, of w_x * grad_out[x, :], x = col_gt[e]
+ * The arithmetic is sage_csr_mean_backward's over these longer rows: every term
+ * one fma; rows longer than SAGE_CSR_MEAN_CHUNK terms are cut into chunks whose
+ * partials are stored and added in chunk order, shorter ones summed in place.
+ * grad_embed [num_groups, dim], leading dimension ldge, is STORED: an empty row
+ * is exact zeros; columns [dim, ldge) and rows at or past num_groups are not
+ * written.  No float atomics.  With index[v] = v and self_loop = 0 the result
+ * equals sage_csr_mean_backward's bit for bit.
+ * A wrong list gives wrong numbers, never an access out of range: ids from
+ * col_gt are clamped into [0, num_nodes), row pointers into
+ * [0, rowptr_gt[num_groups]] and made non-decreasing (col_gt holds at least
+ * rowptr_gt[num_groups] entries).  max_edges bounds rowptr_gt[num_groups] and
+ * sizes the workspace; a bound that is too small costs speed only.
+ * num_groups in [0, 2^31), num_nodes >= 1 unless num_groups == 0, which
+ * returns SAGE_OK without a launch.  Workspace 256-byte aligned; the query
+ * returns 0 for a shape out of range.
+ * ------------------------------------------------------------------------- */
+size_t sage_csr_mean_backward_grouped_workspace_bytes(int64_t num_nodes, int64_t num_groups, int64_t max_edges, int32_t dim);
+int sage_csr_mean_backward_grouped(const int64_t* rowptr, const int32_t* col,
+                                   const int64_t* rowptr_gt, const int32_t* col_gt,
+                                   int64_t num_nodes, int64_t num_groups, int64_t max_edges,
+                                   const float* grad_out, int64_t ldg, int32_t dim, int32_t self_loop,
+                                   float* grad_embed, int64_t ldge,
+                                   void* workspace, size_t workspace_bytes, sage_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * sage_csr_sum (additive, ABI 9) -- the gradient of a shared embedding row.
