@@ -171,7 +171,9 @@ __device__ __forceinline__ void sample_block(
         bool won = false, selfwon = false, lfirst = false, sfirst = false;
         int slot = -1, sslot = -1, ls = -1, sls = -1;
         if (active && gl < c) ls = lds_insert(id, lfirst);
-        if (active && insert_self && gl == 0) sls = lds_insert(v, sfirst);
+        // A negative id cannot be a key (-1 marks an empty slot, in LDS and in the global table): such a v -- a bad id of the caller's,
+        // or what seed_map made of one -- is not inserted and its self_slot is -1, the wide kernel's rule (sage_sample_wide.hip)
+        if (active && insert_self && gl == 0 && v >= 0) sls = lds_insert(v, sfirst);
         if (lfirst) { slot = sage_hash_insert(f.keys, f.mask, id, won); lvals[ls] = slot; }
         if (sfirst) { sslot = sage_hash_insert(f.keys, f.mask, v, selfwon); lvals[sls] = sslot; }
         __syncthreads();

@@ -100,6 +100,8 @@ int sage_frontier_reset(const sage_frontier_t* f, int32_t first_row, sage_stream
  * v.  rows[slot] is valid once this call's kernels have completed (stream
  * order), so a consumer reads row = frontier->rows[nbr_slot[e]].
  * any_nonempty (nullable): set to 1 if any cnt[r] > 0 (reference NaN rule).
+ * Ids outside [0, num_nodes) are empty rows; rows at or past min(*n_dev, n)
+ * are not written; a negative v is never inserted; its self_slot is -1.
  * ------------------------------------------------------------------------- */
 int sage_sample_neighbors(const int64_t* rowptr, const int32_t* col, int64_t num_nodes,
                           const int32_t* nodes, int32_t n, const int32_t* n_dev,
