@@ -1,0 +1,288 @@
+// embed_grad: the gradient of a trainable embedding read through the SAMPLED layer-1 sets (aggregators.py:68-71 under the mean of
+// aggregators.py:60-74): the forward's nbr1 holds EMBEDDING rows (sage355.engine: col1 = index[col]), so
+//     grad_embed[e] = sum over the terms (p, j), t = row_order[p], j < c_t, nbr[t, j] == e, of grad_agg[t] * (1 / c_t)
+// sage_gather_mean_backward_ws (sage_backward_det.hip) computes the same sum with one lane group per destination row walking its
+// whole run.  With node_degree a few hundred rows share every term of the batch (1.5 M at config-3 size, power-law skewed): a handful
+// of lane groups would walk runs of 1e5 terms; and its terms come in ascending frontier ROW order, which is arbitrary (whichever
+// lane won the hash slot).  Here the terms are laid out in row_order POSITION, and after the sort the problem is sage_csr_sum with a
+// weight per term (sage_csr_sum.hip): long runs are cut into chunks of SAGE_CSR_MEAN_CHUNK terms summed by separate lane groups.
+//   1. expand   slot (p, j) -> key = the embedding row (clamped, as det_expand_kernel clamps) or the sentinel embed_rows
+//               (padding, dead rows), value = t; 1 / c_t per row
+//   2. sort     hipcub::DeviceRadixSort::SortPairs on the key bits that matter: stable, so (p, j) order survives inside a run
+//   3. rowptr   rowptr[e] = first position whose key is >= e (a binary search per embedding row): a CSR over the sorted list
+//   4-6. count, carry, expand (sage_csr_common.h): runs of more than one chunk get item entries and partial rows
+//   7. chunk    one lane group per item: partials[item] := the chunk's weighted sum
+//   8. rows     one lane group per embedding row: short runs summed in place, long ones = their partials in chunk order; STORE
+// Arithmetic of a row (its bits depend on nothing else): p_c = 0, then p_c = fma(g, w, p_c) over chunk c's terms in (p, j) order
+// (ONE rounding per term: a fused multiply-add, spelled fmaf so that no compiler flag decides); out = 0 + p_0 + p_1 + ... for a
+// run of more than one chunk, out = p_0 for any other.  No float atomics, no host synchronisation, no allocation.
+#include <hipcub/hipcub.hpp>
+
+#include "sage_csr_common.h"
+
+namespace {
+
+struct EmbedLayout {
+    size_t keys_in, keys_out, vals_in, vals_out, inv_c, rowptr, off, carry, item_row, partials, cub, total;
+    size_t cub_bytes;
+    int64_t cap, nblocks;
+    int slots, bits;
+};
+
+bool embed_layout(int32_t n, int32_t k, int64_t embed_rows, int32_t dim, EmbedLayout* L) {
+    if (n < 1 || k < 1 || dim < 1 || embed_rows < 1 || embed_rows >= (1ll << 31) || (int64_t)n * k >= (1ll << 31)) return false;
+    L->slots = n * k;
+    L->bits = 1;
+    while ((1ll << L->bits) <= embed_rows) ++L->bits;              // keys are in [0, embed_rows] (the sentinel included)
+    L->cap = csr_item_cap((int32_t)embed_rows, L->slots);          // every long run's chunks fit: at most slots terms in all
+    L->nblocks = (embed_rows + kCountTile - 1) / kCountTile;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = align256(off + std::max<size_t>(bytes, 1)); return o; };
+    L->keys_in = take((size_t)L->slots * 4);
+    L->keys_out = take((size_t)L->slots * 4);
+    L->vals_in = take((size_t)L->slots * 4);
+    L->vals_out = take((size_t)L->slots * 4);
+    L->inv_c = take((size_t)n * 4);
+    L->rowptr = take((size_t)(embed_rows + 1) * 8);
+    L->off = take((size_t)embed_rows * 8);
+    L->carry = take((size_t)(L->nblocks + 1) * 8);
+    L->item_row = take((size_t)L->cap * 4);
+    L->partials = take((size_t)L->cap * (size_t)dim * 4);
+    // The sort's temporary.  The library's own size query asks the runtime for the device's architecture, so it answers only where
+    // there is a device; the layout has to be host arithmetic.  Reserved here is a bound on what the sort partitions its temporary
+    // into: a second key and value array (8 bytes per slot), one look-back word per digit (256) and block of at least 512 slots
+    // (at most 4 bytes per slot at 8 bytes a word), digit histograms of a few KiB.  sage_embed_grad asks the library before it sorts
+    // and refuses (SAGE_ELAUNCH, nothing sorted) if it ever wanted more.
+    L->cub_bytes = (size_t)L->slots * 16 + 65536;
+    L->cub = take(L->cub_bytes);
+    L->total = off;
+    return true;
+}
+
+hipError_t sort_temp_bytes(int slots, int bits, size_t* bytes) {
+    *bytes = 0;
+    return hipcub::DeviceRadixSort::SortPairs(nullptr, *bytes, (const int32_t*)nullptr, (int32_t*)nullptr, (const int32_t*)nullptr,
+                                              (int32_t*)nullptr, slots, 0, bits, (hipStream_t)0);
+}
+
+// 1. one thread per slot, slots in row_order POSITION: slot p * k + j is term j of row t = row_order[p]
+__global__ __launch_bounds__(256) void embed_expand_kernel(const int32_t* __restrict__ nbr, const int32_t* __restrict__ cnt, int k, int n,
+                                                           const int32_t* __restrict__ n_dev, const int32_t* __restrict__ row_order,
+                                                           int embed_rows, int32_t* __restrict__ keys, int32_t* __restrict__ vals,
+                                                           float* __restrict__ inv_c) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= (int64_t)n * k) return;
+    int nn = n;
+    if (n_dev) nn = min(max(*n_dev, 0), n);
+    const int p = (int)(i / k), j = (int)(i - (int64_t)p * k);
+    const int t = row_order ? row_order[p] : p;
+    const bool live = t >= 0 && t < nn;                             // a dead row, or an entry of row_order that names no row
+    int key = embed_rows, c = 0;
+    if (live) {
+        c = min(max(cnt[t], 0), k);
+        if (j < c) key = min(max(nbr[(int64_t)t * k + j], 0), embed_rows - 1);      // clamped into the table, as the forward
+        if (j == 0) inv_c[t] = c > 0 ? 1.0f / (float)c : 0.f;
+    }
+    keys[i] = key;
+    vals[i] = live ? t : 0;
+}
+
+// 3. rowptr[e] = the first position of the sorted list whose key is >= e, e in [0, embed_rows]: rowptr[embed_rows] = the terms
+__global__ __launch_bounds__(256) void embed_rowptr_kernel(const int32_t* __restrict__ keys, int slots, int embed_rows,
+                                                           int64_t* __restrict__ rowptr) {
+    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e > embed_rows) return;
+    int lo = 0, hi = slots;
+    while (lo < hi) {
+        const int mid = lo + (hi - lo) / 2;
+        if (keys[mid] < e) lo = mid + 1;
+        else hi = mid;
+    }
+    rowptr[e] = lo;
+}
+
+using V4 = float4;
+
+// acc = fma(grad_agg[vals[i]], inv_c[vals[i]], acc) for i in [b, e), in order; 8 rows in flight, and the NEXT 8 row ids requested
+// before them, so that a trip of the walk is one memory round trip (ids -> rows would be two: measured 72 us for one 512-term chunk)
+__device__ inline void weighted_sum(const float* __restrict__ gagg, int64_t ldg, const int32_t* __restrict__ vals,
+                                    const float* __restrict__ inv_c, int64_t b, int64_t e, int c0, V4& acc) {
+    if (b >= e) return;
+    int r[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) r[u] = vals[min(b + u, e - 1)];
+    for (int64_t i = b; i < e; i += 8) {
+        int rn[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) rn[u] = vals[min(i + 8 + u, e - 1)];        // stays inside [b, e): the last trip re-reads e - 1
+        V4 g[8];
+        float w[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) {
+            w[u] = inv_c[r[u]];
+            g[u] = *reinterpret_cast<const V4*>(gagg + (int64_t)r[u] * ldg + c0);
+        }
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+            if (i + u < e) {
+                acc.x = fmaf(g[u].x, w[u], acc.x);
+                acc.y = fmaf(g[u].y, w[u], acc.y);
+                acc.z = fmaf(g[u].z, w[u], acc.z);
+                acc.w = fmaf(g[u].w, w[u], acc.w);
+            }
+#pragma unroll
+        for (int u = 0; u < 8; ++u) r[u] = rn[u];
+    }
+}
+
+// 7. LG lanes (x 16 B) per item (row, chunk): partials[item] := the chunk's weighted sum
+template <int LG>
+__global__ __launch_bounds__(256) void embed_chunk_kernel(const float* __restrict__ gagg, int64_t ldg, int dim, const int32_t* __restrict__ vals,
+                                                          const float* __restrict__ inv_c, const int64_t* __restrict__ rowptr, int embed_rows,
+                                                          const int64_t* __restrict__ off, const int64_t* __restrict__ carry, int nb,
+                                                          int64_t cap, const int32_t* __restrict__ item_row, float* __restrict__ partials) {
+    const int64_t gid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / LG, ngroups = ((int64_t)gridDim.x * blockDim.x) / LG;
+    const int gl = (int)(threadIdx.x % LG);
+    const int64_t items = min(carry[nb], cap);
+    const int64_t total = rowptr[embed_rows];
+    for (int64_t i = gid; i < items; i += ngroups) {
+        // an entry of a row that did not fit was never written: take one only if it names a row whose chunk range fits and holds i
+        const int r = item_row[i];
+        if (r < 0 || r >= embed_rows) continue;
+        int32_t v;
+        int64_t b, e;
+        row_span(rowptr, embed_rows, nullptr, r, total, v, b, e);
+        const int64_t kc = long_chunks(e - b), o = off[r];
+        if (kc == 0 || o + kc > cap || i < o || i >= o + kc) continue;
+        const int64_t cb = b + (i - o) * kChunk, ce = min(cb + kChunk, e);
+        for (int c0 = gl * 4; c0 < dim; c0 += LG * 4) {              // dim % 4 == 0 (host-checked)
+            V4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+            weighted_sum(gagg, ldg, vals, inv_c, cb, ce, c0, acc);
+            *reinterpret_cast<V4*>(partials + i * dim + c0) = acc;
+        }
+    }
+}
+
+// 8. LG lanes per embedding row
+template <int LG>
+__global__ __launch_bounds__(256) void embed_row_kernel(const float* __restrict__ gagg, int64_t ldg, int dim, const int32_t* __restrict__ vals,
+                                                        const float* __restrict__ inv_c, const int64_t* __restrict__ rowptr, int embed_rows,
+                                                        const int64_t* __restrict__ off, int64_t cap, const float* __restrict__ partials,
+                                                        float* __restrict__ out, int64_t ld) {
+    const int64_t gid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / LG, ngroups = ((int64_t)gridDim.x * blockDim.x) / LG;
+    const int gl = (int)(threadIdx.x % LG);
+    const int64_t total = rowptr[embed_rows];
+    for (int64_t r = gid; r < embed_rows; r += ngroups) {
+        int32_t v;
+        int64_t b, e;
+        row_span(rowptr, embed_rows, nullptr, (int)r, total, v, b, e);
+        const int64_t kc = long_chunks(e - b);
+        const int64_t o = kc > 0 ? off[r] : 0;
+        const bool split = kc > 0 && o + kc <= cap;                 // the chunk pass summed this row's chunks (always, with this cap)
+        for (int c0 = gl * 4; c0 < dim; c0 += LG * 4) {
+            V4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (split) {
+                for (int64_t c = 0; c < kc; ++c) vadd(s, *reinterpret_cast<const V4*>(partials + (o + c) * dim + c0));
+            } else if (kc == 0) {
+                weighted_sum(gagg, ldg, vals, inv_c, b, e, c0, s);
+            } else {                                                 // the chunk pass's sums, here: same operations, same order
+                for (int64_t c = 0; c < kc; ++c) {
+                    V4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+                    weighted_sum(gagg, ldg, vals, inv_c, b + c * kChunk, min(b + (c + 1) * kChunk, e), c0, p);
+                    vadd(s, p);
+                }
+            }
+            *reinterpret_cast<V4*>(out + r * ld + c0) = s;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" size_t sage_embed_grad_workspace_bytes(int32_t n, int32_t k, int64_t embed_rows, int32_t dim) {
+    if (n == 0 && k >= 1 && dim >= 1 && embed_rows >= 1) return 256;
+    EmbedLayout L;
+    return embed_layout(n, k, embed_rows, dim, &L) ? L.total : 0;
+}
+
+extern "C" int sage_embed_grad(const float* grad_agg, int64_t ldg, int32_t dim, const int32_t* nbr, const int32_t* cnt, int32_t k, int32_t n,
+                               const int32_t* n_dev, const int32_t* row_order, float* grad_embed, int64_t embed_rows, int64_t ld,
+                               void* workspace, size_t workspace_bytes, sage_stream_t stream) {
+    // shapes first, then pointers: a bad shape is reported as such whatever the pointers are
+    SAGE_REQUIRE(n >= 0 && k >= 1 && (int64_t)n * k < (1ll << 31), "embed_grad: n = %d, k = %d (n * k < 2^31)", n, k);
+    SAGE_REQUIRE(dim >= 4 && dim % 4 == 0, "embed_grad: dim = %d (rows of 16-byte pieces)", dim);
+    SAGE_REQUIRE(ldg >= dim && ldg % 4 == 0, "embed_grad: ldg = %lld", (long long)ldg);
+    SAGE_REQUIRE(ld >= dim && ld % 4 == 0, "embed_grad: ld = %lld", (long long)ld);
+    SAGE_REQUIRE(embed_rows >= 1 && embed_rows < (1ll << 31), "embed_grad: embed_rows = %lld", (long long)embed_rows);
+    SAGE_REQUIRE(grad_agg && nbr && cnt && grad_embed, "embed_grad: NULL array");
+    SAGE_REQUIRE(sage_aligned(grad_agg, 16) && sage_aligned(grad_embed, 16), "embed_grad: grad_agg / grad_embed not 16-byte aligned");
+    if (n == 0) return SAGE_OK;
+    EmbedLayout L;
+    SAGE_REQUIRE(embed_layout(n, k, embed_rows, dim, &L), "embed_grad: n = %d, k = %d, embed_rows = %lld, dim = %d out of range", n, k,
+                 (long long)embed_rows, dim);
+    if (workspace_bytes < L.total || !workspace) {
+        sage_set_error("embed_grad: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
+        return SAGE_ENOSPACE;
+    }
+    SAGE_REQUIRE(sage_aligned(workspace, 256), "embed_grad: workspace not 256-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    int32_t* keys_in = (int32_t*)(ws + L.keys_in);
+    int32_t* keys_out = (int32_t*)(ws + L.keys_out);
+    int32_t* vals_in = (int32_t*)(ws + L.vals_in);
+    int32_t* vals_out = (int32_t*)(ws + L.vals_out);
+    float* inv_c = (float*)(ws + L.inv_c);
+    int64_t* rowptr = (int64_t*)(ws + L.rowptr);
+    int64_t* off = (int64_t*)(ws + L.off);
+    int64_t* carry = (int64_t*)(ws + L.carry);
+    int32_t* item_row = (int32_t*)(ws + L.item_row);
+    float* partials = (float*)(ws + L.partials);
+    const int R = (int)embed_rows, nb = (int)L.nblocks;
+    size_t sort_bytes = 0;
+    if (sort_temp_bytes(L.slots, L.bits, &sort_bytes) != hipSuccess || sort_bytes > L.cub_bytes) {
+        sage_set_error("embed_grad: the radix sort asks for %zu bytes of temporary, %zu reserved", sort_bytes, L.cub_bytes);
+        return SAGE_ELAUNCH;
+    }
+
+    hipLaunchKernelGGL(embed_expand_kernel, dim3(sage_cdiv(L.slots, 256)), dim3(256), 0, st, nbr, cnt, k, n, n_dev, row_order, R, keys_in, vals_in,
+                       inv_c);
+    SAGE_CHECK_LAUNCH("embed_expand_kernel");
+    size_t cub_bytes = L.cub_bytes;
+    if (hipcub::DeviceRadixSort::SortPairs(ws + L.cub, cub_bytes, (const int32_t*)keys_in, keys_out, (const int32_t*)vals_in, vals_out, L.slots, 0,
+                                           L.bits, st) != hipSuccess) {
+        sage_set_error("embed_grad: radix sort failed");
+        return SAGE_ELAUNCH;
+    }
+    hipLaunchKernelGGL(embed_rowptr_kernel, dim3(sage_cdiv(embed_rows + 1, 256)), dim3(256), 0, st, (const int32_t*)keys_out, L.slots, R, rowptr);
+    SAGE_CHECK_LAUNCH("embed_rowptr_kernel");
+    hipLaunchKernelGGL(csr_count_kernel, dim3(nb), dim3(kCountThreads), 0, st, (const int64_t*)rowptr, embed_rows, (const int32_t*)nullptr, R, off,
+                       carry);
+    SAGE_CHECK_LAUNCH("csr_count_kernel");
+    hipLaunchKernelGGL(csr_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, carry, nb);
+    SAGE_CHECK_LAUNCH("csr_carry_kernel");
+    hipLaunchKernelGGL(csr_expand_kernel, dim3(sage_cdiv(R, 256)), dim3(256), 0, st, (const int64_t*)rowptr, embed_rows, (const int32_t*)nullptr, R,
+                       off, (const int64_t*)carry, L.cap, item_row);
+    SAGE_CHECK_LAUNCH("csr_expand_kernel");
+
+    // lanes of 16 bytes per term row: a whole row per trip up to 256 floats
+    const int lg = dim >= 256 ? 64 : dim >= 128 ? 32 : dim >= 64 ? 16 : 8;
+#define SAGE_EMBED_LG(KERNEL, BLOCKS, ...)                                                                          \
+    do {                                                                                                            \
+        if (lg == 64) hipLaunchKernelGGL(KERNEL<64>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);                   \
+        else if (lg == 32) hipLaunchKernelGGL(KERNEL<32>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);              \
+        else if (lg == 16) hipLaunchKernelGGL(KERNEL<16>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);              \
+        else hipLaunchKernelGGL(KERNEL<8>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);                             \
+    } while (0)
+    if (L.cap > 0) {
+        const int blocks = (int)std::min<int64_t>((L.cap * lg + 255) / 256, kNumCU * 8);
+        SAGE_EMBED_LG(embed_chunk_kernel, blocks, grad_agg, ldg, dim, (const int32_t*)vals_out, (const float*)inv_c, (const int64_t*)rowptr, R,
+                      (const int64_t*)off, (const int64_t*)carry, nb, L.cap, (const int32_t*)item_row, partials);
+        SAGE_CHECK_LAUNCH("embed_chunk_kernel");
+    }
+    const int blocks = (int)std::min<int64_t>((embed_rows * lg + 255) / 256, kNumCU * 8);
+    SAGE_EMBED_LG(embed_row_kernel, blocks, grad_agg, ldg, dim, (const int32_t*)vals_out, (const float*)inv_c, (const int64_t*)rowptr, R,
+                  (const int64_t*)off, L.cap, (const float*)partials, grad_embed, ld);
+#undef SAGE_EMBED_LG
+    SAGE_CHECK_LAUNCH("embed_row_kernel");
+    return SAGE_OK;
+}

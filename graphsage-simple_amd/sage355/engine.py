@@ -156,14 +156,21 @@ class _WeightCopies:
 class TwoHopEngine:
     def __init__(self, rowptr, col, table, w1, w2, k1, k2, concat=False, agg_self_loop=False, act1=ACT_RELU,
                  act2=ACT_RELU, nan_empty=True, fused=True, max_batch=4096, rowptr_outer=None, col_outer=None, relabel=None,
-                 prepare_weights=True, slice_major="auto", _parent=None):
+                 prepare_weights=True, slice_major="auto", embed_index=None, _parent=None):
         """rowptr/col: CSR of enc1.adj_lists (inner hop); rowptr_outer/col_outer: CSR of
         enc2.adj_lists when it differs (injected pre-sampled sets), default the same.
         w1 [h1, d0 | 2*d0], w2 [h2, h1 | 2*h1]: the Encoders' `weight` Parameters
         (referenced, not copied: an optimizer step is seen by the next forward).
         table: referenced too.  What the kernels read instead of the caller's tensors (renumbered / zero-padded / slice-major table
         copies, zero-padded weights) belongs to one _TableCopies and one _WeightCopies, built here and shared with siblings: re-derived
-        in place whenever the caller's version counters move; refresh_table() / invalidate_weights() for writes that do not move them."""
+        in place whenever the caller's version counters move; refresh_table() / invalidate_weights() for writes that do not move them.
+        embed_index (int32 [num_nodes], values in [0, R)): the featureless form (aggregators.py:68-71) -- `table` is then a trainable
+        embedding [R, d0] with R <= num_nodes, node v reads row embed_index[v].  The engine translates the INNER column array once
+        (col1 = embed_index[col]) and hands that to the library, so the sampled layer-1 sets hold embedding rows and every layer-1
+        kernel runs unchanged on the R-row table; frontier, hash and outer hop keep node ids.  gcn encoder without the aggregator's
+        self loop only, no relabel, d0 % 4 == 0, never a slice-major copy."""
+        if embed_index is not None:          # before anything touches the device: every refusal is reachable without one
+            slice_major = self._check_indexed(rowptr, table, embed_index, concat, agg_self_loop, relabel, slice_major, _parent)
         _need_gpu()
         self.rowptr1 = _chk(rowptr, torch.int64, "rowptr", 1)
         self.col1 = _chk(col, torch.int32, "col", 1)
@@ -175,7 +182,7 @@ class TwoHopEngine:
         if relabel not in (None, "degree"):
             raise native.SageError("relabel must be None or 'degree'")
         self.num_nodes = self.rowptr1.shape[0] - 1
-        if table.shape[0] < self.num_nodes:
+        if embed_index is None and table.shape[0] < self.num_nodes:
             raise native.SageError(f"table has {table.shape[0]} rows for {self.num_nodes} nodes")
         self.d0, self.h1, self.h2 = table.shape[1], w1.shape[0], w2.shape[0]
         mult = 2 if concat else 1
@@ -194,6 +201,15 @@ class TwoHopEngine:
             if relabel == "degree":
                 self._renumber_graph()
             self._wcopies = _WeightCopies(w1, w2, self.d0, concat)
+        # what the model struct names as col1: the inner column array itself, or its translation into embedding rows (built once,
+        # shared with siblings).  self.col1 / self.col2 stay node ids: the outer hop of a one-CSR engine keeps the untranslated array
+        self.embed_index, self.embed_rows, self._col1_model = None, None, self.col1
+        if embed_index is not None:
+            self.embed_index, self.embed_rows = _chk(embed_index, torch.int32, "embed_index", 1), int(table.shape[0])
+            if self._tables.table is not table:
+                raise native.SageError("embed_index: the embedding must be readable in place (leading dimension a multiple of 4 floats, "
+                                       "16-byte aligned): a private copy would go stale with every optimizer step")
+            self._col1_model = _parent._col1_model if _parent is not None else self.embed_index[self.col1.long()].contiguous()
         self.d0p, self.h1p = self._wcopies.d0p, self._wcopies.h1p
         self._w1prep = self._w1prep_key = None
         self.prepare_weights = bool(prepare_weights)
@@ -233,6 +249,38 @@ class TwoHopEngine:
         self.rowptr1, self.col1 = renumber(self.rowptr1, self.col1)
         self.rowptr2, self.col2 = (self.rowptr1, self.col1) if same else renumber(self.rowptr2, self.col2)
 
+    @staticmethod
+    def _check_indexed(rowptr, table, embed_index, concat, agg_self_loop, relabel, slice_major, parent):
+        """The shapes an indexed engine takes (host checks on tensors of any device); -> the slice_major it runs with (False)."""
+        if concat:
+            raise native.SageError("embed_index: the concat encoder is not provided on an indexed engine: its own row would need a "
+                                   "translated self_index (gcn encoder only)")
+        if agg_self_loop:
+            raise native.SageError("embed_index: the aggregator's self loop is not provided on an indexed engine: its set-union test "
+                                   "compares node ids with what are embedding rows here")
+        if relabel is not None:
+            raise native.SageError("embed_index: relabel is not provided on an indexed engine: it renumbers the rows of a node table, and "
+                                   "an embedding's rows are not nodes")
+        if slice_major is True:
+            raise native.SageError("embed_index: no slice-major copy on an indexed engine: its stride is num_nodes slices, the embedding "
+                                   "has R rows and changes every step")
+        if not isinstance(table, torch.Tensor) or table.dim() != 2 or not isinstance(rowptr, torch.Tensor) or rowptr.dim() != 1:
+            raise native.SageError("embed_index: table must be the 2-d embedding [R, d0], rowptr the 1-d row pointer")
+        rows, d0, num_nodes = table.shape[0], table.shape[1], rowptr.shape[0] - 1
+        if d0 % 4 != 0:
+            raise native.SageError(f"embed_index: embedding width {d0} is no multiple of 4: the kernels would read a zero-padded private "
+                                   "copy, stale after every optimizer step")
+        if rows < 1 or rows > num_nodes:
+            raise native.SageError(f"embed_index: the embedding has R = {rows} rows for {num_nodes} nodes (1 <= R <= num_nodes)")
+        if not isinstance(embed_index, torch.Tensor) or embed_index.dtype != torch.int32 or embed_index.dim() != 1 or \
+                embed_index.shape[0] != num_nodes:
+            raise native.SageError(f"embed_index: expected an int32 tensor [{num_nodes}] (one embedding row per node)")
+        if parent is None and num_nodes > 0:            # once, at construction (one synchronisation)
+            lo, hi = int(embed_index.min()), int(embed_index.max())
+            if lo < 0 or hi >= rows:
+                raise native.SageError(f"embed_index: value {lo if lo < 0 else hi} outside [0, R = {rows})")
+        return False
+
     def sibling(self):
         """Another engine over the SAME device graph / table / weights (shared, not copied) with a workspace, bf16 weight planes and
         model struct of its own: what every additional mini-batch in flight needs.  It holds this engine's _TableCopies and
@@ -240,7 +288,8 @@ class TwoHopEngine:
         return TwoHopEngine(self.rowptr1, self.col1, self._tables.src, self.w1, self.w2, self.k1, self.k2, concat=self.concat,
                             agg_self_loop=self.agg_self_loop, act1=self.act1, act2=self.act2, nan_empty=self.nan_empty, fused=self.fused,
                             max_batch=self.max_batch, rowptr_outer=self.rowptr2, col_outer=self.col2, relabel=None,
-                            prepare_weights=self.prepare_weights, _parent=self)
+                            prepare_weights=self.prepare_weights, slice_major=False if self.embed_index is not None else "auto",
+                            embed_index=self.embed_index, _parent=self)
 
     def _weights(self):
         """The weight tensors the kernels read: the caller's own, or zero-padded copies kept in step with them."""
@@ -314,7 +363,7 @@ class TwoHopEngine:
         if not (w1.is_contiguous() and w2.is_contiguous()):
             raise native.SageError("weights must be contiguous")
         self._model_c = native.Model(
-            self.rowptr1.data_ptr(), self.col1.data_ptr(), self.rowptr2.data_ptr(), self.col2.data_ptr(), self.num_nodes,
+            self.rowptr1.data_ptr(), self._col1_model.data_ptr(), self.rowptr2.data_ptr(), self.col2.data_ptr(), self.num_nodes,
             self.table.data_ptr(), self.table_ld, self.d0p, w1.data_ptr(), self.h1p, w2.data_ptr(), self.h2, self.k1, self.k2,
             int(self.concat), int(self.agg_self_loop), self.act1, self.act2, int(self.nan_empty), int(self.fused),
             int(self.max_batch))
@@ -446,13 +495,20 @@ class TwoHopEngine:
         return out
 
     # ---- backward of the last forward through the intermediates it left in the workspace (model.py:249) ----
-    def backward_weights(self, out, grad_out, need_w1=True):
+    def backward_weights(self, out, grad_out, need_w1=True, need_embed=False):
         """Gradients of (w1, w2), in the caller's shapes, of the LAST forward on this engine: `out` is what it returned
         ([B, h2]), grad_out = d loss / d out.  Autograd of the reference's expression (mm / relu / cat / div) from
         the engine's own intermediates -- nbr / cnt / row2 / h1 (and the layer-1 means when layer 1 ran split) are still in the
         workspace, the layer-2 means are re-gathered -- with the C-ABI backward kernels.  The table is frozen (model.py:214-215):
-        no gradient reaches it.  No host synchronisation: the frontier size never leaves the device."""
+        no gradient reaches it.  No host synchronisation: the frontier size never leaves the device.
+        need_embed (an indexed engine only; a plain one raises): -> (g_w1, g_w2, g_embed), g_embed [R, d0] the dense gradient of the
+        embedding, every row stored: g_h1 by the mean's backward over (row2, cnt2) -- (seed, slot) order -- then layer 1's grad_x on the
+        kept means, then sage_embed_grad over (nbr1, cnt1) in sage_row_order's order of s1_nodes: no atomics, the bits do not depend
+        on where the frontier's rows sit.  The weight gradients come from the same calls with or without it."""
         from . import ops
+        if need_embed and self.embed_index is None:
+            raise native.SageError("backward_weights: need_embed on an engine without embed_index: its table is frozen features, "
+                                   "no gradient reaches it")
         if getattr(self.w1, "_sage_identity", False):
             raise native.SageError("backward_weights: this engine serves a PRE-TRANSFORMED table (W1 is a declared identity): train with the "
                                    "plain engine on the raw features")
@@ -491,10 +547,10 @@ class TwoHopEngine:
         ws2 = scratch("ws_dw2", lib.sage_linear_act_backward_workspace_bytes(b, h1p, int(self.concat), self.h2))
         native.check(lib.sage_linear_act_backward_ws(P(h1) if self.concat else None, h1p, None, P(agg2), agg2.stride(0), h1p, P(w2p),
                                                      w2p.stride(0), self.h2, self.act2, P(out), out.stride(0), P(grad_out), grad_out.stride(0), b, None,
-                                                     P(g_w2p), g_w2p.stride(0), P(g_x2) if need_w1 else None, g_x2.stride(0), None,
+                                                     P(g_w2p), g_w2p.stride(0), P(g_x2) if (need_w1 or need_embed) else None, g_x2.stride(0), None,
                                                      P(ws2), ws2.numel(), st), "linear_act_backward (layer 2)")
         g_w1p = None
-        if need_w1:
+        if need_w1 or need_embed:
             # ---- layer 1 backward: only dW1 (the table is frozen), summed over the OUTER EDGES (sage_two_hop_grad_w1): the terms
             #      act1'(h1[t]) . g_agg2[r] / c_r (x) X1[t] come in (seed, slot) order, so neither grad_h1 (a scatter) nor an order of the
             #      frontier's arbitrarily placed rows is needed, and the bits do not depend on the layout.  agg1 from the workspace
@@ -508,6 +564,7 @@ class TwoHopEngine:
                     sc["agg1"] = torch.zeros(L.max_s1, d0p, device=dev)
                 ops.gather_mean(self.table, nbr1, cnt1, self_row=self_row1, any_nonempty=sc["any"], n_dev=sc["nlive"], out=sc["agg1"])
                 agg1 = sc["agg1"]
+        if need_w1:
             g_w1p = torch.zeros_like(w1p)
             ws1 = scratch("ws_dw1", lib.sage_two_hop_grad_w1_workspace_bytes(b, k2, d0p, int(self.concat), h1p))
             native.check(lib.sage_two_hop_grad_w1(P(g_x2), g_x2.stride(0), P(row2), P(cnt2), k2, P(self_row2), b, P(h1), h1p, h1p, self.act1,
@@ -520,7 +577,32 @@ class TwoHopEngine:
             g_w2 = torch.cat([g_w2p[:, c * h1p: c * h1p + self.h1] for c in range(mult)], 1)
         else:
             g_w1, g_w2 = g_w1p, g_w2p
-        return g_w1, g_w2
+        if not need_embed:
+            return g_w1, g_w2
+        # ---- the embedding's gradient (indexed engine: gcn encoder, no self loop, d0p == d0): every step an existing entry point but the last
+        n1, k1, rows = L.max_s1, self.k1, self.embed_rows
+        if sc.get("g_h1") is None:
+            sc["g_h1"] = torch.empty(n1, h1p, device=dev)
+            sc["g_agg1"] = torch.empty(n1, d0p, device=dev)
+            sc["order"] = torch.empty(n1, dtype=torch.int32, device=dev)
+        g_h1, g_agg1, order = sc["g_h1"], sc["g_agg1"], sc["order"]
+        # 1. d loss / d h1: the layer-2 mean's backward over the outer samples, terms in (seed, slot) order; rows [0, nlive) are stored
+        wsg = scratch("ws_gh1", lib.sage_gather_mean_backward_workspace_bytes(b, k2, n1))
+        native.check(lib.sage_gather_mean_backward_ws(P(g_x2), g_x2.stride(0), h1p, P(row2), P(cnt2), k2, b, None, None, None, P(g_h1), n1,
+                                                      P(sc["nlive"]), h1p, P(wsg), wsg.numel(), st), "gather_mean_backward_ws (layer 2)")
+        # 2. d loss / d layer-1 means: layer 1's grad_x on the kept means (per row: no order to fix, and without a weight gradient
+        #    the entry point takes no workspace)
+        native.check(lib.sage_linear_act_backward_ws(None, d0p, None, P(agg1), agg1.stride(0), d0p, P(w1p), w1p.stride(0), h1p, self.act1, P(h1),
+                                                     h1p, P(g_h1), h1p, n1, P(sc["nlive"]), None, w1p.stride(0), P(g_agg1), d0p, None,
+                                                     None, 0, st), "linear_act_backward (layer 1, grad_x)")
+        # 3. the frontier's rows by ascending node id, 4. the chunked sum over the sampled sets, which hold embedding rows
+        wso = scratch("ws_order", lib.sage_row_order_workspace_bytes(n1))
+        native.check(lib.sage_row_order(P(s1_nodes), n1, P(sc["nlive"]), 0, P(order), P(wso), wso.numel(), st), "row_order")
+        g_embed = torch.empty(rows, d0p, device=dev)
+        wse = scratch("ws_embed", lib.sage_embed_grad_workspace_bytes(n1, k1, rows, d0p))
+        native.check(lib.sage_embed_grad(P(g_agg1), d0p, d0p, P(nbr1), P(cnt1), k1, n1, P(sc["nlive"]), P(order), P(g_embed), rows, d0p,
+                                         P(wse), wse.numel(), st), "embed_grad")
+        return g_w1, g_w2, g_embed
 
     # ---- read-back of the last forward's intermediates (tests, parity gate, byte counting) ----
     def _view(self, off, count, dtype):
@@ -541,7 +623,8 @@ class TwoHopEngine:
         return view
 
     def intermediates(self):
-        """Sampled sets and layer-1 state of the LAST forward (synchronises)."""
+        """Sampled sets and layer-1 state of the LAST forward (synchronises).  On an indexed engine (embed_index) "nbr1" holds EMBEDDING
+        rows, embed_index of the sampled node ids, since the inner column array is translated; every other id is a node id."""
         ws = self._ws_views()
         torch.cuda.synchronize()
         first = self._last_batch if self.concat else 0

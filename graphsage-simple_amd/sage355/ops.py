@@ -572,6 +572,75 @@ def csr_sum(rowptr, col, table, out=None, max_edges=None, workspace=None):
     return out
 
 
+def row_order(nodes, n_dev=None, first_row=0, out=None, workspace=None):
+    """int32 [n]: the canonical order of a layer's rows (sage_row_order) -- rows [0, first_row) as they are, then the live rows by
+    ascending node id, dead rows (at or past *n_dev) last.  nodes: int32 [n] device tensor, the layer's node ids; n_dev: int32 [1]
+    device tensor or None.  What embed_grad and the reproducible weight gradient sum in."""
+    _need_gpu()
+    _chk(nodes, torch.int32, "nodes", 1)
+    n = nodes.shape[0]
+    if n < 1:
+        raise native.SageError("row_order: no rows")
+    if n_dev is not None:
+        _chk(n_dev, torch.int32, "n_dev")
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=nodes.device)
+    _chk(out, torch.int32, "out", 1)
+    if out.shape[0] < n:
+        raise native.SageError(f"row_order: out has {out.shape[0]} entries for {n} rows")
+    need = int(native.lib().sage_row_order_workspace_bytes(n))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=nodes.device)
+    native.check(native.lib().sage_row_order(native.ptr(nodes), n, native.ptr(n_dev), int(first_row), native.ptr(out), native.ptr(workspace),
+                                             workspace.numel(), native.stream_handle()), "row_order")
+    return out
+
+
+def embed_grad_workspace_bytes(n, k, embed_rows, dim):
+    """Bytes of the workspace sage_embed_grad needs (host arithmetic; 0 = shape out of range)."""
+    return int(native.lib().sage_embed_grad_workspace_bytes(int(n), int(k), int(embed_rows), int(dim)))
+
+
+def embed_grad(grad_agg, nbr, cnt, embed_rows, n_dev=None, row_order=None, out=None, workspace=None):
+    """[embed_rows, dim]: the gradient of an embedding whose rows the sampled sets (nbr [n, k], cnt [n]) name, from the gradient of the
+    sets' means grad_agg [n, dim]: row e is the sum of grad_agg[t] / c_t over the slots (t, j < c_t) with nbr[t, j] == e, the terms in
+    `row_order` position (sage_embed_grad: 512-term chunks, fixed order, no atomics).  Stored, not accumulated: a row nobody names is
+    zeros.  n_dev: int32 [1] live row count; row_order: int32 [n] from ops.row_order (None: rows as they lie); workspace: a uint8
+    device tensor to reuse."""
+    _need_gpu()
+    grad_agg, ldg = _row_major(grad_agg, "grad_agg")
+    _chk(nbr, torch.int32, "nbr", 2)
+    _chk(cnt, torch.int32, "cnt", 1)
+    n, k = nbr.shape
+    dim, rows = grad_agg.shape[1], int(embed_rows)
+    if grad_agg.shape[0] < n or cnt.shape[0] < n:
+        raise native.SageError(f"embed_grad: {n} sets, grad_agg has {grad_agg.shape[0]} rows, cnt {cnt.shape[0]} entries")
+    if n_dev is not None:
+        _chk(n_dev, torch.int32, "n_dev")
+    if row_order is not None:
+        _chk(row_order, torch.int32, "row_order", 1)
+        if row_order.shape[0] < n:
+            raise native.SageError(f"embed_grad: row_order has {row_order.shape[0]} entries for {n} rows")
+    if out is None:
+        out = torch.empty((rows, dim), dtype=torch.float32, device=grad_agg.device)
+    out, ld = _row_major(out, "out")
+    if out.shape[0] < rows or out.shape[1] != dim:
+        raise native.SageError(f"embed_grad: out is {tuple(out.shape)}, expected ({rows}, {dim})")
+    if n == 0:                                             # the library launches nothing then: the zeros are written here
+        out[:rows].zero_()
+        return out
+    need = embed_grad_workspace_bytes(n, k, rows, dim)
+    if need == 0:
+        raise native.SageError(f"embed_grad: n = {n}, k = {k}, embed_rows = {rows}, dim = {dim} out of range")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=grad_agg.device)
+    rc = native.lib().sage_embed_grad(native.ptr(grad_agg), ldg, dim, native.ptr(nbr), native.ptr(cnt), k, n, native.ptr(n_dev),
+                                      native.ptr(row_order), native.ptr(out), rows, ld, native.ptr(workspace), workspace.numel(),
+                                      native.stream_handle())
+    native.check(rc, "embed_grad")
+    return out
+
+
 def xent_head_supported(dim, num_classes):
     return bool(native.lib().sage_xent_head_supported(int(dim), int(num_classes)))
 

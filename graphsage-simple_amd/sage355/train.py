@@ -28,6 +28,7 @@ from torch.nn import init
 from . import dist
 from .aggregators import MeanAggregator
 from .encoders import Encoder
+from .native import ACT_RELU, ACT_SIGMOID
 
 
 class SupervisedGraphSage(nn.Module):
@@ -154,36 +155,60 @@ class EngineTrainer:
     table is frozen (model.py:214-215), so layer 1 needs no input gradient.  Gradients follow torch autograd of the reference's
     expression: d relu, d sigmoid, d mean = 1/|set| per member -- TwoHopEngine.backward_weights: sage_linear_act_backward_ws for
     layer 2, sage_two_hop_grad_w1 (the layer-1 weight gradient summed over the outer samples) for layer 1; no float atomics, two
-    runs of one schedule give the same bits."""
+    runs of one schedule give the same bits.
+
+    Featureless graphs (aggregators.py:68-71, --initializer 1hot / node_degree): table=None with embed_index int32 [N] (values in
+    [0, embed_rows)), embed_rows and embed_dim -- FullGraphTrainer's argument names and rules.  Layer 1 then reads the trainable
+    self.embed_weight [embed_rows, embed_dim] (drawn N(0, 1) as nn.Embedding's weight is, AFTER the three weights, which therefore start
+    as the frozen trainer's do for the same torch seed) through the index: the engine samples embedding rows (TwoHopEngine's
+    embed_index), parameters() and grads() gain a fourth entry, step() updates the embedding in place with the dense [embed_rows,
+    embed_dim] gradient of backward_weights(need_embed=True).  gcn encoder without the aggregator's self loop, no relabel,
+    embed_dim % 4 == 0; no captured step and no data-parallel step in this form.  act1: layer 1's activation (node_degree uses
+    sigmoid, encoders.py:58-59)."""
 
     def __init__(self, rowptr, col, table, num_classes, hidden1=50, hidden2=128, num_sample1=10, num_sample2=10, gcn=True, lr=0.7,
-                 max_batch=256, agg_self_loop=False, relabel=None, head="torch"):
+                 max_batch=256, agg_self_loop=False, relabel=None, head="torch", embed_index=None, embed_rows=None, embed_dim=None,
+                 act1=ACT_RELU):
         """head: "torch" -- the classifier, its loss and their gradients as stock torch ops (the default: its bits are the recorded
         w_cls trajectories); "native" -- one sage_xent_head call, its sums in an order fixed by the shape.  With the
         native head the loss and the classifier gradient that grads() returns live in buffers of the trainer, rewritten by its next call."""
         from . import native, ops
         if head not in ("torch", "native"):
             raise native.SageError(f"EngineTrainer: head = {head!r}, expected 'torch' or 'native'")
+        if act1 not in (ACT_RELU, ACT_SIGMOID):
+            raise native.SageError(f"EngineTrainer: act1 = {act1!r}, expected ACT_RELU or ACT_SIGMOID")
+        if embed_index is not None and table is not None:
+            raise native.SageError("EngineTrainer: table and embed_index are alternatives: layer 1 reads one of them")
+        if embed_index is not None:
+            if embed_rows is None or embed_dim is None or int(embed_rows) < 1 or int(embed_dim) < 1:
+                raise native.SageError(f"EngineTrainer: embed_rows = {embed_rows!r}, embed_dim = {embed_dim!r}")
+            if dist.world_size() > 1:
+                raise native.SageError("EngineTrainer: a trainable embedding is single-process in this build (its gradient is not all-reduced)")
         if head == "native" and not ops.xent_head_supported(hidden2, num_classes):
             raise native.SageError(f"EngineTrainer: head='native' has no kernel for hidden2 = {hidden2}, num_classes = {num_classes}")
         self.head = head
         from .engine import TwoHopEngine
-        dev = table.device
-        d0 = table.shape[1]
+        dev = table.device if embed_index is None else embed_index.device
+        d0 = table.shape[1] if embed_index is None else int(embed_dim)
         m = 1 if gcn else 2
         self.w1 = torch.empty(hidden1, m * d0, device=dev)
         self.w2 = torch.empty(hidden2, m * hidden1, device=dev)
         self.w_cls = torch.empty(num_classes, hidden2, device=dev)
         for w in (self.w1, self.w2, self.w_cls):
             init.xavier_uniform_(w)
+        self.embed_weight = None
+        if embed_index is not None:          # after the three weights: they start as the frozen trainer's do for the same torch seed
+            self.embed_weight = torch.empty(int(embed_rows), d0, device=dev)
+            init.normal_(self.embed_weight)
         self.lr = float(lr)
         self.concat = not gcn
         # data parallel: every rank starts from rank 0's weights.  BEFORE the engine is built: its constructor prepares the bf16
         # planes of W1 (and zero-padded copies of odd widths) and caches them under (data_ptr, _version), which a broadcast
         # through `.data` does not move -- ranks != 0 would run their first step on planes of their own initial W1 (ADVICE r2)
         dist.broadcast_params(self.parameters())
-        self.engine = TwoHopEngine(rowptr, col, table, self.w1, self.w2, num_sample1, num_sample2, concat=self.concat,
-                                   agg_self_loop=agg_self_loop, max_batch=max_batch, relabel=relabel)
+        self.engine = TwoHopEngine(rowptr, col, table if embed_index is None else self.embed_weight, self.w1, self.w2, num_sample1,
+                                   num_sample2, concat=self.concat, agg_self_loop=agg_self_loop, act1=act1, max_batch=max_batch,
+                                   relabel=relabel, embed_index=embed_index)
         self.engine.keep_means = True        # the backward reads the layer-1 means of the forward from the workspace
         self.engine.invalidate_weights()
         self._native, self._ops = native, ops
@@ -202,7 +227,11 @@ class EngineTrainer:
                       "workspace": torch.empty(self._ops.xent_head_workspace_bytes(rows, h2, c), dtype=torch.uint8, device=dev)}
 
     def parameters(self):
-        return [self.w1, self.w2, self.w_cls]
+        return [self.w1, self.w2, self.w_cls] + ([] if self.embed_weight is None else [self.embed_weight])
+
+    def _backward(self, out, g_out):
+        """The engine's gradients behind the classifier's: (g_w1, g_w2), and the embedding's where there is one."""
+        return self.engine.backward_weights(out, g_out, need_embed=self.embed_weight is not None)
 
     def embed(self, seeds, key=0):
         """[B, hidden2] embeddings (no grad): the evaluation forward."""
@@ -223,7 +252,8 @@ class EngineTrainer:
         return self._ops.xent_head(emb, self.w_cls, grads=False, pred=True, workspace=hd["workspace"], out={"pred": hd["pred"]})["pred"].clone()
 
     def grads(self, seeds, labels, key, global_batch=None):
-        """loss (device scalar) and the gradients of (w1, w2, w_cls) for one batch; nothing is updated.
+        """loss (device scalar) and the gradients of (w1, w2, w_cls) -- and of embed_weight, a fourth entry, on an embedding trainer --
+        for one batch; nothing is updated.
         global_batch: data parallel -- this rank holds a shard of a mini-batch of that many seeds; its loss is the SUM over its
         shard / global_batch, so that the SUM of the ranks' gradients is the full-batch gradient."""
         e = self.engine
@@ -243,10 +273,10 @@ class EngineTrainer:
             hd = self._head
             r = self._ops.xent_head(out, self.w_cls, labels, scale=1.0 / float(b if global_batch is None else global_batch),
                                     workspace=hd["workspace"], out=hd)
-            g_w1, g_w2 = e.backward_weights(out, r["grad_emb"])
+            g_w1, g_w2, *g_e = self._backward(out, r["grad_emb"])
             # eager: the caller may keep the loss of every step (run_engine_training does); queued: the captured step copies it at once
             loss = r["loss"][0]
-            return (loss if seeds is None else loss.clone()), (g_w1, g_w2, r["grad_w"])
+            return (loss if seeds is None else loss.clone()), (g_w1, g_w2, r["grad_w"], *g_e)
         # classifier + loss + their gradients: stock torch on the same stream (model.py:59-69)
         # The classifier's weight gradient is a [C, B] x [B, H2] product whose reduction runs over the BATCH: for B >= 1024 the BLAS behind
         # torch.mm may split it and add the pieces with atomics, and two runs of one schedule then differ in the last bits of w_cls (seen
@@ -263,14 +293,16 @@ class EngineTrainer:
         g_out = g_scores @ self.w_cls.detach()                              # [B, C] x [C, H2]: reduction over the classes
         g_cls = _sum_over_batch(g_scores, emb)                               # [C, B] x [B, H2]: reduction over the batch
         # both layers' weight gradients from the intermediates this forward left in the engine's workspace
-        g_w1, g_w2 = e.backward_weights(out, g_out)
-        return loss.detach(), (g_w1, g_w2, g_cls)
+        g_w1, g_w2, *g_e = self._backward(out, g_out)
+        return loss.detach(), (g_w1, g_w2, g_cls, *g_e)
 
     def step(self, seeds, labels, key, global_batch=None):
         """forward + backward + SGD; -> loss as a device scalar (reading it is the caller's only synchronisation).
         With torch.distributed initialised (one process per GPU, backend "nccl" = RCCL over xGMI) the three weight gradients
         travel in ONE flat all-reduce (SUM) per step, ~0.3 MB: latency bound, so one buffer and one call."""
-        loss, (g1, g2, gc) = self.grads(seeds, labels, key, global_batch)
+        loss, (g1, g2, gc, *ge) = self.grads(seeds, labels, key, global_batch)
+        if ge:
+            self.embed_weight.add_(ge[0], alpha=-self.lr)     # in place: the engine reads this very tensor at the next forward
         if dist.world_size() > 1:
             flat = torch.cat([g1.reshape(-1), g2.reshape(-1), gc.reshape(-1)])
             torch.distributed.all_reduce(flat, op=torch.distributed.ReduceOp.SUM)
@@ -291,6 +323,9 @@ class EngineTrainer:
         gathered by the ids at the cursor, the weight planes are re-prepared inside the graph after every update.
         -> the static device scalar that holds the last replayed step's loss."""
         e = self.engine
+        if self.embed_weight is not None:
+            raise self._native.SageError("capture_step: not provided for a trainable embedding in this build (its gradient chain allocates "
+                                         "scratch on first use and has not been captured)")
         if dist.world_size() > 1:
             raise self._native.SageError("capture_step: single-process only (the data-parallel step has a collective per step)")
         e.set_queue(seeds_ring, keys)
@@ -332,21 +367,35 @@ class EngineTrainer:
 
 
 def run_engine_training(graph, feat_data, labels, num_classes, seed=1, epochs=1, batch_size=128, ref_batching=False, lr=0.7,
-                        sample_seed=0, hidden1=50, hidden2=128, num_sample1=10, num_sample2=10, gcn=True, head="torch"):
+                        sample_seed=0, hidden1=50, hidden2=128, num_sample1=10, num_sample2=10, gcn=True, head="torch", initializer=None,
+                        embed_dim=100):
     """run_model (model.py:184-259) on the engine path: same split, shuffles, batching and optimiser as run_training above, every
-    step through EngineTrainer.  -> dict(f1_micro, f1_macro, mean_step_time, losses, trainer)."""
+    step through EngineTrainer.  -> dict(f1_micro, f1_macro, mean_step_time, losses, trainer).
+    initializer: None (or "None") -- the frozen table feat_data; "1hot" -- a trainable embedding row per node, ReLU; "node_degree" -- a
+    row per degree, SIGMOID at layer 1 (encoders.py:58-59).  feat_data is not read for the last two and may be None; embed_dim is
+    the embedding's width (the reference's --feature_dim default), a multiple of 4."""
     from sklearn.metrics import f1_score
+    from . import native
+    from .fullgraph import degree_index, one_hot_index
+    if initializer not in (None, "None", "1hot", "node_degree"):
+        raise native.SageError(f"run_engine_training: initializer = {initializer!r}, expected None, '1hot' or 'node_degree'")
     dev = torch.device("cuda")
     np.random.seed(seed)
     rowptr, col = graph.to(dev)
-    table = torch.as_tensor(feat_data, dtype=torch.float32).to(dev)
     n = graph.num_nodes
+    if initializer in (None, "None"):
+        table, embed_kwargs = torch.as_tensor(feat_data, dtype=torch.float32).to(dev), {}
+    else:
+        index, rows = one_hot_index(n, dev) if initializer == "1hot" else degree_index(rowptr)
+        table = None
+        embed_kwargs = dict(embed_index=index, embed_rows=rows, embed_dim=embed_dim,
+                            act1=ACT_SIGMOID if initializer == "node_degree" else ACT_RELU)
     rand_indices = np.random.permutation(n)
     val = rand_indices[int(0.1 * n):int(0.2 * n)]
     train = list(rand_indices[int(0.2 * n):])
     top = len(train) if ref_batching else batch_size
     tr = EngineTrainer(rowptr, col, table, num_classes, hidden1, hidden2, num_sample1, num_sample2, gcn=gcn, lr=lr, max_batch=max(top, len(val)),
-                       head=head)
+                       head=head, **embed_kwargs)
     labels_dev = torch.as_tensor(np.asarray(labels).reshape(-1), dtype=torch.int64).to(dev)
     shuffler = random.Random(seed)
     losses, key = [], int(sample_seed) << 20

@@ -325,6 +325,51 @@ int sage_csr_sum(const int64_t* rowptr, const int32_t* col, int64_t num_rows, in
                  void* workspace, size_t workspace_bytes, sage_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * sage_embed_grad (additive, ABI 9) -- the gradient of a trainable embedding
+ * read through the SAMPLED layer-1 sets: an engine whose inner column array is
+ * translated (col1 = index[col], table = embed [embed_rows, dim]) leaves
+ * EMBEDDING rows in nbr1, and the mean over a set (aggregators.py:60-74) hands
+ * every member 1 / c of the set's gradient:
+ *     grad_embed[e, :] = sum of grad_agg[t, :] * (1 / c_t) over the terms (p, j)
+ *                        with t = row_order[p] (p itself when row_order is
+ *                        NULL), t live, j < c_t = min(cnt[t], k), nbr[t, j] == e
+ * Live rows are t in [0, min(*n_dev, n)) (n_dev nullable); an entry of
+ * row_order outside them adds nothing.  Ids from nbr are clamped into
+ * [0, embed_rows) as sage_gather_mean_backward_ws clamps them.  A row that is
+ * a member of one set several times counts with its multiplicity.
+ * ORDER is part of the contract.  A row's terms are taken in ascending (p, j)
+ * and cut into consecutive chunks of SAGE_CSR_MEAN_CHUNK terms; each chunk is
+ * summed from zero in term order, every term entering as ONE fused multiply-add
+ * acc = fma(grad_agg[t, c], 1 / c_t, acc) (one rounding per term; 1 / c_t is
+ * the fp32 quotient); the chunk partials are added from zero in chunk order; a
+ * row of at most one chunk is its only partial.  So the bits depend on the
+ * inputs as sets and on row_order only -- with row_order = sage_row_order's
+ * output on the layer's node ids, not on where the frontier's rows sit -- and
+ * never on the grid or the number of CUs.  No float atomics.
+ * Every row in [0, embed_rows) of grad_embed is STORED, exact zeros where no
+ * term points: the caller zeroes nothing.  Not written: columns [dim, ld) and
+ * anything past row embed_rows.
+ * Inverted index per call in the caller's workspace (expand in row_order
+ * position -> stable radix sort by embedding row -> row pointer over the
+ * embedding rows -> sage_csr_sum's chunk split): no host synchronisation, no
+ * allocation.  Load balance is sage_csr_sum's: a row of 1e5 terms is summed by
+ * 200 lane groups, not walked by one.
+ * Limits: dim, ld, ldg multiples of 4 (ld, ldg >= dim), grad_agg / grad_embed
+ * 16-byte aligned, workspace 256-byte aligned, k >= 1, n * k < 2^31,
+ * 1 <= embed_rows < 2^31.  A bad argument returns SAGE_EINVAL with its name in
+ * sage_last_error, a short or missing workspace SAGE_ENOSPACE, both before any
+ * launch; n == 0 returns SAGE_OK without a launch (grad_embed is then left as
+ * it was).  The workspace query is host arithmetic (0 = shape out of range).
+ * ------------------------------------------------------------------------- */
+size_t sage_embed_grad_workspace_bytes(int32_t n, int32_t k, int64_t embed_rows, int32_t dim);
+int    sage_embed_grad(const float* grad_agg, int64_t ldg, int32_t dim,     /* [n, dim]: d loss / d layer-1 means        */
+                       const int32_t* nbr, const int32_t* cnt, int32_t k,   /* the forward's nbr1 / cnt1: EMBEDDING rows */
+                       int32_t n, const int32_t* n_dev,                     /* live rows = min(*n_dev, n); nullable      */
+                       const int32_t* row_order,                            /* sage_row_order's output; nullable = 0..n-1 */
+                       float* grad_embed, int64_t embed_rows, int64_t ld,   /* [embed_rows, dim], STORED                 */
+                       void* workspace, size_t workspace_bytes, sage_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * sage_linear_act --encoders.py:49-62 without materialising the concat:
  *     out[r, :] = act( W[:, 0:ds] . self(r) + W[:, ds:ds+dim] . agg[r, :] )
  * self(r) = self_tab[self_index ? self_index[r] : r, 0:dim]; ds = dim when
