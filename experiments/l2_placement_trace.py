@@ -41,7 +41,10 @@ for r in rows[1:]:
     last = max(last, r[1])
 # warm-up + timed region: the LAST phase of 100 .. 1000 forwards (the preheat phases before it hold thousands)
 cands = [ph for ph in phases if 100 * 4 <= len(ph) <= 1000 * 4]
-p = cands[-1] if cands else max(phases, key=len)
+# (no such phase: the preheat runs into the timed region, or the bench repeats it; then the LAST phase of at least 100 forwards, not
+# the longest one, which may be a preheat of its own that ends in a drained pipe)
+big = [ph for ph in phases if len(ph) >= 100 * 4]
+p = cands[-1] if cands else big[-1] if big else max(phases, key=len)
 print("phases (kernels): " + " ".join(str(len(ph)) for ph in phases if len(ph) >= 50))
 by = collections.defaultdict(list)
 queues = collections.defaultdict(collections.Counter)
@@ -77,3 +80,63 @@ t0 = S["G"][lo, 0]
 print("  timeline of four batches (us from G(b0) start):")
 for b in range(lo, lo + 4):
     print("   b=%d " % b + "  ".join(f"{k} {S[k][b, 0] - t0:7.1f}->{S[k][b, 1] - t0:7.1f}" for k in ("So", "Si", "G", "L")))
+
+# ---- round 11: which constraint binds each kernel start?  (dep_trace.py's idea for the four-kernel pipeline.)  A kernel can start once
+# every one of its constraints is met: the previous kernel of its queue has ended, its producer has ended, and for So the workspace
+# has been released by L(b - depth).  The LAST of them to be met is the binding one; the distance from it to the start is what the
+# hand-off (or the queue's boundary) cost.  The queue of a kernel is the one the trace names, so the table follows whatever cut of the
+# four streams the library made: Si in stream S's queue behind So, or in a layer-1 queue in front of G.
+depth = int(sys.argv[3]) if len(sys.argv) > 3 else 4
+ev = sorted((s, e, k, q, i) for k in ("So", "Si", "G", "L") for i, ((s, e), q) in enumerate(zip(by[k][-n:], [r[3] for r in p if r[2] == k][-n:])))
+prev_in_queue, last_of_queue = {}, {}
+for s, e, k, q, i in ev:
+    prev_in_queue[(k, i)] = last_of_queue.get(q)
+    last_of_queue[q] = (k, i, e / 1e3)
+Q = {(k, i): q for s, e, k, q, i in ev}
+producer = {"Si": "So", "G": "Si", "L": "G"}
+binding = {k: collections.Counter() for k in ("So", "Si", "G", "L")}
+slack = {k: collections.defaultdict(list) for k in ("So", "Si", "G", "L")}
+bound_by = {}
+for k in ("So", "Si", "G", "L"):
+    for b in range(lo, hi):
+        start = S[k][b, 0]
+        cons = {}
+        pq = prev_in_queue[(k, b)]
+        if pq:
+            cons["queue:%s(b%+d)" % (pq[0], pq[1] - b)] = pq[2]
+        if k in producer:
+            cons["producer:%s(b)" % producer[k]] = S[producer[k]][b, 1]
+        if k == "So" and b - depth >= 0:
+            cons["release:L(b-%d)" % depth] = S["L"][b - depth, 1]
+        name, t = max(cons.items(), key=lambda kv: kv[1])
+        binding[k][name] += 1
+        bound_by[(k, b)] = name
+        slack[k][name].append(start - t)
+print(f"last constraint met before each kernel start (batches {lo} .. {hi - 1}; depth {depth}): count, then start - constraint in us")
+for k in ("So", "Si", "G", "L"):
+    for name, c in binding[k].most_common():
+        print(f"  {k:2s} <- {name:18s} x{c:4d} ({100.0 * c / (hi - lo):5.1f} %)  {stat(slack[k][name])}")
+# a layer-1 start held by stream S's own chain: G(b) waited for Si(b), which waited for So(b), which waited for its queue (not the release)
+chain = sum(1 for b in range(lo, hi) if bound_by[("G", b)].startswith("producer:Si") and bound_by[("Si", b)].startswith(("queue:So", "producer:So"))
+            and bound_by[("So", b)].startswith("queue:"))
+print(f"  layer-1 starts whose last constraints lead back through Si(b) and So(b) to So(b)'s queue predecessor: {chain} of {hi - lo} ({100.0 * chain / (hi - lo):.1f} %)")
+print(f"  So(b+1) start - Si(b) end  {stat(S['So'][lo + 1:hi + 1, 0] - S['Si'][lo:hi, 1])}")
+print(f"  Si(b) start - So(b) end    {stat(S['Si'][lo:hi, 0] - S['So'][lo:hi, 1])}")
+print(f"  G(b) start - Si(b) end     {stat(S['G'][lo:hi, 0] - S['Si'][lo:hi, 1])}")
+print(f"  So(b) start - L(b-{depth}) end   {stat(S['So'][lo:hi, 0] - S['L'][lo - depth:hi - depth, 1])}")
+print(f"  L(b+1) start - L(b) end    {stat(S['L'][lo + 1:hi + 1, 0] - S['L'][lo:hi, 1])}")
+# each queue's busy time, and busy time plus the boundary in front of every kernel that followed its queue predecessor's end within
+# 30 us (a longer distance is a wait for data, not a boundary), as a share of the period
+period = (S["L"][hi - 1, 1] - S["L"][lo, 1]) / (hi - 1 - lo)
+busy, bound, kinds = collections.Counter(), collections.Counter(), collections.defaultdict(collections.Counter)
+for s, e, k, q, i in ev:
+    if lo <= i < hi:
+        busy[q] += (e - s) / 1e3
+        kinds[q][k] += 1
+        pq = prev_in_queue[(k, i)]
+        if pq and 0.0 < s / 1e3 - pq[2] < 30.0:
+            bound[q] += s / 1e3 - pq[2]
+print("  per queue, per batch of the pipe: busy us, busy + boundary us, share of the period")
+for q in sorted(busy):
+    what = " ".join(f"{k} x{c}" for k, c in sorted(kinds[q].items()))
+    print(f"   queue {q}: busy {busy[q] / (hi - lo):5.1f}  busy + boundary {(busy[q] + bound[q]) / (hi - lo):5.1f}  = {100.0 * (busy[q] + bound[q]) / (hi - lo) / period:5.1f} % of {period:.1f}   ({what})")

@@ -102,9 +102,20 @@ layer1_form_t layer1_form(const sage_model_t* m, const sage_ws_layout_t& L, cons
     return f;
 }
 
+bool layer2_is_fused(const sage_model_t* m) {
+    return m->fused && sage_layer_fused_supported(m->h1, m->h2, m->concat) && sage_aligned(m->w2, 16);
+}
+}  // namespace
+
+// Both hops are sampled by ONE launch for this model: the two sampling stages cannot be enqueued apart (the role pipeline asks)
+bool sage_forward2_sampler_is_fused(const sage_model_t* m) {
+    return layer2_is_fused(m) && sage_tunables().sample_fused != 0 && m->k1 <= 64 && m->k2 <= 64;
+}
+
+namespace {
 int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes, const int32_t* seeds, int32_t batch,
                   uint64_t seed, float* out, int64_t ldo, sage_stream_t stream, void* const* ev, int stages = SAGE_STAGE_ALL,
-                  void* tail_event = nullptr, void* const* gather_events = nullptr) {
+                  void* tail_event = nullptr, void* const* gather_events = nullptr, bool inner_with_layer1 = false) {
     if (int rc = check_model(m)) return rc;
     SAGE_REQUIRE(m->rowptr1 && m->col1 && m->rowptr2 && m->col2 && m->table && m->w1 && m->w2, "forward2: NULL model array");
     const bool queued = m->queue != nullptr;
@@ -161,8 +172,8 @@ int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes
     const bool split1 = form1.split1, gather_only1 = form1.gather_only1, phase1 = form1.phase1;
     // Layer 2 as a one-launch layer resolves hash slots itself, so both hops can be sampled by ONE launch (sage_sample.hip:
     // sample_fused_kernel).  The choice depends on the model only, so every call on a workspace agrees on who resolves the slots.
-    const bool fuse2 = m->fused && sage_layer_fused_supported(m->h1, m->h2, m->concat) && sage_aligned(m->w2, 16);
-    const bool sfused = fuse2 && sage_tunables().sample_fused != 0 && m->k1 <= 64 && m->k2 <= 64;
+    const bool fuse2 = layer2_is_fused(m);
+    const bool sfused = sage_forward2_sampler_is_fused(m);
 
     // What the launches below read and write, each described once.
     // Layer 1: rows [0, s1_count + first_row) of S1 gather from the feature table ...
@@ -284,7 +295,8 @@ int forward2_impl(const sage_model_t* m, void* workspace, size_t workspace_bytes
         if (int rc = run_stage(SAGE_STAGE_LAYER2, 8, nullptr, [&](sage_launch_events_t* e) {
                 // in a pipeline this launch runs beside the NEXT batch's layer 1: the block shape follows that kernel's form (sage_fused.hip)
                 if (fuse2) return sage_launch_layer_fused(table2, lists2, self2, contract2, sfused ? &resolve2 : nullptr, fin, st, e,
-                                                          phase1 ? SAGE_BESIDE_ONE_WAVE_LAYER1 : SAGE_BESIDE_ANYTHING);
+                                                          !phase1 ? SAGE_BESIDE_ANYTHING : inner_with_layer1 ? SAGE_BESIDE_LAYER1_AND_INNER_SAMPLER
+                                                                                                             : SAGE_BESIDE_ONE_WAVE_LAYER1);
                 if (int rc = sage_launch_gather_mean(table2, lists2, agg2, m->h1, SAGE_ACT_NONE, st)) return rc;
                 return sage_launch_linear_act(means2, lists2, self2, contract2, fin, st);
             }))
@@ -310,9 +322,10 @@ bool sage_forward2_contract1_is_empty(const sage_model_t* m, int32_t batch) {
 // A subset of the forward's launches with the seeds and the sampler key taken from the call (sage_pipe.hip: one call per role stream)
 int sage_forward2_launch_stages(const sage_model_t* m, void* workspace, size_t workspace_bytes, const int32_t* seeds, int32_t batch,
                                 uint64_t seed, float* out, int64_t ldo, int32_t stages, hipStream_t stream, void* tail_event,
-                                void* const* gather_events) {
+                                void* const* gather_events, bool inner_with_layer1) {
+    // inner_with_layer1: the caller enqueues this batch's inner sampler in front of its layer 1, in one queue (it decides layer 2's company)
     return forward2_impl(m, workspace, workspace_bytes, seeds, batch, seed, out, ldo, (sage_stream_t)stream, nullptr, stages, tail_event,
-                         gather_events);
+                         gather_events, inner_with_layer1);
 }
 
 extern "C" int sage_forward2_profiled(const sage_model_t* m, void* workspace, size_t workspace_bytes, const int32_t* seeds,

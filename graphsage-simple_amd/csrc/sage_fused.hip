@@ -462,6 +462,10 @@ constexpr int kTile16InflightOneTrip = 13;
 //    keeps a block of the next batch's launch off that CU, a 1024-thread block (4 x 128) needs two of the three gone.  That is the
 //    reasoning the forms were picked for measurement by; the trace of the shipped form does not isolate it, the
 //    A/B is what decides: 62.6-63.6 against 65.4-66.6 for the parent, config 4 87.4-89.5 against 92.7-95.1 (profiles/r09_ab.json).
+//  * Beside that layer 1 ALTERNATING over two queues with each batch's inner sampler in front of it (role pipeline, round 11,
+//    SAGE_BESIDE_LAYER1_AND_INNER_SAMPLER): 8 waves again.  Same box, five interleaved repetitions: 16 x 13 61.0-61.4, 8 x 7 51.3-51.6
+//    (profiles/r11_ab.json): two overlapping layer-1 launches and a sampler never leave the whole CU a 1024-thread block needs, and
+//    layer 2's queue was at 99.6 % of the period with every launch waiting for the one in front of it (profiles/r11_trace/).
 template <int KP, bool CONCAT>
 int launch_tile16(const FusedArgs& a, int waves, int inflight, hipStream_t st, sage_launch_events_t* ev) {
     constexpr int INFLIGHT = CONCAT ? SAGE_T16_INFLIGHT_CONCAT : SAGE_T16_INFLIGHT;

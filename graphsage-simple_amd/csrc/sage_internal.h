@@ -129,6 +129,8 @@ int sage_launch_linear_act(const sage_rows_t& agg, const sage_lists_t& rows, con
 enum sage_layer_company_t {
     SAGE_BESIDE_ANYTHING = 0,             // unknown, or persistent kernels that share their CUs (column-sliced gather, contraction): 512-thread blocks
     SAGE_BESIDE_ONE_WAVE_LAYER1 = 1,      // the phase-sliced layer 1 of the next batch, one wave of blocks that fills every CU: 1024-thread blocks
+    SAGE_BESIDE_LAYER1_AND_INNER_SAMPLER = 2,   // the same with every batch's inner sampler in that layer 1's queue, in front of it (role pipeline,
+                                          // sage_pipe.hip round 11): 512-thread blocks again -- measured there: 51.6 us per forward against 65.7
 };
 int sage_launch_layer_fused(const sage_rows_t& src, const sage_lists_t& l, const sage_self_t& self, const sage_contract_t& c,
                             const sage_slot_resolve_t* resolve, sage_finish_t fin, hipStream_t st, sage_launch_events_t* ev = nullptr,
@@ -166,9 +168,10 @@ int sage_launch_xent_head(const sage_head_t& h, hipStream_t st);
 #define SAGE_STAGE_ALL          31
 int sage_forward2_launch_stages(const sage_model_t* m, void* workspace, size_t workspace_bytes, const int32_t* seeds, int32_t batch,
                                 uint64_t seed, float* out, int64_t ldo, int32_t stages, hipStream_t stream, void* tail_event = nullptr,
-                                void* const* gather_events = nullptr);
+                                void* const* gather_events = nullptr, bool inner_with_layer1 = false);
 
 bool sage_forward2_contract1_is_empty(const sage_model_t* m, int32_t batch);
+bool sage_forward2_sampler_is_fused(const sage_model_t* m);
 
 // Launch-shape tunables, read ONCE from the environment (A/B runs on one box without rebuilding; defaults are the
 // measured optima recorded in DESIGN.md).  Every value is clamped to a safe range.
@@ -188,7 +191,7 @@ struct sage_tunables_t {
                                   //                      (measured: 24.3 us fused vs 10.3 + 11.4: the inner hop of a block's own winners is
                                   //                      three dependent rounds on 128-256 blocks instead of one round on 1500; pipeline 66.8 vs 66.2 us)
     int tile16_waves;             // SAGE_T16_WAVES       layer-2 tile16 kernel: 16 (1024-thread blocks) or 8 (512-thread blocks); 0 (default, unset) = by the
-                                  //                      launch's company, sage_layer_company_t: 16 beside the one-launch layer 1, 8 otherwise
+                                  //                      launch's company, sage_layer_company_t: 16 beside the one-launch layer 1 alone, 8 otherwise
     int tile16_inflight;          // SAGE_T16_INFLIGHT    layer-2 tile16 kernel, gcn form with 16 waves: 7 or 13 row loads of a lane group in flight per trip
                                   //                      (13: the 25-entry list of config 3 in ONE trip); 0 (default, unset) = by the launch's company:
                                   //                      13 beside the one-launch layer 1, 7 otherwise.  Every other form has 7

@@ -73,6 +73,35 @@
 //   * flush / reset / destroy / set_threads look at host counters only; reset restarts the batch index at 0 (the caller has synchronised).
 //   * submit_profiled: the two timing events ride on the launch, on whichever stream it takes.
 //   * the run-ahead window counts batches (done[RL], markers on stream L): no stream G in it.
+//
+// Inner sampler in front of layer 1 (round 11, SAGE_PIPE_SI_WITH_L1).  With the alternation layer 1 no longer waits for its queue but for
+// its data: every G(b) starts one hand-off behind Si(b), and stream S is a serial chain -- So(b+1) behind Si(b) by stream order although
+// the two share nothing, a ~12 us boundary in front of every So -- whose cycle So + Si + boundary fills the period
+// (profiles/r11_trace/parent.txt: 98.5 % of it; 68 % of layer-1 starts lead back through Si(b) and So(b) to So(b)'s queue predecessor).
+// Where the pipe alternates (takes_inner_with_layer1: the alternation's own conditions for even and odd batches alike, and two sampler
+// launches to cut between), role S launches only So(b), with ev[RS][slot] as its tail, and role G's calls for the batch -- the wait on
+// ev[RS][slot], then Si(b) and layer 1 with ev[RG][slot] as the tail of the latter -- go to the batch's layer-1 stream (st[RG] for even,
+// st[RD] for odd b).  No new stream, no new event; the kernels, their arguments and the workspaces are the same.  Layer 2 of such a batch
+// takes 512-thread blocks (sage_internal.h: SAGE_BESIDE_LAYER1_AND_INNER_SAMPLER): with Si in the layer-1 queues the 1024-thread form
+// starved (DESIGN section 4 has the rows).  What relied on "Si(b) behind So(b) and in front of So(b+1) by stream order", and why it still holds:
+//   * outer-hop data: Si(b) reads s1_nodes, the counters, slot2 and the hash rows So(b) wrote.  ev[RS][slot] is now recorded behind So(b)
+//     alone and the stream that carries Si(b) waits on it first -- the same event layer 1 waited on before, one launch earlier; layer 1
+//     follows Si(b) by stream order.
+//   * the hash-key wipe: Si(b)'s resolve job wipes the slot's keys, which So(b + depth) touches next.  So(b + depth) waits on L(b), L(b)
+//     on ev[RG][slot], the tail of layer 1 (b), which follows Si(b) in its stream.  Different slots never shared keys, so So(b+1)
+//     running beside Si(b) -- the point of the cut -- touches other tables, workspaces and sampler keys.
+//   * query_first: a wait that is skipped because So(b) has already finished is a wait that had nothing to wait for; the query sees the
+//     record made for this batch (host order, next point).
+//   * host threads: role G's thread touches batch b only after role S's thread has made its calls for b (done[RS] > b), as before; the
+//     single-threaded submit makes role S's calls first.  Role S's thread is done with a batch sooner, nothing else changes.
+//   * express batches, captures: the predicate is false, the whole batch (or the old cut) is enqueued as before.  join and fork go over
+//     streams, not over what they carry; reset and update_weights look at host state.  The cut is decided per submit from d_empty: an
+//     update that makes stage D non-empty between two batches gives batch b the new cut and batch b+1 the old one -- Si(b+1) then
+//     follows So(b+1) on st[RS] by stream order, and Si(b) on a layer-1 stream is held to its own batch by events as above (with depth
+//     1, the one case where both use the same slot, So(b+1) waits on L(b)); the other direction is the same argument mirrored.
+//   * submit_profiled: the pair is handed to the gather stage only (sage_forward.hip), so it still brackets the layer-1 launch and not
+//     the sampler in front of it; the tail event cannot ride on a launch that carries the pair and is recorded behind it, as before.
+//   * the run-ahead window counts markers on stream L: no sampler in it.
 #include <sched.h>
 #include <stdlib.h>
 
@@ -96,6 +125,7 @@ struct pipe_desc {                                      // one posted batch
     bool fresh;
     bool express;                                       // an IDLE pipeline's batch: all five launches on stream L, no hand-off (see submit_one)
     bool alt;                                           // role G's calls for this batch go to stream D's idle queue (alternating layer-1 streams)
+    bool inner_with_l1;                                 // the inner sampler is launched by role G, in front of this batch's layer 1 (header, round 11)
     uint64_t index;                                     // the pipe's submit counter at this batch (since the last reset)
     void* gev[2];
 };
@@ -115,6 +145,7 @@ struct sage_pipe {
     uint64_t submitted;
     int64_t express_count;                              // batches that took the express lane (submitting thread only)
     int64_t alternate_count;                            // batches whose layer 1 went to stream D's queue (submitting thread only)
+    int64_t inner_with_l1_count;                        // batches whose inner sampler went in front of their layer 1 (submitting thread only)
     // host enqueue threads
     int device;
     bool threaded;
@@ -215,6 +246,7 @@ extern "C" int sage_pipe_create(const sage_model_t* m, int32_t batch, int32_t de
     p->submitted = 0;
     p->express_count = 0;
     p->alternate_count = 0;
+    p->inner_with_l1_count = 0;
     p->threaded = false;
     p->window = 0;
     p->device = 0;
@@ -307,13 +339,15 @@ static int role_enqueue(sage_pipe* p, int r, const pipe_desc& d, unsigned long l
     }
     // Every role: wait on the producer, launch the role's stages with the hand-off event as their tail, record it unless it rode.
     //   S: outer + inner sample.  Needs the slot's previous batch to have left layer 2 (its last block zeroes the counters).
+    //      Only the outer hop where the batch's inner sampler rides in front of its layer 1 (d.inner_with_l1): role G then launches both,
+    //      in this order, on the one stream `on`; the tail event and the profiled pair stay with the gather, the last of the two.
     //   G: the layer-1 gather (nothing to launch when layer 1 is a one-launch layer; D then waits on S through G's stream order).
     //      A profiled submit's two caller-owned timing events (d.gev) become the gather launch's OWN start / stop events.
     //   D: the contraction (or the whole fused layer 1).
     //   L: layer 2; afterwards the workspace is clean again.
     const struct { int producer, stages, consumer; bool takes_out; } stage[4] = {
-        {RL, SAGE_STAGE_SAMPLE_OUTER | SAGE_STAGE_SAMPLE_INNER, RG, false},
-        {RS, SAGE_STAGE_GATHER1, g_consumer, false},
+        {RL, d.inner_with_l1 ? SAGE_STAGE_SAMPLE_OUTER : SAGE_STAGE_SAMPLE_OUTER | SAGE_STAGE_SAMPLE_INNER, RG, false},
+        {RS, d.inner_with_l1 ? SAGE_STAGE_SAMPLE_INNER | SAGE_STAGE_GATHER1 : SAGE_STAGE_GATHER1, g_consumer, false},
         {RG, SAGE_STAGE_CONTRACT1, RL, false},
         {d_empty ? RG : RD, SAGE_STAGE_LAYER2, RS, true}};
     const auto& s = stage[r];
@@ -358,7 +392,7 @@ static int role_enqueue(sage_pipe* p, int r, const pipe_desc& d, unsigned long l
     if (!skip) {
         void* const t = tail(r, needed);
         if (int rc = sage_forward2_launch_stages(m, ws, p->ws_bytes, d.seeds, p->batch, d.key, s.takes_out ? d.out : nullptr,
-                                                 s.takes_out ? d.ldo : 0, s.stages, on, t, d.gev))
+                                                 s.takes_out ? d.ldo : 0, s.stages, on, t, d.gev, d.inner_with_l1))
             return rc;
         if (t) return SAGE_OK;
     }
@@ -546,6 +580,16 @@ static bool takes_alternate(const sage_pipe* p, const pipe_desc& d, bool capturi
     return alternate_on(p) && !capturing && !d.express && (d.index & 1) && stage_d_skipped(p) && distinct_streams(p);
 }
 
+// Inner sampler in front of layer 1 (header, round 11): SAGE_PIPE_SI_WITH_L1=0 / 1 turns it off / on, read once; unset, the pipe takes it
+// wherever it alternates.  On needs the alternation all the same: with every layer 1 on the single stream G, Si would only add to the
+// pacemaker's cycle, and with the fused sampler (sage_forward2_sampler_is_fused) the two hops are one launch that cannot be cut.
+// Even and odd batches alike: the stream is the one takes_alternate chose for the batch's layer 1.
+static bool takes_inner_with_layer1(const sage_pipe* p, const pipe_desc& d, bool capturing) {
+    static const int knob = [] { const char* v = getenv("SAGE_PIPE_SI_WITH_L1"); return !v || !*v ? -1 : *v == '1' ? 1 : 0; }();
+    if (knob == 0) return false;
+    return alternate_on(p) && !capturing && !d.express && stage_d_skipped(p) && distinct_streams(p) && !sage_forward2_sampler_is_fused(&p->model);
+}
+
 // One batch through the four role streams.
 static int submit_one(sage_pipe* p, const int32_t* seeds, uint64_t key, float* out, int64_t ldo, bool fresh_slot,
                       void* const* gather_events = nullptr) {
@@ -555,6 +599,7 @@ static int submit_one(sage_pipe* p, const int32_t* seeds, uint64_t key, float* o
     d.fresh = fresh_slot;
     d.express = false;
     d.alt = false;
+    d.inner_with_l1 = false;
     d.index = p->submitted;
     d.gev[0] = gather_events ? gather_events[0] : nullptr;
     d.gev[1] = gather_events ? gather_events[1] : nullptr;
@@ -566,6 +611,8 @@ static int submit_one(sage_pipe* p, const int32_t* seeds, uint64_t key, float* o
         p->express_count += d.express ? 1 : 0;
         d.alt = takes_alternate(p, d, false);
         p->alternate_count += d.alt ? 1 : 0;
+        d.inner_with_l1 = takes_inner_with_layer1(p, d, false);
+        p->inner_with_l1_count += d.inner_with_l1 ? 1 : 0;
         return post(p, d);
     }
     unsigned long long cap = 0;
@@ -574,6 +621,8 @@ static int submit_one(sage_pipe* p, const int32_t* seeds, uint64_t key, float* o
     p->express_count += d.express ? 1 : 0;
     d.alt = takes_alternate(p, d, cap != 0 || p->cap_id[slot] != 0);
     p->alternate_count += d.alt ? 1 : 0;
+    d.inner_with_l1 = takes_inner_with_layer1(p, d, cap != 0 || p->cap_id[slot] != 0);
+    p->inner_with_l1_count += d.inner_with_l1 ? 1 : 0;
     for (int r = 0; r < 4; ++r)
         if (int rc = role_enqueue(p, r, d, cap)) return rc;
     p->cap_id[slot] = 0;
@@ -598,6 +647,7 @@ static int submit_one(sage_pipe* p, const int32_t* seeds, uint64_t key, float* o
 
 extern "C" int64_t sage_pipe_express_count(const sage_pipe_t* p) { return p ? p->express_count : -1; }
 extern "C" int64_t sage_pipe_alternate_count(const sage_pipe_t* p) { return p ? p->alternate_count : -1; }
+extern "C" int64_t sage_pipe_inner_with_layer1_count(const sage_pipe_t* p) { return p ? p->inner_with_l1_count : -1; }
 
 // Forget every submit: the next `depth` submits find their workspaces free.  The caller has synchronised (or joined) everything
 // submitted before -- e.g. after a stream capture ended, before eager submission resumes on the same pipe.

@@ -650,7 +650,8 @@ class RolePipeline:
     "SGDL" = four streams, "SGDD" = D and L share one, "SSSS" = one stream (= sage_forward2's launch order).
     `priorities`: per distinct stream, 0 = default, -1 = high (HIP stream priority); none named and four streams: S and L, the
     latency-bound roles, are high.  While stage D is empty (the one-launch layer 1) and stream L outranks streams G and D, the native
-    pipe puts every odd batch's layer 1 on stream D's idle queue (`alternate_count`; SAGE_PIPE_G_ALT=0 / 1 forces it off / on).
+    pipe puts every odd batch's layer 1 on stream D's idle queue (`alternate_count`; SAGE_PIPE_G_ALT=0 / 1 forces it off / on), and
+    every batch's inner sampler in front of its layer 1 (`inner_with_layer1_count`; SAGE_PIPE_SI_WITH_L1=0 / 1).
     The reference has no counterpart (model.py:240-252 is one batch at a time on the host)."""
     _h = None          # the native pipe; a class default because __del__ also meets a pipe whose __init__ failed or never ran
 
@@ -790,6 +791,12 @@ class RolePipeline:
     def alternate_count(self):
         """Batches of this pipe whose layer 1 was enqueued on stream D's idle queue (csrc/sage_pipe.hip, SAGE_PIPE_G_ALT=1)."""
         return int(native.lib().sage_pipe_alternate_count(self._h))
+
+    @property
+    def inner_with_layer1_count(self):
+        """Batches of this pipe whose inner sampler was enqueued in front of their layer 1, on that launch's stream (csrc/sage_pipe.hip,
+        SAGE_PIPE_SI_WITH_L1)."""
+        return int(native.lib().sage_pipe_inner_with_layer1_count(self._h))
 
     def fork(self, stream=None):
         """Every role stream waits for `stream` (default: the current one): inputs written there are ready."""

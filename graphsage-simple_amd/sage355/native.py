@@ -34,7 +34,7 @@ SYMBOLS = [
     "sage_prepared_weight_bytes", "sage_prepare_weights",
     "sage_pipe_create", "sage_pipe_destroy", "sage_pipe_update_weights", "sage_pipe_submit", "sage_pipe_submit_profiled", "sage_pipe_submit_many",
     "sage_pipe_join", "sage_pipe_fork", "sage_pipe_reset", "sage_pipe_set_threads", "sage_pipe_flush",
-    "sage_pipe_express_count", "sage_pipe_alternate_count", "sage_csr_mean_workspace_bytes", "sage_csr_mean",
+    "sage_pipe_express_count", "sage_pipe_alternate_count", "sage_pipe_inner_with_layer1_count", "sage_csr_mean_workspace_bytes", "sage_csr_mean",
     "sage_csr_mean_backward_workspace_bytes", "sage_csr_mean_backward",
     "sage_csr_sum_workspace_bytes", "sage_csr_sum",
     "sage_embed_grad_workspace_bytes", "sage_embed_grad",
@@ -152,6 +152,7 @@ def lib():
     L.sage_pipe_flush.argtypes = [P]
     L.sage_pipe_express_count.argtypes = [P]
     L.sage_pipe_alternate_count.argtypes = [P]
+    L.sage_pipe_inner_with_layer1_count.argtypes = [P]
     L.sage_csr_mean_workspace_bytes.argtypes = [I32, I64, I32]
     L.sage_csr_mean.argtypes = [P, P, I64, P, I32, I64, P, I64, I64, I32, I32, P, P, I64, P, c_size_t, P]
     L.sage_csr_mean_backward_workspace_bytes.argtypes = [I64, I32, I64, I32]
@@ -172,7 +173,7 @@ def lib():
         fn = getattr(L, name)
         if name == "sage_prepared_weight_bytes" or name.endswith("_workspace_bytes"):
             fn.restype = c_size_t
-        elif name in ("sage_pipe_express_count", "sage_pipe_alternate_count"):
+        elif name in ("sage_pipe_express_count", "sage_pipe_alternate_count", "sage_pipe_inner_with_layer1_count"):
             fn.restype = c_int64
         elif name not in ("sage_last_error", "sage_build_arch"):
             fn.restype = c_int32

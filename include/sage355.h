@@ -716,6 +716,16 @@ int64_t sage_pipe_express_count(const sage_pipe_t* p);
  * 4-5 us per forward slower, not faster); SAGE_PIPE_G_ALT=0 / 1 (environment, read once) forces it off / on.
  * Returns how many batches of this pipe had their layer 1 on stream D so far (-1: NULL pipe). */
 int64_t sage_pipe_alternate_count(const sage_pipe_t* p);
+/* Inner sampler in front of layer 1 (additive, ABI 9).  Wherever the pipe alternates its layer-1 streams (above), role S launches only
+ * the outer hop of a batch and role G launches the inner hop and then layer 1, one behind the other on the batch's layer-1 stream (G
+ * for even, D for odd batches): stream S is no longer a serial chain of two samplers per batch, and the stream-to-stream hand-off sits
+ * between the two hops instead of in front of a layer 1 that waits for nothing else.  Layer 2 of such a batch runs in 512-thread
+ * blocks (the 1024-thread form starves beside two layer-1 launches and a sampler).  Same kernels, events, workspaces and
+ * arguments, bit-identical results; never inside a stream capture, for an express batch, without the alternation, or with the fused
+ * sampler (SAGE_SAMPLE_FUSED=1: one launch for both hops).  SAGE_PIPE_SI_WITH_L1=0 / 1 (environment, read once) forces it off / on
+ * where the alternation is taken; unset, the pipe takes it.
+ * Returns how many batches of this pipe had their inner sampler launched in front of their layer 1 so far (-1: NULL pipe). */
+int64_t sage_pipe_inner_with_layer1_count(const sage_pipe_t* p);
 
 /* ---------------------------------------------------------------------------
  * Classifier head (ABI 9): SupervisedGraphSage's scores, CrossEntropyLoss and the three gradients that follow
