@@ -408,3 +408,202 @@ def contraction_bar(x, w, concat):
     e_torch = float(contraction_units((xf @ wf.t()).numpy(), xf.numpy(), wf.numpy())[0].max()) if fin.any() else 0.0
     base = (6.0 if concat else 4.0) if x.shape[1] <= 512 else 6.0
     return max(base, 2.0 * e_torch), e_torch
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The generic contraction linear_act_kernel (csrc/sage_linear.hip): cases, data, a numpy fp32 emulation of its accumulation and
+# masks, and the bar -- shared by tests/test_gpu_linear_act.py (the kernel) and tests/test_linear_act_host.py (the emulation,
+# faithful and deliberately broken, on the very same data).
+LINEAR_MODES = ("gcn", "concat", "concat_index")      # no self_tab; self_tab row r for output row r; self_tab row self_index[r]
+
+# (n, dim, out_dim, small n_dev or None): every n, dim and out_dim the kernel's masks distinguish -- the 64-row tile with its two
+# 32-row accumulators, four waves of 32 columns, 128-column blocks in grid.y, 32-wide K panels -- and each out_dim with an n that is
+# no multiple of 32.  Each shape runs in all three modes, without n_dev and with n_dev = max(n - 3, 0); a small n_dev in addition
+# leaves whole 64-row tiles empty.  dim = 1433 (K = 1433 gcn, 2866 concat: the deepest in use) at n = 65 only.
+LINEAR_SHAPES = [
+    (1, 1, 1, None),
+    (31, 7, 3, None),
+    (33, 31, 31, None),
+    (63, 32, 32, None),
+    (65, 33, 33, None),
+    (129, 50, 50, None),
+    (31, 64, 96, None),
+    (33, 100, 97, None),
+    (63, 1, 127, None),
+    (65, 7, 128, None),
+    (129, 31, 129, None),
+    (1, 33, 300, None),
+    (32, 50, 33, None),
+    (64, 64, 50, None),
+    (129, 100, 300, 40),
+    (65, 1433, 128, None),
+]
+LINEAR_RUNS = [(n, dim, h, mode, small) for (n, dim, h, small) in LINEAR_SHAPES for mode in LINEAR_MODES]
+
+
+def linear_n_devs(n, small):
+    """The device-side row counts a shape runs with: absent, n - 3 (0 at n < 3: the only tile is empty) and the small one."""
+    return [None, max(n - 3, 0)] + ([small] if small is not None else [])
+
+
+def linear_case(n, dim, out_dim, mode, seed=0):
+    """Hand-made inputs of one linear_act call as the kernel sees them: flat fp32 allocations (numpy) with every operand a view
+    ("agg", "self", "w", "out": (offset, ld) into the allocation of the same name + "_flat"), based one float in, with odd pads --
+    ld_agg = dim + 1, ld_self = dim + 3, ldw = 2 dim + 5, ldo = out_dim + 3 -- and one spare row behind each.  W is allocated as
+    the concat W [out_dim, 2 dim]; the gcn mode's W is its agg half, the view W[:, dim:] (same ld).  Every entry, pads included, is
+    +-U[0.5, 1): each of the K terms of an output is at least 1 / (4 K) of sum |x||w|, and a read that strays into a pad finds a
+    finite value of the same size.  concat_index: the table has n + 3 rows, self_index is a permutation of the first n + 2 without
+    a fixed point in [0, n), and the last row, which no index names, is NaN."""
+    assert mode in LINEAR_MODES
+    rs = np.random.default_rng(1000 * n + 10 * dim + out_dim + seed)
+
+    def flat(size):
+        return (rs.uniform(0.5, 1.0, size) * rs.choice([-1.0, 1.0], size)).astype(np.float32)
+
+    ld_agg, ld_self, ldw, ldo = dim + 1, dim + 3, 2 * dim + 5, out_dim + 3
+    tab_rows = n + 3 if mode == "concat_index" else n
+    c = {"n": n, "dim": dim, "out_dim": out_dim, "mode": mode, "tab_rows": tab_rows,
+         "agg_flat": flat(1 + ld_agg * (n + 1)), "agg": (1, ld_agg),
+         "self_flat": flat(1 + ld_self * (tab_rows + 1)), "self": (1, ld_self) if mode != "gcn" else None,
+         "w_flat": flat(1 + ldw * (out_dim + 1)), "w": (1 + (dim if mode == "gcn" else 0), ldw),
+         "out": (1, ldo), "out_size": 1 + ldo * (n + 1), "self_index": None}
+    if mode == "concat_index":
+        while True:
+            perm = rs.permutation(n + 2)
+            if not np.any(perm[:n] == np.arange(n)):
+                break
+        c["self_index"] = perm[:n].astype(np.int64)
+        off, ld = c["self"]
+        c["self_flat"][off + ld * (n + 2): off + ld * (n + 2) + dim] = np.nan
+    return c
+
+
+def linear_poisoned(c, n_dev):
+    """The case as it is run with a device-side row count: rows of agg (and, without self_index, of self_tab) at or past n_dev are
+    NaN, entries of self_index at or past n_dev name the spare NaN row of the table.  A copy; `c` is left alone."""
+    p = dict(c)
+    n, dim = c["n"], c["dim"]
+    p["agg_flat"] = c["agg_flat"].copy()
+    off, ld = c["agg"]
+    for r in range(n_dev, n):
+        p["agg_flat"][off + r * ld: off + r * ld + dim] = np.nan
+    if c["mode"] == "concat":
+        p["self_flat"] = c["self_flat"].copy()
+        off, ld = c["self"]
+        for r in range(n_dev, n):
+            p["self_flat"][off + r * ld: off + r * ld + dim] = np.nan
+    if c["mode"] == "concat_index":
+        p["self_index"] = c["self_index"].copy()
+        p["self_index"][n_dev:] = n + 2
+    return p
+
+
+def linear_view(c, name, rows, cols):
+    """The [rows, cols] operand `name` of a case, a copy"""
+    off, ld = c[name]
+    return c[name + "_flat"][off + ld * np.arange(rows)[:, None] + np.arange(cols)[None, :]]
+
+
+def linear_operands(c):
+    """-> (x [n, K], w [out_dim, K]): the [self | agg] rows and the weight rows that the call's arguments name."""
+    n, dim = c["n"], c["dim"]
+    agg = linear_view(c, "agg", n, dim)
+    k = dim * (1 if c["mode"] == "gcn" else 2)
+    w = linear_view(c, "w", c["out_dim"], k)
+    if c["mode"] == "gcn":
+        return agg, w
+    tab = linear_view(c, "self", c["tab_rows"], dim)
+    own = tab[:n] if c["self_index"] is None else tab[c["self_index"]]
+    return np.concatenate([own, agg], 1), w
+
+
+def bf16_round(x):
+    """fp32 -> the nearest bf16 (ties to even), as fp32"""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32)
+    u = (u + (((u >> 16) & 1) + np.uint32(0x7FFF))) & np.uint32(0xFFFF0000)
+    return u.view(np.float32)
+
+
+LINEAR_VARIANTS = ("fma", "mul_add")
+LINEAR_BROKEN = ("drop_k", "seam", "self_row", "k_tail", "bf16")
+
+
+def linear_broken_applies(broken, c):
+    """Does this defect change what the kernel computes at this case?  The seam and the self row exist in the concat modes, the K
+    tail where K is no multiple of the 32-wide panel."""
+    k = c["dim"] * (1 if c["mode"] == "gcn" else 2)
+    return {"drop_k": True, "bf16": True, "seam": c["mode"] != "gcn", "self_row": c["mode"] == "concat_index", "k_tail": k % 32 != 0}[broken]
+
+
+def linear_act_emulate(c, nn=None, variant="fma", broken=None, fill=np.nan):
+    """linear_act_kernel's pre-activation in numpy fp32, loads, masks and order as the kernel has them: 32-wide K panels, panel column
+    gk < ds from self_tab row self_index[r] (or r), the rest from agg column gk - ds, rows at or past nn and columns at or past K
+    zero, W rows likewise; k ascending, two terms per matrix instruction.  The instruction's rounding is not documented, so there
+    are two variants: "fma", acc = fma(a1, b1, fma(a0, b0, acc)), and "mul_add", both products rounded to fp32 and added to acc one
+    after the other.  Rows at or past nn are not stored: they hold `fill`.  -> [n, out_dim] fp32.
+    broken: "drop_k" leaves out the term k = K // 2; "seam" puts the seam one column early (panel column ds - 1 is read from agg
+    column -1); "self_row" reads self_tab row r where self_index[r] is meant; "k_tail" does not mask the panel columns at or past K
+    (both operands read on past their rows); "bf16" rounds the row operand to bf16."""
+    n, dim, h = c["n"], c["dim"], c["out_dim"]
+    nn = n if nn is None else min(nn, n)
+    ds = 0 if c["self"] is None else dim
+    K = ds + dim
+    kp = -(-K // 32) * 32
+    gk = np.arange(kp)
+    rows = np.arange(n)
+
+    def load(name, r, col):
+        off, ld = c[name]
+        buf = c[name + "_flat"]
+        return buf[np.clip(off + ld * r[:, None] + col[None, :], 0, len(buf) - 1)]
+
+    kmask = np.ones(kp, dtype=bool) if broken == "k_tail" else gk < K
+    seam = ds - 1 if (broken == "seam" and ds) else ds
+    a = np.zeros((n, kp), dtype=np.float32)
+    if ds:
+        sr = c["self_index"] if (c["self_index"] is not None and broken != "self_row") else rows
+        a[:, :seam] = load("self", sr, gk[:seam])
+    a[:, seam:] = load("agg", rows, gk[seam:] - ds)
+    a[:, ~kmask] = 0
+    a[nn:] = 0
+    b = load("w", np.arange(h), gk)
+    b[:, ~kmask] = 0
+    if broken == "drop_k":
+        a[:, K // 2] = 0
+    if broken == "bf16":
+        a = bf16_round(a)
+    a64, b64 = a.astype(np.float64), b.astype(np.float64)
+    acc = np.zeros((n, h), dtype=np.float32)
+    with np.errstate(invalid="ignore", over="ignore"):
+        for k in range(kp):
+            p = a64[:, k, None] * b64[None, :, k]                # an fp32 x fp32 product is exact in fp64
+            if variant == "mul_add":
+                p = p.astype(np.float32).astype(np.float64)
+            acc = (acc.astype(np.float64) + p).astype(np.float32)
+    out = np.full((n, h), fill, dtype=np.float32)
+    out[:nn] = acc[:nn]
+    return out
+
+
+def linear_bar(c, nn=None):
+    """The bar of the generic contraction on one case, in units of 2^-23 sum_k |x_k||w_k| per element: twice the worst figure that
+    either variant of the emulation leaves on the same data (NOT a figure of the kernel) -- the margin of 2 because nobody has
+    measured how v_mfma_f32_32x32x2_f32 rounds its two-term step; both variants measured 0.5 to 1.8 units on this kind of data for
+    K from 1 to 2866.  And the condition under which that bar has teeth: the smallest single term's share of an output,
+    min over (row, column, k) of |x_k w_k| in the same units, of which the bar must stay below one eighth.
+    Rows at or past nn are left out.  -> (bar, {variant: figure}, share)"""
+    n = c["n"] if nn is None else min(nn, c["n"])
+    x, w = linear_operands(c)
+    x, w = x[:n], w
+    if n == 0:
+        return 0.0, {v: 0.0 for v in LINEAR_VARIANTS}, np.inf
+    figs = {}
+    for v in LINEAR_VARIANTS:
+        got = linear_act_emulate(c, nn=nn, variant=v)[:n]
+        figs[v] = float(contraction_units(got, x, w)[0].max())
+    ax, aw = np.abs(x.astype(np.float64)), np.abs(w.astype(np.float64))
+    smallest = np.full((n, w.shape[0]), np.inf)
+    for k in range(x.shape[1]):
+        smallest = np.minimum(smallest, ax[:, k, None] * aw[None, :, k])
+    share = float((smallest / (2.0 ** -23 * (ax @ aw.T))).min())
+    return 2.0 * max(figs.values()), figs, share
