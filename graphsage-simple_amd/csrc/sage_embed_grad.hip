@@ -13,6 +13,8 @@
 //   4-6. count, carry, expand (sage_csr_common.h): runs of more than one chunk get item entries and partial rows
 //   7. chunk    one lane group per item: partials[item] := the chunk's weighted sum
 //   8. rows     one lane group per embedding row: short runs summed in place, long ones = their partials in chunk order; STORE
+// sage_embed_grad_rows (below) is the same sum for the rows that have a term only, with the SGD update of those rows fused in: steps
+// 1, 2, 4-7 unchanged, step 3 a run list of the sorted keys instead of a row pointer over the table, step 8 over the runs.
 // Arithmetic of a row (its bits depend on nothing else): p_c = 0, then p_c = fma(g, w, p_c) over chunk c's terms in (p, j) order
 // (ONE rounding per term: a fused multiply-add, spelled fmaf so that no compiler flag decides); out = 0 + p_0 + p_1 + ... for a
 // run of more than one chunk, out = p_0 for any other.  No float atomics, no host synchronisation, no allocation.
@@ -163,6 +165,29 @@ __global__ __launch_bounds__(256) void embed_chunk_kernel(const float* __restric
     }
 }
 
+// Columns [c0, c0 + 4) of the sum of the run [b, e) of the sorted list, entry r of the row pointer that the chunk pass walked (an
+// embedding row for sage_embed_grad, a run for sage_embed_grad_rows): THE arithmetic of a row, the only copy of it
+__device__ inline V4 run_sum(const float* __restrict__ gagg, int64_t ldg, int dim, const int32_t* __restrict__ vals,
+                             const float* __restrict__ inv_c, const int64_t* __restrict__ off, int64_t cap,
+                             const float* __restrict__ partials, int64_t r, int64_t b, int64_t e, int c0) {
+    const int64_t kc = long_chunks(e - b);
+    const int64_t o = kc > 0 ? off[r] : 0;
+    const bool split = kc > 0 && o + kc <= cap;                     // the chunk pass summed this row's chunks (always, with this cap)
+    V4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (split) {
+        for (int64_t c = 0; c < kc; ++c) vadd(s, *reinterpret_cast<const V4*>(partials + (o + c) * dim + c0));
+    } else if (kc == 0) {
+        weighted_sum(gagg, ldg, vals, inv_c, b, e, c0, s);
+    } else {                                                         // the chunk pass's sums, here: same operations, same order
+        for (int64_t c = 0; c < kc; ++c) {
+            V4 p = make_float4(0.f, 0.f, 0.f, 0.f);
+            weighted_sum(gagg, ldg, vals, inv_c, b + c * kChunk, min(b + (c + 1) * kChunk, e), c0, p);
+            vadd(s, p);
+        }
+    }
+    return s;
+}
+
 // 8. LG lanes per embedding row
 template <int LG>
 __global__ __launch_bounds__(256) void embed_row_kernel(const float* __restrict__ gagg, int64_t ldg, int dim, const int32_t* __restrict__ vals,
@@ -176,23 +201,156 @@ __global__ __launch_bounds__(256) void embed_row_kernel(const float* __restrict_
         int32_t v;
         int64_t b, e;
         row_span(rowptr, embed_rows, nullptr, (int)r, total, v, b, e);
-        const int64_t kc = long_chunks(e - b);
-        const int64_t o = kc > 0 ? off[r] : 0;
-        const bool split = kc > 0 && o + kc <= cap;                 // the chunk pass summed this row's chunks (always, with this cap)
-        for (int c0 = gl * 4; c0 < dim; c0 += LG * 4) {
-            V4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (split) {
-                for (int64_t c = 0; c < kc; ++c) vadd(s, *reinterpret_cast<const V4*>(partials + (o + c) * dim + c0));
-            } else if (kc == 0) {
-                weighted_sum(gagg, ldg, vals, inv_c, b, e, c0, s);
-            } else {                                                 // the chunk pass's sums, here: same operations, same order
-                for (int64_t c = 0; c < kc; ++c) {
-                    V4 p = make_float4(0.f, 0.f, 0.f, 0.f);
-                    weighted_sum(gagg, ldg, vals, inv_c, b + c * kChunk, min(b + (c + 1) * kChunk, e), c0, p);
-                    vadd(s, p);
-                }
+        for (int c0 = gl * 4; c0 < dim; c0 += LG * 4)
+            *reinterpret_cast<V4*>(out + r * ld + c0) = run_sum(gagg, ldg, dim, vals, inv_c, off, cap, partials, r, b, e, c0);
+    }
+}
+
+// ---- sage_embed_grad_rows: the same sums over the RUNS of the sorted list, nothing sized by embed_rows -----------------------------
+// The sorted keys are the embedding rows with a term, ascending, each a run of equal keys, then the sentinels.  A run list takes the
+// place of the row pointer over the embedding rows: run u = (run_row[u], [runptr[u], runptr[u + 1])), u < U; entries [U, runs_cap] of
+// runptr hold the end of the terms (empty spans), so the count / carry / expand / chunk kernels above walk it as they walk a CSR of
+// runs_cap rows.  runs_cap = min(slots, embed_rows) bounds U on the host.
+struct RowsLayout {
+    size_t keys_in, keys_out, vals_in, vals_out, inv_c, run_row, runptr, heads, end_pos, off, carry, item_row, partials, cub, total;
+    size_t cub_bytes;
+    int64_t cap, nblocks, head_blocks, runs_cap;
+    int slots, bits;
+};
+
+constexpr int kHeadThreads = 256, kHeadIpt = 8, kHeadTile = kHeadThreads * kHeadIpt;
+
+bool rows_layout(int32_t n, int32_t k, int64_t embed_rows, int32_t dim, RowsLayout* L) {
+    if (n < 1 || k < 1 || dim < 1 || embed_rows < 1 || embed_rows >= (1ll << 31) || (int64_t)n * k >= (1ll << 31)) return false;
+    L->slots = n * k;
+    L->bits = 1;
+    while ((1ll << L->bits) <= embed_rows) ++L->bits;              // keys are in [0, embed_rows] (the sentinel included)
+    L->runs_cap = std::min<int64_t>(L->slots, embed_rows);         // distinct rows with a term: what every array below is sized by
+    L->cap = csr_item_cap((int32_t)L->runs_cap, L->slots);
+    L->nblocks = (L->runs_cap + kCountTile - 1) / kCountTile;
+    L->head_blocks = ((int64_t)L->slots + kHeadTile - 1) / kHeadTile;
+    size_t off = 0;
+    auto take = [&](size_t bytes) { size_t o = off; off = align256(off + std::max<size_t>(bytes, 1)); return o; };
+    L->keys_in = take((size_t)L->slots * 4);
+    L->keys_out = take((size_t)L->slots * 4);
+    L->vals_in = take((size_t)L->slots * 4);
+    L->vals_out = take((size_t)L->slots * 4);
+    L->inv_c = take((size_t)n * 4);
+    L->run_row = take((size_t)L->runs_cap * 4);
+    L->runptr = take((size_t)(L->runs_cap + 1) * 8);
+    L->heads = take((size_t)(L->head_blocks + 1) * 8);
+    L->end_pos = take(8);
+    L->off = take((size_t)L->runs_cap * 8);
+    L->carry = take((size_t)(L->nblocks + 1) * 8);
+    L->item_row = take((size_t)L->cap * 4);
+    L->partials = take((size_t)L->cap * (size_t)dim * 4);
+    L->cub_bytes = (size_t)L->slots * 16 + 65536;                  // the sort's temporary: embed_layout's bound and its reasons
+    L->cub = take(L->cub_bytes);
+    L->total = off;
+    return true;
+}
+
+// Is position i of the sorted keys the first of a run of a row (the sentinel's run is none)?
+__device__ inline bool run_head(const int32_t* __restrict__ keys, int64_t i, int sentinel) {
+    const int key = keys[i];
+    return key != sentinel && (i == 0 || keys[i - 1] != key);
+}
+
+// 3a / 3c. kHeadIpt consecutive positions per thread.  SCATTER false: heads[block] := the run heads in the block's tile (then
+// csr_carry_kernel: heads[block] := the runs before the tile, heads[head_blocks] := U).  SCATTER true: run u = heads[block] + (the
+// heads before it in the tile) gets its row and its start, and the one position where the terms end (the first sentinel, or
+// slots) is written to end_pos
+template <bool SCATTER>
+__global__ __launch_bounds__(kHeadThreads) void embed_heads_kernel(const int32_t* __restrict__ keys, int slots, int sentinel, int64_t runs_cap,
+                                                                    int64_t* __restrict__ heads, int32_t* __restrict__ run_row,
+                                                                    int64_t* __restrict__ runptr, int64_t* __restrict__ end_pos) {
+    __shared__ int wave_sum[kHeadThreads / kWave];
+    const int64_t i0 = (int64_t)blockIdx.x * kHeadTile + (int64_t)threadIdx.x * kHeadIpt;
+    bool h[kHeadIpt];
+    int s = 0;
+#pragma unroll
+    for (int u = 0; u < kHeadIpt; ++u) {
+        h[u] = i0 + u < slots && run_head(keys, i0 + u, sentinel);
+        s += h[u] ? 1 : 0;
+    }
+    const int lane = sage_lane(), w = threadIdx.x / kWave;
+    int incl = s;
+#pragma unroll
+    for (int d = 1; d < kWave; d <<= 1) {
+        const int y = __shfl_up(incl, d, kWave);
+        if (lane >= d) incl += y;
+    }
+    if (lane == kWave - 1) wave_sum[w] = incl;
+    __syncthreads();
+    int before = 0, block = 0;
+#pragma unroll
+    for (int i = 0; i < kHeadThreads / kWave; ++i) {
+        if (i < w) before += wave_sum[i];
+        block += wave_sum[i];
+    }
+    if (!SCATTER) {
+        if (threadIdx.x == 0) heads[blockIdx.x] = block;
+        return;
+    }
+    int64_t u_run = heads[blockIdx.x] + before + incl - s;
+#pragma unroll
+    for (int u = 0; u < kHeadIpt; ++u) {
+        const int64_t i = i0 + u;
+        if (i >= slots) break;
+        if (h[u]) {
+            if (u_run < runs_cap) {                                  // always: distinct keys below the sentinel are at most runs_cap
+                run_row[u_run] = keys[i];
+                runptr[u_run] = i;
             }
-            *reinterpret_cast<V4*>(out + r * ld + c0) = s;
+            ++u_run;
+        }
+        const int key = keys[i];
+        if (key == sentinel && (i == 0 || keys[i - 1] != sentinel)) *end_pos = i;          // sorted: exactly one such position, or none
+        if (i == slots - 1 && key != sentinel) *end_pos = slots;
+    }
+}
+
+// 3d. runptr[u] := the end of the terms for u in [U, runs_cap]; num_rows_out[0] := U
+__global__ __launch_bounds__(256) void embed_runs_fill_kernel(const int64_t* __restrict__ heads, int head_blocks, const int64_t* __restrict__ end_pos,
+                                                              int64_t runs_cap, int64_t* __restrict__ runptr, int32_t* __restrict__ num_rows_out) {
+    const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int64_t nruns = min(heads[head_blocks], runs_cap);
+    if (u == 0) num_rows_out[0] = (int32_t)nruns;
+    if (u >= nruns && u <= runs_cap) runptr[u] = *end_pos;
+}
+
+// 8'. LG lanes per run u < U (U read on the device): the run's sum, run_sum above, stored as row u of the compact gradient (u <
+// max_rows) and / or applied to row run_row[u] of the embedding: embed = fma(-lr, sum, embed), one rounding
+template <int LG>
+__global__ __launch_bounds__(256) void embed_runs_row_kernel(const float* __restrict__ gagg, int64_t ldg, int dim, const int32_t* __restrict__ vals,
+                                                             const float* __restrict__ inv_c, const int64_t* __restrict__ runptr, int runs_cap,
+                                                             const int64_t* __restrict__ num_runs, const int64_t* __restrict__ off, int64_t cap,
+                                                             const float* __restrict__ partials, const int32_t* __restrict__ run_row,
+                                                             int32_t* __restrict__ rows_out, float* __restrict__ grad_rows, int64_t max_rows,
+                                                             int64_t ldr, float* __restrict__ embed, int64_t lde, int embed_rows, float lr) {
+    const int64_t gid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / LG, ngroups = ((int64_t)gridDim.x * blockDim.x) / LG;
+    const int gl = (int)(threadIdx.x % LG);
+    const int64_t total = runptr[runs_cap];
+    const int64_t nruns = min(*num_runs, (int64_t)runs_cap);
+    for (int64_t u = gid; u < nruns; u += ngroups) {
+        int32_t v;
+        int64_t b, e;
+        row_span(runptr, runs_cap, nullptr, (int)u, total, v, b, e);
+        const int row = min(max(run_row[u], 0), embed_rows - 1);   // a key of the expand kernel: inside the table already
+        const bool keep = grad_rows != nullptr && u < max_rows;
+        if (keep && gl == 0) rows_out[u] = row;
+        for (int c0 = gl * 4; c0 < dim; c0 += LG * 4) {
+            const V4 s = run_sum(gagg, ldg, dim, vals, inv_c, off, cap, partials, u, b, e, c0);
+            if (keep) *reinterpret_cast<V4*>(grad_rows + u * ldr + c0) = s;
+            if (embed) {
+                V4* p = reinterpret_cast<V4*>(embed + (int64_t)row * lde + c0);
+                V4 x = *p;
+                x.x = fmaf(-lr, s.x, x.x);
+                x.y = fmaf(-lr, s.y, x.y);
+                x.z = fmaf(-lr, s.z, x.z);
+                x.w = fmaf(-lr, s.w, x.w);
+                *p = x;
+            }
         }
     }
 }
@@ -284,5 +442,113 @@ extern "C" int sage_embed_grad(const float* grad_agg, int64_t ldg, int32_t dim, 
                   (const int64_t*)off, L.cap, (const float*)partials, grad_embed, ld);
 #undef SAGE_EMBED_LG
     SAGE_CHECK_LAUNCH("embed_row_kernel");
+    return SAGE_OK;
+}
+
+extern "C" size_t sage_embed_grad_rows_workspace_bytes(int32_t n, int32_t k, int64_t embed_rows, int32_t dim) {
+    if (n == 0 && k >= 1 && dim >= 1 && embed_rows >= 1) return 256;
+    RowsLayout L;
+    return rows_layout(n, k, embed_rows, dim, &L) ? L.total : 0;
+}
+
+extern "C" int sage_embed_grad_rows(const float* grad_agg, int64_t ldg, int32_t dim, const int32_t* nbr, const int32_t* cnt, int32_t k, int32_t n,
+                                    const int32_t* n_dev, const int32_t* row_order, int64_t embed_rows, int32_t* num_rows_out,
+                                    int32_t* rows_out, float* grad_rows, int64_t max_rows, int64_t ldr, float* embed, int64_t lde, float lr,
+                                    void* workspace, size_t workspace_bytes, sage_stream_t stream) {
+    // sage_embed_grad's rules and order: shapes first, then pointers
+    SAGE_REQUIRE(n >= 0 && k >= 1 && (int64_t)n * k < (1ll << 31), "embed_grad_rows: n = %d, k = %d (n * k < 2^31)", n, k);
+    SAGE_REQUIRE(dim >= 4 && dim % 4 == 0, "embed_grad_rows: dim = %d (rows of 16-byte pieces)", dim);
+    SAGE_REQUIRE(ldg >= dim && ldg % 4 == 0, "embed_grad_rows: ldg = %lld", (long long)ldg);
+    SAGE_REQUIRE(!grad_rows || (ldr >= dim && ldr % 4 == 0), "embed_grad_rows: ldr = %lld", (long long)ldr);
+    SAGE_REQUIRE(!embed || (lde >= dim && lde % 4 == 0), "embed_grad_rows: lde = %lld", (long long)lde);
+    SAGE_REQUIRE(embed_rows >= 1 && embed_rows < (1ll << 31), "embed_grad_rows: embed_rows = %lld", (long long)embed_rows);
+    SAGE_REQUIRE(!grad_rows || max_rows >= 1, "embed_grad_rows: max_rows = %lld with grad_rows", (long long)max_rows);
+    SAGE_REQUIRE(grad_agg && nbr && cnt && num_rows_out, "embed_grad_rows: NULL array");
+    SAGE_REQUIRE(grad_rows || embed, "embed_grad_rows: neither grad_rows nor embed is given");
+    SAGE_REQUIRE(!grad_rows || rows_out, "embed_grad_rows: grad_rows without rows_out");
+    SAGE_REQUIRE(sage_aligned(grad_agg, 16) && sage_aligned(grad_rows, 16) && sage_aligned(embed, 16),
+                 "embed_grad_rows: grad_agg / grad_rows / embed not 16-byte aligned");
+    if (n == 0) return SAGE_OK;
+    RowsLayout L;
+    SAGE_REQUIRE(rows_layout(n, k, embed_rows, dim, &L), "embed_grad_rows: n = %d, k = %d, embed_rows = %lld, dim = %d out of range", n, k,
+                 (long long)embed_rows, dim);
+    if (workspace_bytes < L.total || !workspace) {
+        sage_set_error("embed_grad_rows: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
+        return SAGE_ENOSPACE;
+    }
+    SAGE_REQUIRE(sage_aligned(workspace, 256), "embed_grad_rows: workspace not 256-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    int32_t* keys_in = (int32_t*)(ws + L.keys_in);
+    int32_t* keys_out = (int32_t*)(ws + L.keys_out);
+    int32_t* vals_in = (int32_t*)(ws + L.vals_in);
+    int32_t* vals_out = (int32_t*)(ws + L.vals_out);
+    float* inv_c = (float*)(ws + L.inv_c);
+    int32_t* run_row = (int32_t*)(ws + L.run_row);
+    int64_t* runptr = (int64_t*)(ws + L.runptr);
+    int64_t* heads = (int64_t*)(ws + L.heads);
+    int64_t* end_pos = (int64_t*)(ws + L.end_pos);
+    int64_t* off = (int64_t*)(ws + L.off);
+    int64_t* carry = (int64_t*)(ws + L.carry);
+    int32_t* item_row = (int32_t*)(ws + L.item_row);
+    float* partials = (float*)(ws + L.partials);
+    const int R = (int)embed_rows, C = (int)L.runs_cap, nb = (int)L.nblocks, hb = (int)L.head_blocks;
+    size_t sort_bytes = 0;
+    if (sort_temp_bytes(L.slots, L.bits, &sort_bytes) != hipSuccess || sort_bytes > L.cub_bytes) {
+        sage_set_error("embed_grad_rows: the radix sort asks for %zu bytes of temporary, %zu reserved", sort_bytes, L.cub_bytes);
+        return SAGE_ELAUNCH;
+    }
+
+    hipLaunchKernelGGL(embed_expand_kernel, dim3(sage_cdiv(L.slots, 256)), dim3(256), 0, st, nbr, cnt, k, n, n_dev, row_order, R, keys_in, vals_in,
+                       inv_c);
+    SAGE_CHECK_LAUNCH("embed_expand_kernel");
+    size_t cub_bytes = L.cub_bytes;
+    if (hipcub::DeviceRadixSort::SortPairs(ws + L.cub, cub_bytes, (const int32_t*)keys_in, keys_out, (const int32_t*)vals_in, vals_out, L.slots, 0,
+                                           L.bits, st) != hipSuccess) {
+        sage_set_error("embed_grad_rows: radix sort failed");
+        return SAGE_ELAUNCH;
+    }
+    // the run list: count the heads per tile, scan the tiles, write the runs, close the list
+    hipLaunchKernelGGL(embed_heads_kernel<false>, dim3(hb), dim3(kHeadThreads), 0, st, (const int32_t*)keys_out, L.slots, R, L.runs_cap, heads,
+                       run_row, runptr, end_pos);
+    SAGE_CHECK_LAUNCH("embed_heads_kernel (count)");
+    hipLaunchKernelGGL(csr_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, heads, hb);
+    SAGE_CHECK_LAUNCH("csr_carry_kernel (runs)");
+    hipLaunchKernelGGL(embed_heads_kernel<true>, dim3(hb), dim3(kHeadThreads), 0, st, (const int32_t*)keys_out, L.slots, R, L.runs_cap, heads,
+                       run_row, runptr, end_pos);
+    SAGE_CHECK_LAUNCH("embed_heads_kernel (scatter)");
+    hipLaunchKernelGGL(embed_runs_fill_kernel, dim3(sage_cdiv(L.runs_cap + 1, 256)), dim3(256), 0, st, (const int64_t*)heads, hb,
+                       (const int64_t*)end_pos, L.runs_cap, runptr, num_rows_out);
+    SAGE_CHECK_LAUNCH("embed_runs_fill_kernel");
+    // the chunk split over the runs: sage_embed_grad's launches with the run list as the row pointer
+    hipLaunchKernelGGL(csr_count_kernel, dim3(nb), dim3(kCountThreads), 0, st, (const int64_t*)runptr, L.runs_cap, (const int32_t*)nullptr, C, off,
+                       carry);
+    SAGE_CHECK_LAUNCH("csr_count_kernel");
+    hipLaunchKernelGGL(csr_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, carry, nb);
+    SAGE_CHECK_LAUNCH("csr_carry_kernel");
+    hipLaunchKernelGGL(csr_expand_kernel, dim3(sage_cdiv(C, 256)), dim3(256), 0, st, (const int64_t*)runptr, L.runs_cap, (const int32_t*)nullptr, C,
+                       off, (const int64_t*)carry, L.cap, item_row);
+    SAGE_CHECK_LAUNCH("csr_expand_kernel");
+
+    const int lg = dim >= 256 ? 64 : dim >= 128 ? 32 : dim >= 64 ? 16 : 8;
+#define SAGE_EMBED_LG(KERNEL, BLOCKS, ...)                                                                          \
+    do {                                                                                                            \
+        if (lg == 64) hipLaunchKernelGGL(KERNEL<64>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);                   \
+        else if (lg == 32) hipLaunchKernelGGL(KERNEL<32>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);              \
+        else if (lg == 16) hipLaunchKernelGGL(KERNEL<16>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);              \
+        else hipLaunchKernelGGL(KERNEL<8>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);                             \
+    } while (0)
+    if (L.cap > 0) {
+        const int blocks = (int)std::min<int64_t>((L.cap * lg + 255) / 256, kNumCU * 8);
+        SAGE_EMBED_LG(embed_chunk_kernel, blocks, grad_agg, ldg, dim, (const int32_t*)vals_out, (const float*)inv_c, (const int64_t*)runptr, C,
+                      (const int64_t*)off, (const int64_t*)carry, nb, L.cap, (const int32_t*)item_row, partials);
+        SAGE_CHECK_LAUNCH("embed_chunk_kernel");
+    }
+    const int blocks = (int)std::min<int64_t>((L.runs_cap * lg + 255) / 256, kNumCU * 8);
+    SAGE_EMBED_LG(embed_runs_row_kernel, blocks, grad_agg, ldg, dim, (const int32_t*)vals_out, (const float*)inv_c, (const int64_t*)runptr, C,
+                  (const int64_t*)(heads + hb), (const int64_t*)off, L.cap, (const float*)partials, (const int32_t*)run_row, rows_out, grad_rows,
+                  max_rows, ldr, embed, lde, R, lr);
+#undef SAGE_EMBED_LG
+    SAGE_CHECK_LAUNCH("embed_runs_row_kernel");
     return SAGE_OK;
 }

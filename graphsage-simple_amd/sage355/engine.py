@@ -495,7 +495,7 @@ class TwoHopEngine:
         return out
 
     # ---- backward of the last forward through the intermediates it left in the workspace (model.py:249) ----
-    def backward_weights(self, out, grad_out, need_w1=True, need_embed=False):
+    def backward_weights(self, out, grad_out, need_w1=True, need_embed=False, embed_lr=None):
         """Gradients of (w1, w2), in the caller's shapes, of the LAST forward on this engine: `out` is what it returned
         ([B, h2]), grad_out = d loss / d out.  Autograd of the reference's expression (mm / relu / cat / div) from
         the engine's own intermediates -- nbr / cnt / row2 / h1 (and the layer-1 means when layer 1 ran split) are still in the
@@ -504,8 +504,21 @@ class TwoHopEngine:
         need_embed (an indexed engine only; a plain one raises): -> (g_w1, g_w2, g_embed), g_embed [R, d0] the dense gradient of the
         embedding, every row stored: g_h1 by the mean's backward over (row2, cnt2) -- (seed, slot) order -- then layer 1's grad_x on the
         kept means, then sage_embed_grad over (nbr1, cnt1) in sage_row_order's order of s1_nodes: no atomics, the bits do not depend
-        on where the frontier's rows sit.  The weight gradients come from the same calls with or without it."""
+        on where the frontier's rows sit.  The weight gradients come from the same calls with or without it.
+        need_embed="rows": -> (g_w1, g_w2, (rows, num_rows, grad_rows)), the gradient of the TOUCHED rows only (sage_embed_grad_rows):
+        num_rows int32 [1] on the device, rows int32 [cap] ascending, grad_rows [cap, d0] the very bits need_embed=True stores in those
+        rows, cap = min(max_s1 * k1, R); the buffers are the engine's, allocated on first use and rewritten by the next call.  With
+        embed_lr=<float> the same call also applies embed[rows] = fma(-embed_lr, grad_rows, embed[rows]) to the engine's embedding.
+        need_embed="update" (embed_lr required): the update alone, no gradient materialised; the third entry is num_rows.  Nothing on
+        these two forms costs time or memory in proportion to R.  The update moves the embedding's version counter as an in-place
+        torch op would, so a live RolePipeline over the same tensor orders its streams behind it at its next submit."""
         from . import ops
+        if need_embed not in (False, True, "rows", "update"):
+            raise native.SageError(f"backward_weights: need_embed = {need_embed!r}, expected False, True, 'rows' or 'update'")
+        if embed_lr is not None and need_embed not in ("rows", "update"):
+            raise native.SageError("backward_weights: embed_lr goes with need_embed='rows' or 'update'")
+        if need_embed == "update" and embed_lr is None:
+            raise native.SageError("backward_weights: need_embed='update' needs embed_lr")
         if need_embed and self.embed_index is None:
             raise native.SageError("backward_weights: need_embed on an engine without embed_index: its table is frozen features, "
                                    "no gradient reaches it")
@@ -598,11 +611,34 @@ class TwoHopEngine:
         # 3. the frontier's rows by ascending node id, 4. the chunked sum over the sampled sets, which hold embedding rows
         wso = scratch("ws_order", lib.sage_row_order_workspace_bytes(n1))
         native.check(lib.sage_row_order(P(s1_nodes), n1, P(sc["nlive"]), 0, P(order), P(wso), wso.numel(), st), "row_order")
-        g_embed = torch.empty(rows, d0p, device=dev)
-        wse = scratch("ws_embed", lib.sage_embed_grad_workspace_bytes(n1, k1, rows, d0p))
-        native.check(lib.sage_embed_grad(P(g_agg1), d0p, d0p, P(nbr1), P(cnt1), k1, n1, P(sc["nlive"]), P(order), P(g_embed), rows, d0p,
-                                         P(wse), wse.numel(), st), "embed_grad")
-        return g_w1, g_w2, g_embed
+        if need_embed not in ("rows", "update"):
+            g_embed = torch.empty(rows, d0p, device=dev)
+            wse = scratch("ws_embed", lib.sage_embed_grad_workspace_bytes(n1, k1, rows, d0p))
+            native.check(lib.sage_embed_grad(P(g_agg1), d0p, d0p, P(nbr1), P(cnt1), k1, n1, P(sc["nlive"]), P(order), P(g_embed), rows, d0p,
+                                             P(wse), wse.numel(), st), "embed_grad")
+            return g_w1, g_w2, g_embed
+        # the touched rows only: the compact gradient and / or the update of the embedding in place, nothing sized by R
+        cap = min(n1 * k1, rows)
+        if sc.get("num_rows") is None:
+            sc["num_rows"] = torch.zeros(1, dtype=torch.int32, device=dev)
+        rows_t = grad_t = None
+        if need_embed == "rows":
+            if sc.get("rows") is None:
+                sc["rows"] = torch.empty(cap, dtype=torch.int32, device=dev)
+                sc["grad_rows"] = torch.empty(cap, d0p, device=dev)
+            rows_t, grad_t = sc["rows"], sc["grad_rows"]
+        embed = self.table if embed_lr is not None else None                # the caller's tensor itself (an indexed engine reads it in place)
+        wsr = scratch("ws_embed_rows", lib.sage_embed_grad_rows_workspace_bytes(n1, k1, rows, d0p))
+        native.check(lib.sage_embed_grad_rows(P(g_agg1), d0p, d0p, P(nbr1), P(cnt1), k1, n1, P(sc["nlive"]), P(order), rows, P(sc["num_rows"]),
+                                              P(rows_t), P(grad_t), cap, d0p, P(embed), self.table_ld, float(embed_lr or 0.0),
+                                              P(wsr), wsr.numel(), st), "embed_grad_rows")
+        if embed is not None:
+            # the write went past torch: move the version counter as `embed.add_()` would, for everything keyed on it (RolePipeline's
+            # _weights_key: join, fork behind this stream).  The engine itself holds no copy of an indexed table to refresh
+            torch.autograd.graph.increment_version(self._tables.src)
+        if need_embed == "rows":
+            return g_w1, g_w2, (rows_t, sc["num_rows"], grad_t)
+        return g_w1, g_w2, sc["num_rows"]
 
     # ---- read-back of the last forward's intermediates (tests, parity gate, byte counting) ----
     def _view(self, off, count, dtype):

@@ -37,7 +37,7 @@ SYMBOLS = [
     "sage_pipe_express_count", "sage_pipe_alternate_count", "sage_pipe_inner_with_layer1_count", "sage_csr_mean_workspace_bytes", "sage_csr_mean",
     "sage_csr_mean_backward_workspace_bytes", "sage_csr_mean_backward",
     "sage_csr_sum_workspace_bytes", "sage_csr_sum",
-    "sage_embed_grad_workspace_bytes", "sage_embed_grad",
+    "sage_embed_grad_workspace_bytes", "sage_embed_grad", "sage_embed_grad_rows_workspace_bytes", "sage_embed_grad_rows",
     "sage_csr_mean_indexed", "sage_csr_mean_backward_grouped_workspace_bytes", "sage_csr_mean_backward_grouped",
     "sage_layer1_fused", "sage_layer1_fused_supported",
     "sage_xent_head_supported", "sage_xent_head_workspace_bytes", "sage_xent_head",
@@ -161,6 +161,8 @@ def lib():
     L.sage_csr_sum.argtypes = [P, P, I64, I64, P, I64, I64, I32, P, I64, P, c_size_t, P]
     L.sage_embed_grad_workspace_bytes.argtypes = [I32, I32, I64, I32]
     L.sage_embed_grad.argtypes = [P, I64, I32, P, P, I32, I32, P, P, P, I64, I64, P, c_size_t, P]
+    L.sage_embed_grad_rows_workspace_bytes.argtypes = [I32, I32, I64, I32]
+    L.sage_embed_grad_rows.argtypes = [P, I64, I32, P, P, I32, I32, P, P, I64, P, P, P, I64, I64, P, I64, c_float, P, c_size_t, P]
     L.sage_csr_mean_indexed.argtypes = [P, P, I64, P, I32, I64, P, P, I64, I64, I32, I32, P, P, I64, P, c_size_t, P]
     L.sage_csr_mean_backward_grouped_workspace_bytes.argtypes = [I64, I64, I64, I32]
     L.sage_csr_mean_backward_grouped.argtypes = [P, P, P, P, I64, I64, I64, P, I64, I32, I32, P, I64, P, c_size_t, P]

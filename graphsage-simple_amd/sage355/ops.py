@@ -641,6 +641,82 @@ def embed_grad(grad_agg, nbr, cnt, embed_rows, n_dev=None, row_order=None, out=N
     return out
 
 
+def embed_grad_rows_workspace_bytes(n, k, embed_rows, dim):
+    """Bytes of the workspace sage_embed_grad_rows needs (host arithmetic; 0 = shape out of range; one value for every
+    embed_rows >= n * k)."""
+    return int(native.lib().sage_embed_grad_rows_workspace_bytes(int(n), int(k), int(embed_rows), int(dim)))
+
+
+def embed_grad_rows(grad_agg, nbr, cnt, embed_rows, n_dev=None, row_order=None, max_rows=None, embed=None, lr=None, want_grad=True,
+                    out=None, workspace=None):
+    """embed_grad for the touched rows only, and / or their SGD update in place (sage_embed_grad_rows: nothing sized by embed_rows).
+    -> (rows, num_rows, grad_rows): num_rows int32 [1] on the device, the number U of distinct embedding rows with a term; rows int32
+    [max_rows], grad_rows [max_rows, dim]: the first min(U, max_rows) of them ascending and their sums, bit for bit the rows
+    embed_grad stores (entries past that are left as they were); both None with want_grad=False.  max_rows: default min(n * k,
+    embed_rows), which always holds every row.  embed [embed_rows, dim] with lr: embed[e] = fma(-lr, sum, embed[e]) for ALL U rows, in
+    place, other rows untouched (torch's version counter of `embed` does not move: the caller's business).  out: (rows, num_rows,
+    grad_rows) to write into (rows / grad_rows may be None there with want_grad=False); workspace: a uint8 device tensor to reuse."""
+    _need_gpu()
+    grad_agg, ldg = _row_major(grad_agg, "grad_agg")
+    _chk(nbr, torch.int32, "nbr", 2)
+    _chk(cnt, torch.int32, "cnt", 1)
+    n, k = nbr.shape
+    dim, rows = grad_agg.shape[1], int(embed_rows)
+    dev = grad_agg.device
+    if grad_agg.shape[0] < n or cnt.shape[0] < n:
+        raise native.SageError(f"embed_grad_rows: {n} sets, grad_agg has {grad_agg.shape[0]} rows, cnt {cnt.shape[0]} entries")
+    if n_dev is not None:
+        _chk(n_dev, torch.int32, "n_dev")
+    if row_order is not None:
+        _chk(row_order, torch.int32, "row_order", 1)
+        if row_order.shape[0] < n:
+            raise native.SageError(f"embed_grad_rows: row_order has {row_order.shape[0]} entries for {n} rows")
+    if not want_grad and embed is None:
+        raise native.SageError("embed_grad_rows: nothing to do: want_grad=False and no embed to update")
+    if (embed is None) != (lr is None):
+        raise native.SageError("embed_grad_rows: embed and lr go together")
+    lde = 0
+    if embed is not None:
+        embed, lde = _row_major(embed, "embed")
+        if embed.shape[0] < rows or embed.shape[1] != dim:
+            raise native.SageError(f"embed_grad_rows: embed is {tuple(embed.shape)}, expected ({rows}, {dim})")
+    cap = min(n * k, rows) if max_rows is None else int(max_rows)
+    if want_grad and cap < 1 and n > 0:
+        raise native.SageError(f"embed_grad_rows: max_rows = {cap}")
+    cap = max(cap, 1)
+    rows_t, num_t, grad_t = out if out is not None else (None, None, None)
+    if num_t is None:
+        num_t = torch.empty(1, dtype=torch.int32, device=dev)
+    _chk(num_t, torch.int32, "num_rows", 1)
+    ldr = 0
+    if want_grad:
+        if rows_t is None:
+            rows_t = torch.empty(cap, dtype=torch.int32, device=dev)
+        if grad_t is None:
+            grad_t = torch.empty((cap, dim), dtype=torch.float32, device=dev)
+        _chk(rows_t, torch.int32, "rows", 1)
+        grad_t, ldr = _row_major(grad_t, "grad_rows")
+        if rows_t.shape[0] < cap or grad_t.shape[0] < cap or grad_t.shape[1] != dim:
+            raise native.SageError(f"embed_grad_rows: out is rows {tuple(rows_t.shape)}, grad_rows {tuple(grad_t.shape)}, expected "
+                                   f"({cap},) and ({cap}, {dim})")
+    else:
+        rows_t = grad_t = None
+    if n == 0:                                             # the library launches nothing then: the count is written here
+        num_t.zero_()
+        return rows_t, num_t, grad_t
+    need = embed_grad_rows_workspace_bytes(n, k, rows, dim)
+    if need == 0:
+        raise native.SageError(f"embed_grad_rows: n = {n}, k = {k}, embed_rows = {rows}, dim = {dim} out of range")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    rc = native.lib().sage_embed_grad_rows(native.ptr(grad_agg), ldg, dim, native.ptr(nbr), native.ptr(cnt), k, n, native.ptr(n_dev),
+                                           native.ptr(row_order), rows, native.ptr(num_t), native.ptr(rows_t), native.ptr(grad_t), cap, ldr,
+                                           native.ptr(embed), lde, 0.0 if lr is None else float(lr), native.ptr(workspace),
+                                           workspace.numel(), native.stream_handle())
+    native.check(rc, "embed_grad_rows")
+    return rows_t, num_t, grad_t
+
+
 def xent_head_supported(dim, num_classes):
     return bool(native.lib().sage_xent_head_supported(int(dim), int(num_classes)))
 

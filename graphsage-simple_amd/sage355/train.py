@@ -164,11 +164,16 @@ class EngineTrainer:
     embed_index), parameters() and grads() gain a fourth entry, step() updates the embedding in place with the dense [embed_rows,
     embed_dim] gradient of backward_weights(need_embed=True).  gcn encoder without the aggregator's self loop, no relabel,
     embed_dim % 4 == 0; no captured step and no data-parallel step in this form.  act1: layer 1's activation (node_degree uses
-    sigmoid, encoders.py:58-59)."""
+    sigmoid, encoders.py:58-59).
+    sparse_embed=True (an embedding trainer only; the default stays False): step() applies the embedding's update to the rows the batch
+    touched and to nothing else, inside the gradient call itself (backward_weights(need_embed="update"): embed[e] = fma(-lr, g[e],
+    embed[e]), one rounding), and grads() returns the compact triple (rows, num_rows, grad_rows) -- buffers of the engine, rewritten by
+    the next call -- as its fourth entry: no [embed_rows, embed_dim] tensor exists anywhere in the step.  For a 1hot table of millions
+    of rows; a small table (node_degree) gains little."""
 
     def __init__(self, rowptr, col, table, num_classes, hidden1=50, hidden2=128, num_sample1=10, num_sample2=10, gcn=True, lr=0.7,
                  max_batch=256, agg_self_loop=False, relabel=None, head="torch", embed_index=None, embed_rows=None, embed_dim=None,
-                 act1=ACT_RELU):
+                 act1=ACT_RELU, sparse_embed=False):
         """head: "torch" -- the classifier, its loss and their gradients as stock torch ops (the default: its bits are the recorded
         w_cls trajectories); "native" -- one sage_xent_head call, its sums in an order fixed by the shape.  With the
         native head the loss and the classifier gradient that grads() returns live in buffers of the trainer, rewritten by its next call."""
@@ -179,6 +184,8 @@ class EngineTrainer:
             raise native.SageError(f"EngineTrainer: act1 = {act1!r}, expected ACT_RELU or ACT_SIGMOID")
         if embed_index is not None and table is not None:
             raise native.SageError("EngineTrainer: table and embed_index are alternatives: layer 1 reads one of them")
+        if sparse_embed and embed_index is None:
+            raise native.SageError("EngineTrainer: sparse_embed needs embed_index: a frozen table has no update to make sparse")
         if embed_index is not None:
             if embed_rows is None or embed_dim is None or int(embed_rows) < 1 or int(embed_dim) < 1:
                 raise native.SageError(f"EngineTrainer: embed_rows = {embed_rows!r}, embed_dim = {embed_dim!r}")
@@ -201,6 +208,7 @@ class EngineTrainer:
             self.embed_weight = torch.empty(int(embed_rows), d0, device=dev)
             init.normal_(self.embed_weight)
         self.lr = float(lr)
+        self.sparse_embed = bool(sparse_embed)
         self.concat = not gcn
         # data parallel: every rank starts from rank 0's weights.  BEFORE the engine is built: its constructor prepares the bf16
         # planes of W1 (and zero-padded copies of odd widths) and caches them under (data_ptr, _version), which a broadcast
@@ -229,8 +237,11 @@ class EngineTrainer:
     def parameters(self):
         return [self.w1, self.w2, self.w_cls] + ([] if self.embed_weight is None else [self.embed_weight])
 
-    def _backward(self, out, g_out):
-        """The engine's gradients behind the classifier's: (g_w1, g_w2), and the embedding's where there is one."""
+    def _backward(self, out, g_out, embed_lr=None):
+        """The engine's gradients behind the classifier's: (g_w1, g_w2), and the embedding's where there is one: dense, or on a sparse
+        trainer the compact triple -- with embed_lr the update is applied instead and the third entry is the touched-row count."""
+        if self.sparse_embed:
+            return self.engine.backward_weights(out, g_out, need_embed="rows" if embed_lr is None else "update", embed_lr=embed_lr)
         return self.engine.backward_weights(out, g_out, need_embed=self.embed_weight is not None)
 
     def embed(self, seeds, key=0):
@@ -251,9 +262,11 @@ class EngineTrainer:
         hd = self._head
         return self._ops.xent_head(emb, self.w_cls, grads=False, pred=True, workspace=hd["workspace"], out={"pred": hd["pred"]})["pred"].clone()
 
-    def grads(self, seeds, labels, key, global_batch=None):
-        """loss (device scalar) and the gradients of (w1, w2, w_cls) -- and of embed_weight, a fourth entry, on an embedding trainer --
-        for one batch; nothing is updated.
+    def grads(self, seeds, labels, key, global_batch=None, _embed_lr=None):
+        """loss (device scalar) and the gradients of (w1, w2, w_cls) -- and of embed_weight, a fourth entry, on an embedding trainer
+        (dense [embed_rows, embed_dim]; with sparse_embed the triple (rows, num_rows, grad_rows) of the touched rows) -- for one batch;
+        nothing is updated (_embed_lr is step()'s: on a sparse trainer the embedding's update is applied inside the gradient call and
+        the fourth entry is the touched-row count).
         global_batch: data parallel -- this rank holds a shard of a mini-batch of that many seeds; its loss is the SUM over its
         shard / global_batch, so that the SUM of the ranks' gradients is the full-batch gradient."""
         e = self.engine
@@ -273,7 +286,7 @@ class EngineTrainer:
             hd = self._head
             r = self._ops.xent_head(out, self.w_cls, labels, scale=1.0 / float(b if global_batch is None else global_batch),
                                     workspace=hd["workspace"], out=hd)
-            g_w1, g_w2, *g_e = self._backward(out, r["grad_emb"])
+            g_w1, g_w2, *g_e = self._backward(out, r["grad_emb"], _embed_lr)
             # eager: the caller may keep the loss of every step (run_engine_training does); queued: the captured step copies it at once
             loss = r["loss"][0]
             return (loss if seeds is None else loss.clone()), (g_w1, g_w2, r["grad_w"], *g_e)
@@ -293,15 +306,15 @@ class EngineTrainer:
         g_out = g_scores @ self.w_cls.detach()                              # [B, C] x [C, H2]: reduction over the classes
         g_cls = _sum_over_batch(g_scores, emb)                               # [C, B] x [B, H2]: reduction over the batch
         # both layers' weight gradients from the intermediates this forward left in the engine's workspace
-        g_w1, g_w2, *g_e = self._backward(out, g_out)
+        g_w1, g_w2, *g_e = self._backward(out, g_out, _embed_lr)
         return loss.detach(), (g_w1, g_w2, g_cls, *g_e)
 
     def step(self, seeds, labels, key, global_batch=None):
         """forward + backward + SGD; -> loss as a device scalar (reading it is the caller's only synchronisation).
         With torch.distributed initialised (one process per GPU, backend "nccl" = RCCL over xGMI) the three weight gradients
         travel in ONE flat all-reduce (SUM) per step, ~0.3 MB: latency bound, so one buffer and one call."""
-        loss, (g1, g2, gc, *ge) = self.grads(seeds, labels, key, global_batch)
-        if ge:
+        loss, (g1, g2, gc, *ge) = self.grads(seeds, labels, key, global_batch, _embed_lr=self.lr if self.sparse_embed else None)
+        if ge and not self.sparse_embed:                      # (sparse: the touched rows were updated inside the gradient call)
             self.embed_weight.add_(ge[0], alpha=-self.lr)     # in place: the engine reads this very tensor at the next forward
         if dist.world_size() > 1:
             flat = torch.cat([g1.reshape(-1), g2.reshape(-1), gc.reshape(-1)])
@@ -368,12 +381,13 @@ class EngineTrainer:
 
 def run_engine_training(graph, feat_data, labels, num_classes, seed=1, epochs=1, batch_size=128, ref_batching=False, lr=0.7,
                         sample_seed=0, hidden1=50, hidden2=128, num_sample1=10, num_sample2=10, gcn=True, head="torch", initializer=None,
-                        embed_dim=100):
+                        embed_dim=100, sparse_embed=False):
     """run_model (model.py:184-259) on the engine path: same split, shuffles, batching and optimiser as run_training above, every
     step through EngineTrainer.  -> dict(f1_micro, f1_macro, mean_step_time, losses, trainer).
     initializer: None (or "None") -- the frozen table feat_data; "1hot" -- a trainable embedding row per node, ReLU; "node_degree" -- a
     row per degree, SIGMOID at layer 1 (encoders.py:58-59).  feat_data is not read for the last two and may be None; embed_dim is
-    the embedding's width (the reference's --feature_dim default), a multiple of 4."""
+    the embedding's width (the reference's --feature_dim default), a multiple of 4.  sparse_embed: EngineTrainer's (an initializer
+    only): update the touched embedding rows alone."""
     from sklearn.metrics import f1_score
     from . import native
     from .fullgraph import degree_index, one_hot_index
@@ -384,12 +398,12 @@ def run_engine_training(graph, feat_data, labels, num_classes, seed=1, epochs=1,
     rowptr, col = graph.to(dev)
     n = graph.num_nodes
     if initializer in (None, "None"):
-        table, embed_kwargs = torch.as_tensor(feat_data, dtype=torch.float32).to(dev), {}
+        table, embed_kwargs = torch.as_tensor(feat_data, dtype=torch.float32).to(dev), dict(sparse_embed=sparse_embed)
     else:
         index, rows = one_hot_index(n, dev) if initializer == "1hot" else degree_index(rowptr)
         table = None
         embed_kwargs = dict(embed_index=index, embed_rows=rows, embed_dim=embed_dim,
-                            act1=ACT_SIGMOID if initializer == "node_degree" else ACT_RELU)
+                            act1=ACT_SIGMOID if initializer == "node_degree" else ACT_RELU, sparse_embed=sparse_embed)
     rand_indices = np.random.permutation(n)
     val = rand_indices[int(0.1 * n):int(0.2 * n)]
     train = list(rand_indices[int(0.2 * n):])

@@ -370,6 +370,56 @@ int    sage_embed_grad(const float* grad_agg, int64_t ldg, int32_t dim,     /* [
                        void* workspace, size_t workspace_bytes, sage_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * sage_embed_grad_rows (additive, ABI 9) -- sage_embed_grad for the TOUCHED
+ * rows only, and the SGD update of those rows in place: what a 1hot embedding
+ * of millions of rows needs, where a batch names a few hundred thousand.
+ * The first nine arguments and embed_rows are sage_embed_grad's, with its
+ * clamp, its live-row rule and its ORDER contract.  Let e_0 < e_1 < ... <
+ * e_{U-1} be the distinct embedding rows that receive at least one term and
+ * s_u row e_u's sum, bit for bit the row sage_embed_grad stores there (one
+ * copy of that arithmetic serves both entry points).
+ *   num_rows_out[0] = U on every call that launches (0 without a live term),
+ *                     also when U > max_rows: the caller sees a short buffer.
+ *   rows_out / grad_rows (a nullable pair; rows_out is required with grad_rows):
+ *                     for u < min(U, max_rows): rows_out[u] = e_u and
+ *                     grad_rows[u, 0:dim] = s_u.  Not written: rows at or past
+ *                     max_rows or U, columns [dim, ldr).
+ *   embed (nullable): embed[e_u, c] = fma(-lr, s_u[c], embed[e_u, c]) for EVERY
+ *                     u < U, whatever max_rows is: one rounding (fmaf).  Rows
+ *                     that no term names are neither read nor written; columns
+ *                     [dim, lde) are not written.
+ * At least one of grad_rows and embed; with both, the gradient returned is the
+ * one that was applied.
+ * NOTHING costs time or memory in proportion to embed_rows: no grid, loop,
+ * memset or workspace array is sized by it; it enters through the sort's key
+ * bits and the clamp only.  After sage_embed_grad's expand and stable sort the
+ * run heads of the sorted keys are counted and scanned into a run list (row,
+ * start; at most min(n * k, embed_rows) runs, a host-known capacity), which
+ * takes the place of the row pointer in sage_embed_grad's chunk split; the row
+ * kernel strides over u < U, read on the device.  No float atomics, no host
+ * synchronisation, no allocation.
+ * Limits and errors are sage_embed_grad's: dim, ldg multiples of 4, ldr / lde
+ * >= dim and multiples of 4 where their array is given, max_rows >= 1 with
+ * grad_rows, grad_agg / grad_rows / embed 16-byte aligned, workspace 256-byte
+ * aligned.  Shapes are checked before pointers; SAGE_EINVAL with the name in
+ * sage_last_error, SAGE_ENOSPACE for a short or missing workspace, both before
+ * any launch; n == 0 returns SAGE_OK without a launch (num_rows_out is then
+ * left as it was).  The workspace query is host arithmetic (0 = shape out of
+ * range) and returns one value for every embed_rows >= n * k.
+ * ------------------------------------------------------------------------- */
+size_t sage_embed_grad_rows_workspace_bytes(int32_t n, int32_t k, int64_t embed_rows, int32_t dim);
+int    sage_embed_grad_rows(const float* grad_agg, int64_t ldg, int32_t dim,     /* as sage_embed_grad ...                  */
+                            const int32_t* nbr, const int32_t* cnt, int32_t k,
+                            int32_t n, const int32_t* n_dev,
+                            const int32_t* row_order,
+                            int64_t embed_rows,
+                            int32_t* num_rows_out,                               /* [1] device, required                    */
+                            int32_t* rows_out, float* grad_rows,                 /* [max_rows], [max_rows, dim]: nullable pair */
+                            int64_t max_rows, int64_t ldr,
+                            float* embed, int64_t lde, float lr,                 /* [embed_rows, dim] updated in place; nullable */
+                            void* workspace, size_t workspace_bytes, sage_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * sage_linear_act --encoders.py:49-62 without materialising the concat:
  *     out[r, :] = act( W[:, 0:ds] . self(r) + W[:, ds:ds+dim] . agg[r, :] )
  * self(r) = self_tab[self_index ? self_index[r] : r, 0:dim]; ds = dim when
