@@ -1,7 +1,14 @@
-// What the full-neighbourhood mean (sage_csr_mean.hip) and its backward (sage_csr_mean_backward.hip) share: the clamped row span,
-// the small vector helpers, and the three launches that cut long rows into chunks of SAGE_CSR_MEAN_CHUNK edges
-// (count -> carry -> expand; see the head of sage_csr_mean.hip).  Everything has internal linkage: each translation unit that
-// includes this holds its own copy of the kernels.
+// The chunked row sum behind sage_csr_mean.hip, sage_csr_sum.hip, sage_csr_mean_backward.hip and sage_embed_grad.hip: rows longer
+// than SAGE_CSR_MEAN_CHUNK entries are cut into chunks, every chunk is summed in stored order, a row's partials are added in chunk
+// order, no float atomics.  This header holds the ONE copy of that rule:
+//   host    WsCursor / ChunkWs / chunk_ws (the workspace sub-layout), csr_chunk_plan (launches 1-3: count -> carry -> expand; see
+//           the head of sage_csr_mean.hip), csr_workspace_check
+//   device  row_span (the clamped row), chunk_item (is item i a chunk of a row that fits, and which entries), chunked_row_sum (a
+//           row's total: its partials, its entries in place, or -- a long row without workspace room -- the chunk pass's sums
+//           redone with the same operations in the same order), sum_edges (the unweighted term walker)
+// What differs per file is the TERM (a table row, a weighted gradient row) and what happens to a row's total; each file hands its
+// term walker to chunked_row_sum, so "same bits in the chunk pass and in the fall-back" holds by construction.
+// Everything has internal linkage: each translation unit that includes this holds its own copy of the kernels.
 #pragma once
 #include "sage_internal.h"
 
@@ -25,11 +32,27 @@ __device__ inline float4 vscale(const float4& a, float s) { return make_float4(a
 __device__ inline float vscale(const float& a, float s) { return a * s; }
 __device__ inline void vfill(float4& a, float s) { a = make_float4(s, s, s, s); }
 __device__ inline void vfill(float& a, float s) { a = s; }
+__device__ inline void vfma(float4& a, float s, const float4& b) {
+    a.x = __builtin_fmaf(s, b.x, a.x); a.y = __builtin_fmaf(s, b.y, a.y); a.z = __builtin_fmaf(s, b.z, a.z); a.w = __builtin_fmaf(s, b.w, a.w);
+}
+__device__ inline void vfma(float& a, float s, const float& b) { a = __builtin_fmaf(s, b, a); }
 
 __device__ inline int64_t uniform64(int64_t x) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
     const uint32_t hi = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)x >> 32));
     return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+// UNIFORM: the caller is ONE WAVE per row or item, so what it reads about the row is the same in every lane and is broadcast from the
+// first lane (it then lives in scalar registers).  The lane-group kernels of sage_embed_grad.hip hold several rows in a wave: they
+// pass false and every lane keeps its own value.  A template parameter, so that no caller can forget which it is.
+template <bool UNIFORM> __device__ inline int32_t bcast(int32_t x) {
+    if constexpr (UNIFORM) return __builtin_amdgcn_readfirstlane(x);
+    else return x;
+}
+template <bool UNIFORM> __device__ inline int64_t bcast(int64_t x) {
+    if constexpr (UNIFORM) return uniform64(x);
+    else return x;
 }
 
 // Row r's node and edge range, clamped: a node id outside [0, num_nodes) is an empty row without a self term (v = -1),
@@ -44,7 +67,24 @@ __device__ inline void row_span(const int64_t* __restrict__ rowptr, int64_t num_
     e = min(max(e, b), total);
 }
 
+template <bool UNIFORM>
+__device__ inline void row_span(const int64_t* __restrict__ rowptr, int64_t num_nodes, const int32_t* __restrict__ nodes, int r,
+                                int64_t total, int32_t& v, int64_t& b, int64_t& e) {
+    row_span(rowptr, num_nodes, nodes, r, total, v, b, e);
+    v = bcast<UNIFORM>(v);
+    b = bcast<UNIFORM>(b);
+    e = bcast<UNIFORM>(e);
+}
+
 __device__ inline int64_t long_chunks(int64_t deg) { return deg > kChunk ? (deg + kChunk - 1) / kChunk : 0; }
+
+// Did the chunk pass sum the k chunks of the row whose first item is o?  (k == 0: a row of one chunk, which has no items.)
+__device__ inline bool chunks_fit(int64_t k, int64_t o, int64_t cap) { return k > 0 && o + k <= cap; }
+
+// The first item of row r, read only where the row has items.
+template <bool UNIFORM> __device__ inline int64_t first_item(const int64_t* __restrict__ off, int64_t r, int64_t k) {
+    return k > 0 ? bcast<UNIFORM>(off[r]) : 0;
+}
 
 // 1. per-thread kCountIpt consecutive rows; off[r] := block-local exclusive offset, carry[block] := the block's chunk sum
 __global__ __launch_bounds__(kCountThreads) void csr_count_kernel(const int64_t* __restrict__ rowptr, int64_t num_nodes,
@@ -134,12 +174,160 @@ __global__ __launch_bounds__(256) void csr_expand_kernel(const int64_t* __restri
     const int64_t k = long_chunks(e - b);
     const int64_t o = off[r] + carry[r / kCountTile];
     off[r] = o;
-    if (k > 0 && o + k <= cap)
+    if (chunks_fit(k, o, cap))
         for (int64_t c = 0; c < k; ++c) item_row[o + c] = r;
 }
 
-// Item entries (= partial rows) a workspace sized for max_edges holds: the chunks of all long rows are at most
-// floor(E_sel / E) + (number of long rows), and a long row has more than E edges.
-inline int64_t csr_item_cap(int32_t n, int64_t max_edges) { return max_edges / kChunk + std::min<int64_t>(n, max_edges / (kChunk + 1)); }
+// Item i of the chunk pass: false if it is no chunk of a row that fits, else v = the row's node (-1: none) and [cb, ce) = the chunk's
+// entries.  With a max_edges below the truth the entries of a row that did not fit were never written: an entry counts only if it
+// names a row whose chunk range fits and holds i (the ranges are disjoint, so a stale value cannot pass).  Nothing is read through an
+// entry that names no row.  One exit on purpose: with a return per refusal hipcc schedules embed_chunk_kernel's walk so that a trip
+// waits for all of its rows before the first fma (measured: sage_embed_grad 252 us against 245).
+template <bool UNIFORM>
+__device__ inline bool chunk_item(int64_t i, const int32_t* __restrict__ item_row, const int64_t* __restrict__ rowptr, int64_t num_nodes,
+                                  const int32_t* __restrict__ nodes, int n, int64_t total, const int64_t* __restrict__ off, int64_t cap,
+                                  int32_t& v, int64_t& cb, int64_t& ce) {
+    const int r = bcast<UNIFORM>(item_row[i]);
+    bool mine = r >= 0 && r < n;
+    int64_t b = 0, e = 0, o = 0;
+    v = -1;
+    if (mine) {
+        row_span<UNIFORM>(rowptr, num_nodes, nodes, r, total, v, b, e);
+        const int64_t k = long_chunks(e - b);
+        o = bcast<UNIFORM>(off[r]);
+        mine = !(k == 0 || o + k > cap || i < o || i >= o + k);
+    }
+    cb = b + (i - o) * kChunk;
+    ce = min(cb + kChunk, e);
+    return mine;
+}
+
+// THE arithmetic of a row, the only copy of it: lane columns [c0, c0 + width of V) of the total of row [b, e), whose k chunks start
+// at item o.  term(b, e, acc) is the file's walker: acc += the terms of entries [b, e) in stored order.  ok: the lane holds columns.
+template <typename V, typename Term>
+__device__ inline V chunked_row_sum(int64_t k, int64_t o, int64_t cap, const float* __restrict__ partials, int dim, int c0, bool ok,
+                                    int64_t b, int64_t e, Term term) {
+    V s;
+    vfill(s, 0.f);
+    if (chunks_fit(k, o, cap)) {                      // the chunk pass summed this row's chunks
+        if (ok)
+            for (int64_t c = 0; c < k; ++c) vadd(s, *reinterpret_cast<const V*>(partials + (o + c) * dim + c0));
+    } else if (__builtin_expect(k == 0, 1)) {         // nearly every row, so the straight path: as a taken branch to the end of the
+                                                      // kernel it cost sage_csr_sum, whose groups are mostly empty, 2 % (0.349 ms for 0.342)
+        term(b, e, s);
+    } else {                                          // long row without workspace room: the chunk pass's sums, here
+        for (int64_t c = 0; c < k; ++c) {
+            V p;
+            vfill(p, 0.f);
+            term(b + c * kChunk, min(b + (c + 1) * kChunk, e), p);
+            vadd(s, p);
+        }
+    }
+    return s;
+}
+
+// acc += table rows of col[b..e) in stored order (the sage_gather.hip inner loop: ids broadcast by readlane, 8 rows in flight).
+// b, e wave-uniform.  SELF: found |= some entry of the range is node v (compiled out otherwise: v and found are not touched).
+// IDX: the id is a node id, clamped into [0, last_node]; the row read is index[id], clamped into [0, last_row].
+template <int VEC, bool IDX, bool SELF>
+__device__ inline void sum_edges(const int32_t* __restrict__ col, int64_t b, int64_t e, const float* __restrict__ table, int64_t ld,
+                                 int last_row, int c0, bool ok, int32_t v, typename VecT<VEC>::type& acc, bool& found,
+                                 const int32_t* __restrict__ index, int last_node) {
+    using V = typename VecT<VEC>::type;
+    const int lane = sage_lane();
+    for (int64_t base = b; base < e; base += kWave) {
+        const int m = (int)min((int64_t)kWave, e - base);
+        const int raw = (lane < m) ? col[base + lane] : -1;
+        if constexpr (SELF)
+            if (__any(lane < m && raw == v)) found = true;
+        int myid;
+        if constexpr (IDX) {
+            const int node = min(max(raw, 0), last_node);                            // never read outside index[]
+            myid = min(max(lane < m ? index[node] : 0, 0), last_row);                // ... nor outside embed[]
+        } else {
+            myid = min(max(raw, 0), last_row);           // never read outside the table
+        }
+        for (int j0 = 0; j0 < m; j0 += 8) {
+            V t[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                const int id = __builtin_amdgcn_readlane(myid, min(j0 + u, m - 1));
+                if (ok) t[u] = *reinterpret_cast<const V*>(table + (int64_t)id * ld + c0);
+                else vfill(t[u], 0.f);
+            }
+#pragma unroll
+            for (int u = 0; u < 8; ++u)
+                if (j0 + u < m) vadd(acc, t[u]);
+        }
+    }
+}
+
+// ---- host ---------------------------------------------------------------------------------------------------------------------------
+// A workspace is cut front to back into 256-byte aligned pieces; every take aligns on its own, so a layout's total does not depend on
+// the order of its fields.
+struct WsCursor {
+    size_t off = 0;
+    size_t take(size_t bytes) {
+        const size_t o = off;
+        off = align256(off + std::max<size_t>(bytes, 1));
+        return o;
+    }
+};
+
+// What the chunk split of `rows` rows needs of a workspace; every file's layout holds one beside its own fields.
+struct ChunkWs {
+    size_t off, carry, item_row, partials;
+    int64_t cap;       // item entries (= partial rows) the workspace holds
+    int64_t nblocks;   // count-kernel blocks
+};
+
+// Item entries a workspace sized for max_edges holds: the chunks of all long rows are at most floor(E_sel / E) + (number of long
+// rows), and a long row has more than E edges.  false: more than an int32 item index reaches.  rows, max_edges >= 0.
+inline bool chunk_ws(int64_t rows, int64_t max_edges, int32_t dim, WsCursor& cur, ChunkWs* C) {
+    C->cap = max_edges / kChunk + std::min<int64_t>(rows, max_edges / (kChunk + 1));
+    if (C->cap >= (1ll << 31)) return false;
+    C->nblocks = (rows + kCountTile - 1) / kCountTile;
+    C->off = cur.take((size_t)rows * 8);
+    C->carry = cur.take((size_t)(C->nblocks + 1) * 8);
+    C->item_row = cur.take((size_t)C->cap * 4);
+    C->partials = cur.take((size_t)C->cap * (size_t)dim * 4);
+    return true;
+}
+
+// The arrays of a ChunkWs inside a workspace, as the chunk and row kernels take them.
+struct ChunkPlan {
+    int64_t* off;
+    int64_t* carry;
+    int32_t* item_row;
+    float* partials;
+    int64_t cap;
+    int nb;
+};
+
+// Launches 1-3 over the n rows of (rowptr, nodes): afterwards off[r] is row r's first item, carry[nb] the number of items, and the
+// items that fit name their rows.
+inline int csr_chunk_plan(const int64_t* rowptr, int64_t num_nodes, const int32_t* nodes, int n, void* workspace, const ChunkWs& C,
+                          hipStream_t st, ChunkPlan* P) {
+    char* ws = (char*)workspace;
+    *P = ChunkPlan{(int64_t*)(ws + C.off), (int64_t*)(ws + C.carry), (int32_t*)(ws + C.item_row), (float*)(ws + C.partials), C.cap, (int)C.nblocks};
+    hipLaunchKernelGGL(csr_count_kernel, dim3(P->nb), dim3(kCountThreads), 0, st, rowptr, num_nodes, nodes, n, P->off, P->carry);
+    SAGE_CHECK_LAUNCH("csr_count_kernel");
+    hipLaunchKernelGGL(csr_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, P->carry, P->nb);
+    SAGE_CHECK_LAUNCH("csr_carry_kernel");
+    hipLaunchKernelGGL(csr_expand_kernel, dim3(sage_cdiv(n, 256)), dim3(256), 0, st, rowptr, num_nodes, nodes, n, P->off, (const int64_t*)P->carry,
+                       C.cap, P->item_row);
+    SAGE_CHECK_LAUNCH("csr_expand_kernel");
+    return SAGE_OK;
+}
+
+// The last refusals of every entry: a workspace too small (or none), then one that is not aligned.
+inline int csr_workspace_check(const char* name, const void* workspace, size_t workspace_bytes, size_t need) {
+    if (workspace_bytes < need || !workspace) {
+        sage_set_error("%s: workspace of %zu bytes, %zu needed", name, workspace_bytes, need);
+        return SAGE_ENOSPACE;
+    }
+    SAGE_REQUIRE(sage_aligned(workspace, 256), "%s: workspace not 256-byte aligned", name);
+    return SAGE_OK;
+}
 
 }  // namespace

@@ -15,8 +15,12 @@
 // The item list is sized on the host from max_edges.  A caller whose bound is too small costs speed only: a long row
 // whose chunks do not fit is summed chunk by chunk by its row wave, with the same operations in the same order.
 //
-// Arithmetic of a row (its bits depend on nothing else): p_c = 0 + t_0 + t_1 + ... over chunk c's edges in CSR order;
-// S = 0 + p_0 + p_1 + ...; S += self row (set union, aggregators.py:50-51); out = S * (1 / count).
+// Launches 1-3, the item check of launch 4 and the three ways launch 5 totals a row are sage_csr_common.h's (csr_chunk_plan,
+// chunk_item, chunked_row_sum), shared with sage_csr_sum.hip, sage_csr_mean_backward.hip and sage_embed_grad.hip; this file owns the
+// has_self flags and what follows a row's total.
+//
+// Arithmetic of a row (its bits depend on nothing else): p_c = 0 + t_0 + t_1 + ... over chunk c's edges in CSR order (sum_edges);
+// S = 0 + p_0 + p_1 + ... (chunked_row_sum); S += self row (set union, aggregators.py:50-51); out = S * (1 / count).
 //
 // IDX instantiations (sage_csr_mean_indexed): the table is virtual, T[v] = embed[index[v]] (aggregators.py:68-71), and only the
 // ADDRESS of a row changes: the lane that loads col[base + lane] also loads index[] of the clamped id, the self row is read
@@ -26,60 +30,17 @@
 namespace {
 
 struct CsrLayout {
-    size_t off, carry, item_row, has_self, partials, total;
-    int64_t cap;       // item entries (= partial rows) the workspace holds
-    int64_t nblocks;   // count-kernel blocks
+    ChunkWs c;
+    size_t has_self, total;
 };
 
 bool csr_layout(int32_t n, int64_t max_edges, int32_t dim, CsrLayout* L) {
     if (n < 0 || max_edges < 0 || dim < 1) return false;
-    L->cap = csr_item_cap(n, max_edges);
-    if (L->cap >= (1ll << 31)) return false;
-    L->nblocks = ((int64_t)n + kCountTile - 1) / kCountTile;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align256(off + std::max<size_t>(bytes, 1)); return o; };
-    L->off = take((size_t)n * 8);
-    L->carry = take((size_t)(L->nblocks + 1) * 8);
-    L->item_row = take((size_t)L->cap * 4);
-    L->has_self = take((size_t)L->cap * 4);
-    L->partials = take((size_t)L->cap * (size_t)dim * 4);
-    L->total = off;
+    WsCursor cur;
+    if (!chunk_ws(n, max_edges, dim, cur, &L->c)) return false;
+    L->has_self = cur.take((size_t)L->c.cap * 4);
+    L->total = cur.off;
     return true;
-}
-
-// acc += table rows of col[b..e) in edge order (the sage_gather.hip inner loop: ids broadcast by readlane, 8 rows in flight).
-// b, e wave-uniform.  found |= some edge of the range is node v.
-// IDX: the id is a node id, clamped into [0, last_node]; the row read is index[id], clamped into [0, last_row].
-template <int VEC, bool IDX>
-__device__ inline void sum_edges(const int32_t* __restrict__ col, int64_t b, int64_t e, const float* __restrict__ table, int64_t ld,
-                                 int last_row, int c0, bool ok, int32_t v, typename VecT<VEC>::type& acc, bool& found,
-                                 const int32_t* __restrict__ index, int last_node) {
-    using V = typename VecT<VEC>::type;
-    const int lane = sage_lane();
-    for (int64_t base = b; base < e; base += kWave) {
-        const int m = (int)min((int64_t)kWave, e - base);
-        const int raw = (lane < m) ? col[base + lane] : -1;
-        if (__any(lane < m && raw == v)) found = true;
-        int myid;
-        if constexpr (IDX) {
-            const int node = min(max(raw, 0), last_node);                            // never read outside index[]
-            myid = min(max(lane < m ? index[node] : 0, 0), last_row);                // ... nor outside embed[]
-        } else {
-            myid = min(max(raw, 0), last_row);           // never read outside the table
-        }
-        for (int j0 = 0; j0 < m; j0 += 8) {
-            V t[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int id = __builtin_amdgcn_readlane(myid, min(j0 + u, m - 1));
-                if (ok) t[u] = *reinterpret_cast<const V*>(table + (int64_t)id * ld + c0);
-                else vfill(t[u], 0.f);
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (j0 + u < m) vadd(acc, t[u]);
-        }
-    }
 }
 
 // 4. one wave per item (row, chunk): partials[item] := the chunk's sum, has_self[item] := the chunk holds node v
@@ -97,27 +58,16 @@ __global__ __launch_bounds__(256) void csr_chunk_kernel(const int64_t* __restric
     const int64_t items = min(carry[nb], cap);
     const int64_t total = rowptr[num_nodes];
     for (int64_t i = wave; i < items; i += nwaves) {
-        // With a max_edges below the truth the entries of a row that did not fit were never written: take an entry only if
-        // it names a row whose chunk range fits and holds i (the ranges are disjoint, so a stale value cannot pass)
-        const int r = __builtin_amdgcn_readfirstlane(item_row[i]);
-        if (r < 0 || r >= n) continue;
         int32_t v;
-        int64_t b, e;
-        row_span(rowptr, num_nodes, nodes, r, total, v, b, e);
-        v = __builtin_amdgcn_readfirstlane(v);
-        b = uniform64(b);
-        e = uniform64(e);
-        const int64_t k = long_chunks(e - b), o = uniform64(off[r]);
-        if (k == 0 || o + k > cap || i < o || i >= o + k) continue;
-        const int64_t cb = b + (i - o) * kChunk;
-        const int64_t ce = min(cb + kChunk, e);
+        int64_t cb, ce;
+        if (!chunk_item<true>(i, item_row, rowptr, num_nodes, nodes, n, total, off, cap, v, cb, ce)) continue;
         bool found = false;
         for (int cbk = 0; cbk < dim; cbk += kWave * VEC) {
             const int c0 = cbk + lane * VEC;
             const bool ok = c0 < dim;
             V acc;
             vfill(acc, 0.f);
-            sum_edges<VEC, IDX>(col, cb, ce, table, ld, table_rows - 1, c0, ok, v, acc, found, index, (int)num_nodes - 1);
+            sum_edges<VEC, IDX, true>(col, cb, ce, table, ld, table_rows - 1, c0, ok, v, acc, found, index, (int)num_nodes - 1);
             if (ok) *reinterpret_cast<V*>(partials + i * dim + c0) = acc;
         }
         if (lane == 0) has_self[i] = found ? 1 : 0;
@@ -144,16 +94,12 @@ __global__ __launch_bounds__(256) void csr_row_kernel(const int64_t* __restrict_
     for (int r = wave; r < n; r += nwaves) {
         int32_t v;
         int64_t b, e;
-        row_span(rowptr, num_nodes, nodes, r, total, v, b, e);
-        v = __builtin_amdgcn_readfirstlane(v);
-        b = uniform64(b);
-        e = uniform64(e);
+        row_span<true>(rowptr, num_nodes, nodes, r, total, v, b, e);
         const int64_t deg = e - b;
         const int64_t k = long_chunks(deg);
-        const int64_t o = k > 0 ? uniform64(off[r]) : 0;
-        const bool split = k > 0 && o + k <= cap;        // the chunk pass summed this row's chunks
+        const int64_t o = first_item<true>(off, r, k);
         bool found = false;
-        if (split) {
+        if (chunks_fit(k, o, cap)) {                     // the chunk pass looked for node v in this row's chunks
             bool f = false;
             for (int64_t c = lane; c < k; c += kWave) f |= has_self[o + c] != 0;
             found = __any(f);
@@ -161,22 +107,9 @@ __global__ __launch_bounds__(256) void csr_row_kernel(const int64_t* __restrict_
         for (int cb = 0; cb < dim; cb += kWave * VEC) {
             const int c0 = cb + lane * VEC;
             const bool ok = c0 < dim;
-            V s;
-            vfill(s, 0.f);
-            if (split) {
-                if (ok)
-                    for (int64_t c = 0; c < k; ++c) vadd(s, *reinterpret_cast<const V*>(partials + (o + c) * dim + c0));
-            } else if (k == 0) {
-                sum_edges<VEC, IDX>(col, b, e, table, ld, last_row, c0, ok, v, s, found, index, last_node);
-            } else {                                      // long row without workspace room: the chunk pass's sums, here
-                for (int64_t c = 0; c < k; ++c) {
-                    V p;
-                    vfill(p, 0.f);
-                    sum_edges<VEC, IDX>(col, b + c * kChunk, min(b + (c + 1) * kChunk, e), table, ld, last_row, c0, ok, v, p, found, index,
-                                        last_node);
-                    vadd(s, p);
-                }
-            }
+            V s = chunked_row_sum<V>(k, o, cap, partials, dim, c0, ok, b, e, [&](int64_t tb, int64_t te, V& acc) {
+                sum_edges<VEC, IDX, true>(col, tb, te, table, ld, last_row, c0, ok, v, acc, found, index, last_node);
+            });
             const bool extra = self_loop && v >= 0 && !found;   // aggregators.py:50-51: set union
             if (extra && ok) {
                 int self;                                       // v is in [0, num_nodes) here
@@ -202,33 +135,35 @@ extern "C" size_t sage_csr_mean_workspace_bytes(int32_t n, int64_t max_edges, in
     return csr_layout(n, max_edges, dim, &L) ? L.total : 0;
 }
 
-// The five launches, for the plain table (index == nullptr) and for the virtual one.  Arguments are validated by the entries.
-static int csr_mean_launch(const int64_t* rowptr, const int32_t* col, int64_t num_nodes, const int32_t* nodes, int32_t n,
-                           const int32_t* index, const float* table, int64_t table_rows, int64_t ld, int32_t dim, int32_t self_loop,
-                           const int32_t* any_nonempty, float* out, int64_t ldo, void* workspace, const CsrLayout& L,
-                           sage_stream_t stream) {
+// Both entries: the refusals (shapes first, then pointers, then the workspace: a bad shape is reported as such whatever the pointers
+// are) under the entry's `name` and its word for the table's rows, then the five launches, for the plain table (index == nullptr,
+// indexed false) and for the virtual one.
+static int csr_mean_run(const char* name, const char* rows_name, bool indexed, const int64_t* rowptr, const int32_t* col, int64_t num_nodes,
+                        const int32_t* nodes, int32_t n, int64_t max_edges, const int32_t* index, const float* table, int64_t table_rows,
+                        int64_t ld, int32_t dim, int32_t self_loop, const int32_t* any_nonempty, float* out, int64_t ldo, void* workspace,
+                        size_t workspace_bytes, sage_stream_t stream) {
+    SAGE_REQUIRE(num_nodes >= 0 && num_nodes < (1ll << 31), "%s: num_nodes = %lld", name, (long long)num_nodes);
+    SAGE_REQUIRE(n >= 0 && (nodes || n <= num_nodes), "%s: n = %d rows for %lld nodes without a node list", name, n, (long long)num_nodes);
+    SAGE_REQUIRE(max_edges >= 0, "%s: max_edges = %lld", name, (long long)max_edges);
+    SAGE_REQUIRE(dim >= 1 && ld >= dim && ldo >= dim, "%s: dim = %d, ld = %lld, ldo = %lld", name, dim, (long long)ld, (long long)ldo);
+    SAGE_REQUIRE(table_rows >= 1 && table_rows < (1ll << 31), "%s: %s = %lld", name, rows_name, (long long)table_rows);
+    SAGE_REQUIRE(self_loop == 0 || self_loop == 1, "%s: self_loop = %d", name, self_loop);
+    SAGE_REQUIRE(rowptr && col && (index || !indexed) && table && out, "%s: NULL array", name);
+    CsrLayout L;
+    SAGE_REQUIRE(csr_layout(n, max_edges, dim, &L), "%s: n = %d, max_edges = %lld, dim = %d out of range", name, n, (long long)max_edges, dim);
+    if (const int rc = csr_workspace_check(name, workspace, workspace_bytes, L.total)) return rc;
+    if (n == 0) return SAGE_OK;
+
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    int64_t* off = (int64_t*)(ws + L.off);
-    int64_t* carry = (int64_t*)(ws + L.carry);
-    int32_t* item_row = (int32_t*)(ws + L.item_row);
-    int32_t* has_self = (int32_t*)(ws + L.has_self);
-    float* partials = (float*)(ws + L.partials);
-    const int nb = (int)L.nblocks;
-
-    hipLaunchKernelGGL(csr_count_kernel, dim3(nb), dim3(kCountThreads), 0, st, rowptr, num_nodes, nodes, n, off, carry);
-    SAGE_CHECK_LAUNCH("csr_count_kernel");
-    hipLaunchKernelGGL(csr_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, carry, nb);
-    SAGE_CHECK_LAUNCH("csr_carry_kernel");
-    hipLaunchKernelGGL(csr_expand_kernel, dim3(sage_cdiv(n, 256)), dim3(256), 0, st, rowptr, num_nodes, nodes, n, off, carry, L.cap, item_row);
-    SAGE_CHECK_LAUNCH("csr_expand_kernel");
-
+    ChunkPlan P;
+    if (const int rc = csr_chunk_plan(rowptr, num_nodes, nodes, n, workspace, L.c, st, &P)) return rc;
+    int32_t* has_self = (int32_t*)((char*)workspace + L.has_self);
     const bool vec4 = (dim % 4 == 0) && (ld % 4 == 0) && (ldo % 4 == 0) && sage_aligned(table, 16) && sage_aligned(out, 16);
-    if (L.cap > 0) {
-        const int blocks = (int)std::min<int64_t>((L.cap + 3) / 4, kNumCU * 8);
+    if (P.cap > 0) {
+        const int blocks = (int)std::min<int64_t>((P.cap + 3) / 4, kNumCU * 8);
 #define SAGE_CSR_CHUNK(VEC, IDX)                                                                                                       \
     hipLaunchKernelGGL((csr_chunk_kernel<VEC, IDX>), dim3(blocks), dim3(256), 0, st, rowptr, col, num_nodes, nodes, n, table, (int)table_rows, \
-                       ld, dim, off, carry, nb, L.cap, item_row, has_self, partials, index)
+                       ld, dim, P.off, P.carry, P.nb, P.cap, P.item_row, has_self, P.partials, index)
         if (index) { if (vec4) SAGE_CSR_CHUNK(4, true); else SAGE_CSR_CHUNK(1, true); }
         else { if (vec4) SAGE_CSR_CHUNK(4, false); else SAGE_CSR_CHUNK(1, false); }
 #undef SAGE_CSR_CHUNK
@@ -237,7 +172,7 @@ static int csr_mean_launch(const int64_t* rowptr, const int32_t* col, int64_t nu
     const int blocks = std::min(sage_cdiv(n, 4), kNumCU * 8);
 #define SAGE_CSR_ROW(VEC, IDX)                                                                                                            \
     hipLaunchKernelGGL((csr_row_kernel<VEC, IDX>), dim3(blocks), dim3(256), 0, st, rowptr, col, num_nodes, nodes, n, table, (int)table_rows, ld, \
-                       dim, self_loop, any_nonempty, off, L.cap, has_self, partials, out, ldo, index)
+                       dim, self_loop, any_nonempty, P.off, P.cap, has_self, P.partials, out, ldo, index)
     if (index) { if (vec4) SAGE_CSR_ROW(4, true); else SAGE_CSR_ROW(1, true); }
     else { if (vec4) SAGE_CSR_ROW(4, false); else SAGE_CSR_ROW(1, false); }
 #undef SAGE_CSR_ROW
@@ -249,48 +184,14 @@ extern "C" int sage_csr_mean(const int64_t* rowptr, const int32_t* col, int64_t 
                              int64_t max_edges, const float* table, int64_t table_rows, int64_t ld, int32_t dim, int32_t self_loop,
                              const int32_t* any_nonempty, float* out, int64_t ldo, void* workspace, size_t workspace_bytes,
                              sage_stream_t stream) {
-    // shapes first, then pointers: a bad shape is reported as such whatever the pointers are
-    SAGE_REQUIRE(num_nodes >= 0 && num_nodes < (1ll << 31), "csr_mean: num_nodes = %lld", (long long)num_nodes);
-    SAGE_REQUIRE(n >= 0 && (nodes || n <= num_nodes), "csr_mean: n = %d rows for %lld nodes without a node list", n, (long long)num_nodes);
-    SAGE_REQUIRE(max_edges >= 0, "csr_mean: max_edges = %lld", (long long)max_edges);
-    SAGE_REQUIRE(dim >= 1 && ld >= dim && ldo >= dim, "csr_mean: dim = %d, ld = %lld, ldo = %lld", dim, (long long)ld, (long long)ldo);
-    SAGE_REQUIRE(table_rows >= 1 && table_rows < (1ll << 31), "csr_mean: table_rows = %lld", (long long)table_rows);
-    SAGE_REQUIRE(self_loop == 0 || self_loop == 1, "csr_mean: self_loop = %d", self_loop);
-    SAGE_REQUIRE(rowptr && col && table && out, "csr_mean: NULL array");
-    CsrLayout L;
-    SAGE_REQUIRE(csr_layout(n, max_edges, dim, &L), "csr_mean: n = %d, max_edges = %lld, dim = %d out of range", n, (long long)max_edges, dim);
-    if (workspace_bytes < L.total || !workspace) {
-        sage_set_error("csr_mean: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
-        return SAGE_ENOSPACE;
-    }
-    SAGE_REQUIRE(sage_aligned(workspace, 256), "csr_mean: workspace not 256-byte aligned");
-    if (n == 0) return SAGE_OK;
-    return csr_mean_launch(rowptr, col, num_nodes, nodes, n, nullptr, table, table_rows, ld, dim, self_loop, any_nonempty, out, ldo, workspace, L,
-                           stream);
+    return csr_mean_run("csr_mean", "table_rows", false, rowptr, col, num_nodes, nodes, n, max_edges, nullptr, table, table_rows, ld, dim,
+                        self_loop, any_nonempty, out, ldo, workspace, workspace_bytes, stream);
 }
 
 extern "C" int sage_csr_mean_indexed(const int64_t* rowptr, const int32_t* col, int64_t num_nodes, const int32_t* nodes, int32_t n,
                                      int64_t max_edges, const int32_t* index, const float* embed, int64_t embed_rows, int64_t ld, int32_t dim,
                                      int32_t self_loop, const int32_t* any_nonempty, float* out, int64_t ldo, void* workspace,
                                      size_t workspace_bytes, sage_stream_t stream) {
-    // shapes first, then pointers, then the workspace: sage_csr_mean's order
-    SAGE_REQUIRE(num_nodes >= 0 && num_nodes < (1ll << 31), "csr_mean_indexed: num_nodes = %lld", (long long)num_nodes);
-    SAGE_REQUIRE(n >= 0 && (nodes || n <= num_nodes), "csr_mean_indexed: n = %d rows for %lld nodes without a node list", n,
-                 (long long)num_nodes);
-    SAGE_REQUIRE(max_edges >= 0, "csr_mean_indexed: max_edges = %lld", (long long)max_edges);
-    SAGE_REQUIRE(dim >= 1 && ld >= dim && ldo >= dim, "csr_mean_indexed: dim = %d, ld = %lld, ldo = %lld", dim, (long long)ld, (long long)ldo);
-    SAGE_REQUIRE(embed_rows >= 1 && embed_rows < (1ll << 31), "csr_mean_indexed: embed_rows = %lld", (long long)embed_rows);
-    SAGE_REQUIRE(self_loop == 0 || self_loop == 1, "csr_mean_indexed: self_loop = %d", self_loop);
-    SAGE_REQUIRE(rowptr && col && index && embed && out, "csr_mean_indexed: NULL array");
-    CsrLayout L;
-    SAGE_REQUIRE(csr_layout(n, max_edges, dim, &L), "csr_mean_indexed: n = %d, max_edges = %lld, dim = %d out of range", n,
-                 (long long)max_edges, dim);
-    if (workspace_bytes < L.total || !workspace) {
-        sage_set_error("csr_mean_indexed: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
-        return SAGE_ENOSPACE;
-    }
-    SAGE_REQUIRE(sage_aligned(workspace, 256), "csr_mean_indexed: workspace not 256-byte aligned");
-    if (n == 0) return SAGE_OK;
-    return csr_mean_launch(rowptr, col, num_nodes, nodes, n, index, embed, embed_rows, ld, dim, self_loop, any_nonempty, out, ldo, workspace, L,
-                           stream);
+    return csr_mean_run("csr_mean_indexed", "embed_rows", true, rowptr, col, num_nodes, nodes, n, max_edges, index, embed, embed_rows, ld, dim,
+                        self_loop, any_nonempty, out, ldo, workspace, workspace_bytes, stream);
 }

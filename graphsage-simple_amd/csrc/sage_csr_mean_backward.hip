@@ -12,13 +12,14 @@
 //               rows, so a hub costs its chunks' waves what any other 512 entries cost; the row of an entry is found by a
 //               bisection of rowptr inside the rows the wave's 512 entries span.  Racing stores all store 1.   (self_loop only)
 //   c. weight   per node: flag[v] := extra_v (in place of found), w[v] := c_v > 0 ? 1.0f / (float)c_v : 0
-//   1-3. count, carry, expand on the transposed rows (sage_csr_common.h)
+//   1-3. count, carry, expand on the transposed rows (sage_csr_common.h: csr_chunk_plan)
 //   4. chunk    one wave per item: partials[item] := the chunk's weighted sum
 //   5. rows     one wave per row: short rows summed in place; long rows = their partials in chunk order; self term; store
 //
 // Arithmetic of a row (its bits depend on nothing else): p_c = fma(w_x, g_x, ...fma(w_x0, g_x0, 0)) over chunk c's entries in
 // stored order; S = 0 + p_0 + p_1 + ...; S = fma(w_u, g_u, S) if extra_u; grad_table[r] = S.  Every term is ONE fma, in the
-// chunk pass and in the fall-back alike (sum_weighted is the only place that forms a term).
+// chunk pass and in the fall-back alike: sum_weighted is the only place that forms a term, and sage_csr_common.h's chunked_row_sum
+// the only place that adds a row's terms and partials up (with its item check, chunk_item, shared by the four files of this family).
 //
 // GROUPED instantiations (sage_csr_mean_backward_grouped): the gradient of an embedding read as embed[index[v]] through the
 // forward.  The caller's rectangular CSR has one row per EMBEDDING row and lists, for every node that reads it, that node's
@@ -29,32 +30,19 @@
 namespace {
 
 struct BwdLayout {
-    size_t off, carry, item_row, partials, weight, flag, total;
-    int64_t cap;       // item entries (= partial rows) the workspace holds
-    int64_t nblocks;   // count-kernel blocks
+    ChunkWs c;
+    size_t weight, flag, total;
 };
 
 bool bwd_layout(int64_t num_nodes, int32_t n, int64_t max_edges, int32_t dim, BwdLayout* L) {
     if (num_nodes < 0 || num_nodes >= (1ll << 31) || n < 0 || max_edges < 0 || dim < 1) return false;
-    L->cap = csr_item_cap(n, max_edges);
-    if (L->cap >= (1ll << 31)) return false;
-    L->nblocks = ((int64_t)n + kCountTile - 1) / kCountTile;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align256(off + std::max<size_t>(bytes, 1)); return o; };
-    L->off = take((size_t)n * 8);
-    L->carry = take((size_t)(L->nblocks + 1) * 8);
-    L->item_row = take((size_t)L->cap * 4);
-    L->partials = take((size_t)L->cap * (size_t)dim * 4);
-    L->weight = take((size_t)num_nodes * 4);
-    L->flag = take((size_t)num_nodes * 4);
-    L->total = off;
+    WsCursor cur;
+    if (!chunk_ws(n, max_edges, dim, cur, &L->c)) return false;
+    L->weight = cur.take((size_t)num_nodes * 4);
+    L->flag = cur.take((size_t)num_nodes * 4);
+    L->total = cur.off;
     return true;
 }
-
-__device__ inline void vfma(float4& a, float s, const float4& b) {
-    a.x = __builtin_fmaf(s, b.x, a.x); a.y = __builtin_fmaf(s, b.y, a.y); a.z = __builtin_fmaf(s, b.z, a.z); a.w = __builtin_fmaf(s, b.w, a.w);
-}
-__device__ inline void vfma(float& a, float s, const float& b) { a = __builtin_fmaf(s, b, a); }
 
 // The largest r in [lo, hi] with rowptr[r] <= x (lo if there is none).  At most 32 steps whatever rowptr holds; r stays in [lo, hi].
 __device__ inline int32_t row_of(const int64_t* __restrict__ rowptr, int32_t lo, int32_t hi, int64_t x) {
@@ -147,18 +135,9 @@ __global__ __launch_bounds__(256) void bwd_chunk_kernel(const int64_t* __restric
     const int64_t total = rowptr_t[num_nodes];
     const int last_row = (int)(GROUPED ? num_src : num_nodes) - 1;      // GROUPED: num_nodes counts the rows (groups), num_src the nodes
     for (int64_t i = wave; i < items; i += nwaves) {
-        // as in the forward: an entry counts only if it names a row whose chunk range fits the workspace and holds i
-        const int r = __builtin_amdgcn_readfirstlane(item_row[i]);
-        if (r < 0 || r >= n) continue;
         int32_t v;
-        int64_t b, e;
-        row_span(rowptr_t, num_nodes, nodes, r, total, v, b, e);
-        b = uniform64(b);
-        e = uniform64(e);
-        const int64_t k = long_chunks(e - b), o = uniform64(off[r]);
-        if (k == 0 || o + k > cap || i < o || i >= o + k) continue;
-        const int64_t cb = b + (i - o) * kChunk;
-        const int64_t ce = min(cb + kChunk, e);
+        int64_t cb, ce;
+        if (!chunk_item<true>(i, item_row, rowptr_t, num_nodes, nodes, n, total, off, cap, v, cb, ce)) continue;
         for (int cbk = 0; cbk < dim; cbk += kWave * VEC) {
             const int c0 = cbk + lane * VEC;
             const bool ok = c0 < dim;
@@ -187,33 +166,17 @@ __global__ __launch_bounds__(256) void bwd_row_kernel(const int64_t* __restrict_
     for (int r = wave; r < n; r += nwaves) {
         int32_t u;
         int64_t b, e;
-        row_span(rowptr_t, num_nodes, nodes, r, total, u, b, e);
-        u = __builtin_amdgcn_readfirstlane(u);
-        b = uniform64(b);
-        e = uniform64(e);
+        row_span<true>(rowptr_t, num_nodes, nodes, r, total, u, b, e);
         const int64_t k = long_chunks(e - b);
-        const int64_t o = k > 0 ? uniform64(off[r]) : 0;
-        const bool split = k > 0 && o + k <= cap;        // the chunk pass summed this row's chunks
+        const int64_t o = first_item<true>(off, r, k);
         const bool extra = !GROUPED && u >= 0 && __builtin_amdgcn_readfirstlane(flag[max(u, 0)]) != 0;   // GROUPED: the list holds the self entries
         const float wu = extra ? __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(w[u]))) : 0.f;
         for (int cb = 0; cb < dim; cb += kWave * VEC) {
             const int c0 = cb + lane * VEC;
             const bool ok = c0 < dim;
-            V s;
-            vfill(s, 0.f);
-            if (split) {
-                if (ok)
-                    for (int64_t c = 0; c < k; ++c) vadd(s, *reinterpret_cast<const V*>(partials + (o + c) * dim + c0));
-            } else if (k == 0) {
-                sum_weighted<VEC>(col_t, b, e, w, g, ldg, last_row, c0, ok, s);
-            } else {                                      // long row without workspace room: the chunk pass's sums, here
-                for (int64_t c = 0; c < k; ++c) {
-                    V p;
-                    vfill(p, 0.f);
-                    sum_weighted<VEC>(col_t, b + c * kChunk, min(b + (c + 1) * kChunk, e), w, g, ldg, last_row, c0, ok, p);
-                    vadd(s, p);
-                }
-            }
+            V s = chunked_row_sum<V>(k, o, cap, partials, dim, c0, ok, b, e, [&](int64_t tb, int64_t te, V& acc) {
+                sum_weighted<VEC>(col_t, tb, te, w, g, ldg, last_row, c0, ok, acc);
+            });
             if (ok) {
                 if (extra) vfma(s, wu, *reinterpret_cast<const V*>(g + (int64_t)u * ldg + c0));   // the self term, last
                 *reinterpret_cast<V*>(grad_table + (int64_t)r * ldgt + c0) = s;
@@ -236,14 +199,8 @@ static int bwd_launch(const int64_t* rowptr, const int32_t* col, const int64_t* 
                       int32_t dim, int32_t self_loop, float* grad_table, int64_t ldgt, void* workspace, const BwdLayout& L,
                       sage_stream_t stream) {
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    int64_t* off = (int64_t*)(ws + L.off);
-    int64_t* carry = (int64_t*)(ws + L.carry);
-    int32_t* item_row = (int32_t*)(ws + L.item_row);
-    float* partials = (float*)(ws + L.partials);
-    float* w = (float*)(ws + L.weight);
-    int32_t* flag = (int32_t*)(ws + L.flag);
-    const int nb = (int)L.nblocks;
+    float* w = (float*)((char*)workspace + L.weight);
+    int32_t* flag = (int32_t*)((char*)workspace + L.flag);
 
     // the weights of the forward's rows.  num_nodes >= 1 here: n > 0 rows without a node list need it, and with one and no nodes
     // every row is empty -- the kernels below then read neither w nor flag
@@ -259,19 +216,15 @@ static int bwd_launch(const int64_t* rowptr, const int32_t* col, const int64_t* 
         SAGE_CHECK_LAUNCH("bwd_weight_kernel");
     }
 
-    hipLaunchKernelGGL(csr_count_kernel, dim3(nb), dim3(kCountThreads), 0, st, rowptr_t, num_rows, nodes, n, off, carry);
-    SAGE_CHECK_LAUNCH("csr_count_kernel");
-    hipLaunchKernelGGL(csr_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, carry, nb);
-    SAGE_CHECK_LAUNCH("csr_carry_kernel");
-    hipLaunchKernelGGL(csr_expand_kernel, dim3(sage_cdiv(n, 256)), dim3(256), 0, st, rowptr_t, num_rows, nodes, n, off, carry, L.cap, item_row);
-    SAGE_CHECK_LAUNCH("csr_expand_kernel");
+    ChunkPlan P;
+    if (const int rc = csr_chunk_plan(rowptr_t, num_rows, nodes, n, workspace, L.c, st, &P)) return rc;
 
     const bool vec4 = (dim % 4 == 0) && (ldg % 4 == 0) && (ldgt % 4 == 0) && sage_aligned(grad_out, 16) && sage_aligned(grad_table, 16);
-    if (L.cap > 0) {
-        const int blocks = (int)std::min<int64_t>((L.cap + 3) / 4, kNumCU * 8);
+    if (P.cap > 0) {
+        const int blocks = (int)std::min<int64_t>((P.cap + 3) / 4, kNumCU * 8);
 #define SAGE_BWD_CHUNK(VEC, GROUPED)                                                                                                    \
     hipLaunchKernelGGL((bwd_chunk_kernel<VEC, GROUPED>), dim3(blocks), dim3(256), 0, st, rowptr_t, col_t, num_rows, nodes, n, w, grad_out, ldg, \
-                       dim, off, carry, nb, L.cap, item_row, partials, num_nodes)
+                       dim, P.off, P.carry, P.nb, P.cap, P.item_row, P.partials, num_nodes)
         if (grouped) { if (vec4) SAGE_BWD_CHUNK(4, true); else SAGE_BWD_CHUNK(1, true); }
         else { if (vec4) SAGE_BWD_CHUNK(4, false); else SAGE_BWD_CHUNK(1, false); }
 #undef SAGE_BWD_CHUNK
@@ -280,7 +233,7 @@ static int bwd_launch(const int64_t* rowptr, const int32_t* col, const int64_t* 
     const int blocks = std::min(sage_cdiv(n, 4), kNumCU * 8);
 #define SAGE_BWD_ROW(VEC, GROUPED)                                                                                                        \
     hipLaunchKernelGGL((bwd_row_kernel<VEC, GROUPED>), dim3(blocks), dim3(256), 0, st, rowptr_t, col_t, num_rows, nodes, n, w, flag, grad_out, ldg, \
-                       dim, off, L.cap, partials, grad_table, ldgt, num_nodes)
+                       dim, P.off, P.cap, P.partials, grad_table, ldgt, num_nodes)
     if (grouped) { if (vec4) SAGE_BWD_ROW(4, true); else SAGE_BWD_ROW(1, true); }
     else { if (vec4) SAGE_BWD_ROW(4, false); else SAGE_BWD_ROW(1, false); }
 #undef SAGE_BWD_ROW
@@ -304,11 +257,7 @@ extern "C" int sage_csr_mean_backward(const int64_t* rowptr, const int32_t* col,
     BwdLayout L;
     SAGE_REQUIRE(bwd_layout(num_nodes, n, max_edges, dim, &L), "csr_mean_backward: n = %d, max_edges = %lld, dim = %d out of range", n,
                  (long long)max_edges, dim);
-    if (workspace_bytes < L.total || !workspace) {
-        sage_set_error("csr_mean_backward: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
-        return SAGE_ENOSPACE;
-    }
-    SAGE_REQUIRE(sage_aligned(workspace, 256), "csr_mean_backward: workspace not 256-byte aligned");
+    if (const int rc = csr_workspace_check("csr_mean_backward", workspace, workspace_bytes, L.total)) return rc;
     if (n == 0) return SAGE_OK;
     return bwd_launch(rowptr, col, rowptr_t, col_t, num_nodes, num_nodes, false, nodes, n, max_edges, grad_out, ldg, dim, self_loop, grad_table,
                       ldgt, workspace, L, stream);
@@ -337,11 +286,7 @@ extern "C" int sage_csr_mean_backward_grouped(const int64_t* rowptr, const int32
     SAGE_REQUIRE(bwd_layout(num_nodes, (int32_t)num_groups, max_edges, dim, &L),
                  "csr_mean_backward_grouped: num_groups = %lld, max_edges = %lld, dim = %d out of range", (long long)num_groups,
                  (long long)max_edges, dim);
-    if (workspace_bytes < L.total || !workspace) {
-        sage_set_error("csr_mean_backward_grouped: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
-        return SAGE_ENOSPACE;
-    }
-    SAGE_REQUIRE(sage_aligned(workspace, 256), "csr_mean_backward_grouped: workspace not 256-byte aligned");
+    if (const int rc = csr_workspace_check("csr_mean_backward_grouped", workspace, workspace_bytes, L.total)) return rc;
     if (num_groups == 0) return SAGE_OK;
     return bwd_launch(rowptr, col, rowptr_gt, col_gt, num_nodes, num_groups, true, nullptr, (int32_t)num_groups, max_edges, grad_out, ldg, dim,
                       self_loop, grad_embed, ldge, workspace, L, stream);

@@ -10,54 +10,61 @@
 //               (padding, dead rows), value = t; 1 / c_t per row
 //   2. sort     hipcub::DeviceRadixSort::SortPairs on the key bits that matter: stable, so (p, j) order survives inside a run
 //   3. rowptr   rowptr[e] = first position whose key is >= e (a binary search per embedding row): a CSR over the sorted list
-//   4-6. count, carry, expand (sage_csr_common.h): runs of more than one chunk get item entries and partial rows
+//   4-6. count, carry, expand (sage_csr_common.h: csr_chunk_plan): runs of more than one chunk get item entries and partial rows
 //   7. chunk    one lane group per item: partials[item] := the chunk's weighted sum
 //   8. rows     one lane group per embedding row: short runs summed in place, long ones = their partials in chunk order; STORE
 // sage_embed_grad_rows (below) is the same sum for the rows that have a term only, with the SGD update of those rows fused in: steps
 // 1, 2, 4-7 unchanged, step 3 a run list of the sorted keys instead of a row pointer over the table, step 8 over the runs.
 // Arithmetic of a row (its bits depend on nothing else): p_c = 0, then p_c = fma(g, w, p_c) over chunk c's terms in (p, j) order
 // (ONE rounding per term: a fused multiply-add, spelled fmaf so that no compiler flag decides); out = 0 + p_0 + p_1 + ... for a
-// run of more than one chunk, out = p_0 for any other.  No float atomics, no host synchronisation, no allocation.
+// run of more than one chunk, out = p_0 for any other.  The terms are weighted_sum's; the item check of step 7 and a row's total are
+// sage_csr_common.h's chunk_item and chunked_row_sum (through run_sum), shared with the three CSR files, here with one lane GROUP per
+// item or row and therefore without their wave broadcasts.  No float atomics, no host synchronisation, no allocation.
 #include <hipcub/hipcub.hpp>
 
 #include "sage_csr_common.h"
 
 namespace {
 
-struct EmbedLayout {
-    size_t keys_in, keys_out, vals_in, vals_out, inv_c, rowptr, off, carry, item_row, partials, cub, total;
+// What both entry points need to lay the terms out and sort them.
+struct SortWs {
+    size_t keys_in, keys_out, vals_in, vals_out, inv_c, cub;
     size_t cub_bytes;
-    int64_t cap, nblocks;
     int slots, bits;
 };
 
-bool embed_layout(int32_t n, int32_t k, int64_t embed_rows, int32_t dim, EmbedLayout* L) {
+bool sort_ws(int32_t n, int32_t k, int64_t embed_rows, int32_t dim, WsCursor& cur, SortWs* S) {
     if (n < 1 || k < 1 || dim < 1 || embed_rows < 1 || embed_rows >= (1ll << 31) || (int64_t)n * k >= (1ll << 31)) return false;
-    L->slots = n * k;
-    L->bits = 1;
-    while ((1ll << L->bits) <= embed_rows) ++L->bits;              // keys are in [0, embed_rows] (the sentinel included)
-    L->cap = csr_item_cap((int32_t)embed_rows, L->slots);          // every long run's chunks fit: at most slots terms in all
-    L->nblocks = (embed_rows + kCountTile - 1) / kCountTile;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align256(off + std::max<size_t>(bytes, 1)); return o; };
-    L->keys_in = take((size_t)L->slots * 4);
-    L->keys_out = take((size_t)L->slots * 4);
-    L->vals_in = take((size_t)L->slots * 4);
-    L->vals_out = take((size_t)L->slots * 4);
-    L->inv_c = take((size_t)n * 4);
-    L->rowptr = take((size_t)(embed_rows + 1) * 8);
-    L->off = take((size_t)embed_rows * 8);
-    L->carry = take((size_t)(L->nblocks + 1) * 8);
-    L->item_row = take((size_t)L->cap * 4);
-    L->partials = take((size_t)L->cap * (size_t)dim * 4);
+    S->slots = n * k;
+    S->bits = 1;
+    while ((1ll << S->bits) <= embed_rows) ++S->bits;              // keys are in [0, embed_rows] (the sentinel included)
+    S->keys_in = cur.take((size_t)S->slots * 4);
+    S->keys_out = cur.take((size_t)S->slots * 4);
+    S->vals_in = cur.take((size_t)S->slots * 4);
+    S->vals_out = cur.take((size_t)S->slots * 4);
+    S->inv_c = cur.take((size_t)n * 4);
     // The sort's temporary.  The library's own size query asks the runtime for the device's architecture, so it answers only where
     // there is a device; the layout has to be host arithmetic.  Reserved here is a bound on what the sort partitions its temporary
     // into: a second key and value array (8 bytes per slot), one look-back word per digit (256) and block of at least 512 slots
-    // (at most 4 bytes per slot at 8 bytes a word), digit histograms of a few KiB.  sage_embed_grad asks the library before it sorts
+    // (at most 4 bytes per slot at 8 bytes a word), digit histograms of a few KiB.  sort_terms asks the library before it sorts
     // and refuses (SAGE_ELAUNCH, nothing sorted) if it ever wanted more.
-    L->cub_bytes = (size_t)L->slots * 16 + 65536;
-    L->cub = take(L->cub_bytes);
-    L->total = off;
+    S->cub_bytes = (size_t)S->slots * 16 + 65536;
+    S->cub = cur.take(S->cub_bytes);
+    return true;
+}
+
+struct EmbedLayout {
+    SortWs s;
+    size_t rowptr, total;
+    ChunkWs c;
+};
+
+bool embed_layout(int32_t n, int32_t k, int64_t embed_rows, int32_t dim, EmbedLayout* L) {
+    WsCursor cur;
+    if (!sort_ws(n, k, embed_rows, dim, cur, &L->s)) return false;
+    L->rowptr = cur.take((size_t)(embed_rows + 1) * 8);
+    if (!chunk_ws(embed_rows, L->s.slots, dim, cur, &L->c)) return false;     // every long run's chunks fit: at most slots terms in all
+    L->total = cur.off;
     return true;
 }
 
@@ -148,15 +155,9 @@ __global__ __launch_bounds__(256) void embed_chunk_kernel(const float* __restric
     const int64_t items = min(carry[nb], cap);
     const int64_t total = rowptr[embed_rows];
     for (int64_t i = gid; i < items; i += ngroups) {
-        // an entry of a row that did not fit was never written: take one only if it names a row whose chunk range fits and holds i
-        const int r = item_row[i];
-        if (r < 0 || r >= embed_rows) continue;
         int32_t v;
-        int64_t b, e;
-        row_span(rowptr, embed_rows, nullptr, r, total, v, b, e);
-        const int64_t kc = long_chunks(e - b), o = off[r];
-        if (kc == 0 || o + kc > cap || i < o || i >= o + kc) continue;
-        const int64_t cb = b + (i - o) * kChunk, ce = min(cb + kChunk, e);
+        int64_t cb, ce;
+        if (!chunk_item<false>(i, item_row, rowptr, embed_rows, nullptr, embed_rows, total, off, cap, v, cb, ce)) continue;
         for (int c0 = gl * 4; c0 < dim; c0 += LG * 4) {              // dim % 4 == 0 (host-checked)
             V4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
             weighted_sum(gagg, ldg, vals, inv_c, cb, ce, c0, acc);
@@ -166,26 +167,14 @@ __global__ __launch_bounds__(256) void embed_chunk_kernel(const float* __restric
 }
 
 // Columns [c0, c0 + 4) of the sum of the run [b, e) of the sorted list, entry r of the row pointer that the chunk pass walked (an
-// embedding row for sage_embed_grad, a run for sage_embed_grad_rows): THE arithmetic of a row, the only copy of it
+// embedding row for sage_embed_grad, a run for sage_embed_grad_rows): chunked_row_sum over weighted_sum's terms.  With this file's cap
+// the chunk pass summed every long run.
 __device__ inline V4 run_sum(const float* __restrict__ gagg, int64_t ldg, int dim, const int32_t* __restrict__ vals,
                              const float* __restrict__ inv_c, const int64_t* __restrict__ off, int64_t cap,
                              const float* __restrict__ partials, int64_t r, int64_t b, int64_t e, int c0) {
     const int64_t kc = long_chunks(e - b);
-    const int64_t o = kc > 0 ? off[r] : 0;
-    const bool split = kc > 0 && o + kc <= cap;                     // the chunk pass summed this row's chunks (always, with this cap)
-    V4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (split) {
-        for (int64_t c = 0; c < kc; ++c) vadd(s, *reinterpret_cast<const V4*>(partials + (o + c) * dim + c0));
-    } else if (kc == 0) {
-        weighted_sum(gagg, ldg, vals, inv_c, b, e, c0, s);
-    } else {                                                         // the chunk pass's sums, here: same operations, same order
-        for (int64_t c = 0; c < kc; ++c) {
-            V4 p = make_float4(0.f, 0.f, 0.f, 0.f);
-            weighted_sum(gagg, ldg, vals, inv_c, b + c * kChunk, min(b + (c + 1) * kChunk, e), c0, p);
-            vadd(s, p);
-        }
-    }
-    return s;
+    return chunked_row_sum<V4>(kc, first_item<false>(off, r, kc), cap, partials, dim, c0, true, b, e,
+                               [&](int64_t tb, int64_t te, V4& acc) { weighted_sum(gagg, ldg, vals, inv_c, tb, te, c0, acc); });
 }
 
 // 8. LG lanes per embedding row
@@ -212,41 +201,25 @@ __global__ __launch_bounds__(256) void embed_row_kernel(const float* __restrict_
 // runptr hold the end of the terms (empty spans), so the count / carry / expand / chunk kernels above walk it as they walk a CSR of
 // runs_cap rows.  runs_cap = min(slots, embed_rows) bounds U on the host.
 struct RowsLayout {
-    size_t keys_in, keys_out, vals_in, vals_out, inv_c, run_row, runptr, heads, end_pos, off, carry, item_row, partials, cub, total;
-    size_t cub_bytes;
-    int64_t cap, nblocks, head_blocks, runs_cap;
-    int slots, bits;
+    SortWs s;
+    size_t run_row, runptr, heads, end_pos, total;
+    ChunkWs c;
+    int64_t head_blocks, runs_cap;
 };
 
 constexpr int kHeadThreads = 256, kHeadIpt = 8, kHeadTile = kHeadThreads * kHeadIpt;
 
 bool rows_layout(int32_t n, int32_t k, int64_t embed_rows, int32_t dim, RowsLayout* L) {
-    if (n < 1 || k < 1 || dim < 1 || embed_rows < 1 || embed_rows >= (1ll << 31) || (int64_t)n * k >= (1ll << 31)) return false;
-    L->slots = n * k;
-    L->bits = 1;
-    while ((1ll << L->bits) <= embed_rows) ++L->bits;              // keys are in [0, embed_rows] (the sentinel included)
-    L->runs_cap = std::min<int64_t>(L->slots, embed_rows);         // distinct rows with a term: what every array below is sized by
-    L->cap = csr_item_cap((int32_t)L->runs_cap, L->slots);
-    L->nblocks = (L->runs_cap + kCountTile - 1) / kCountTile;
-    L->head_blocks = ((int64_t)L->slots + kHeadTile - 1) / kHeadTile;
-    size_t off = 0;
-    auto take = [&](size_t bytes) { size_t o = off; off = align256(off + std::max<size_t>(bytes, 1)); return o; };
-    L->keys_in = take((size_t)L->slots * 4);
-    L->keys_out = take((size_t)L->slots * 4);
-    L->vals_in = take((size_t)L->slots * 4);
-    L->vals_out = take((size_t)L->slots * 4);
-    L->inv_c = take((size_t)n * 4);
-    L->run_row = take((size_t)L->runs_cap * 4);
-    L->runptr = take((size_t)(L->runs_cap + 1) * 8);
-    L->heads = take((size_t)(L->head_blocks + 1) * 8);
-    L->end_pos = take(8);
-    L->off = take((size_t)L->runs_cap * 8);
-    L->carry = take((size_t)(L->nblocks + 1) * 8);
-    L->item_row = take((size_t)L->cap * 4);
-    L->partials = take((size_t)L->cap * (size_t)dim * 4);
-    L->cub_bytes = (size_t)L->slots * 16 + 65536;                  // the sort's temporary: embed_layout's bound and its reasons
-    L->cub = take(L->cub_bytes);
-    L->total = off;
+    WsCursor cur;
+    if (!sort_ws(n, k, embed_rows, dim, cur, &L->s)) return false;
+    L->runs_cap = std::min<int64_t>(L->s.slots, embed_rows);       // distinct rows with a term: what every array below is sized by
+    L->head_blocks = ((int64_t)L->s.slots + kHeadTile - 1) / kHeadTile;
+    L->run_row = cur.take((size_t)L->runs_cap * 4);
+    L->runptr = cur.take((size_t)(L->runs_cap + 1) * 8);
+    L->heads = cur.take((size_t)(L->head_blocks + 1) * 8);
+    L->end_pos = cur.take(8);
+    if (!chunk_ws(L->runs_cap, L->s.slots, dim, cur, &L->c)) return false;
+    L->total = cur.off;
     return true;
 }
 
@@ -355,6 +328,65 @@ __global__ __launch_bounds__(256) void embed_runs_row_kernel(const float* __rest
     }
 }
 
+// The sorted terms: keys ascending (embedding rows, then the sentinels), vals the set of each term, inv_c the weight of each set
+struct SortedTerms {
+    const int32_t* keys;
+    const int32_t* vals;
+    const float* inv_c;
+};
+
+// Steps 1-2 of both entry points, errors under the entry's `name`: the sort's temporary is checked before anything is launched.
+int sort_terms(const char* name, const int32_t* nbr, const int32_t* cnt, int32_t k, int32_t n, const int32_t* n_dev, const int32_t* row_order,
+               int embed_rows, void* workspace, const SortWs& S, hipStream_t st, SortedTerms* T) {
+    char* ws = (char*)workspace;
+    int32_t* keys_in = (int32_t*)(ws + S.keys_in);
+    int32_t* keys_out = (int32_t*)(ws + S.keys_out);
+    int32_t* vals_in = (int32_t*)(ws + S.vals_in);
+    int32_t* vals_out = (int32_t*)(ws + S.vals_out);
+    float* inv_c = (float*)(ws + S.inv_c);
+    size_t sort_bytes = 0;
+    if (sort_temp_bytes(S.slots, S.bits, &sort_bytes) != hipSuccess || sort_bytes > S.cub_bytes) {
+        sage_set_error("%s: the radix sort asks for %zu bytes of temporary, %zu reserved", name, sort_bytes, S.cub_bytes);
+        return SAGE_ELAUNCH;
+    }
+    hipLaunchKernelGGL(embed_expand_kernel, dim3(sage_cdiv(S.slots, 256)), dim3(256), 0, st, nbr, cnt, k, n, n_dev, row_order, embed_rows, keys_in,
+                       vals_in, inv_c);
+    SAGE_CHECK_LAUNCH("embed_expand_kernel");
+    size_t cub_bytes = S.cub_bytes;
+    if (hipcub::DeviceRadixSort::SortPairs(ws + S.cub, cub_bytes, (const int32_t*)keys_in, keys_out, (const int32_t*)vals_in, vals_out, S.slots, 0,
+                                           S.bits, st) != hipSuccess) {
+        sage_set_error("%s: radix sort failed", name);
+        return SAGE_ELAUNCH;
+    }
+    *T = SortedTerms{keys_out, vals_out, inv_c};
+    return SAGE_OK;
+}
+
+// lanes of 16 bytes per term row: a whole row per trip up to 256 floats
+int lane_group(int dim) { return dim >= 256 ? 64 : dim >= 128 ? 32 : dim >= 64 ? 16 : 8; }
+
+#define SAGE_EMBED_LG(KERNEL, BLOCKS, ...)                                                                          \
+    do {                                                                                                            \
+        if (lg == 64) hipLaunchKernelGGL(KERNEL<64>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);                   \
+        else if (lg == 32) hipLaunchKernelGGL(KERNEL<32>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);              \
+        else if (lg == 16) hipLaunchKernelGGL(KERNEL<16>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);              \
+        else hipLaunchKernelGGL(KERNEL<8>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);                             \
+    } while (0)
+
+// The chunk split of the `rows` rows of `rowptr` over the sorted list (the embedding rows, or the runs), and the chunk pass
+int chunk_pass(const float* grad_agg, int64_t ldg, int32_t dim, const SortedTerms& T, const int64_t* rowptr, int rows, void* workspace,
+               const ChunkWs& C, hipStream_t st, ChunkPlan* P) {
+    if (const int rc = csr_chunk_plan(rowptr, rows, nullptr, rows, workspace, C, st, P)) return rc;
+    if (P->cap > 0) {
+        const int lg = lane_group(dim);
+        const int blocks = (int)std::min<int64_t>((P->cap * lg + 255) / 256, kNumCU * 8);
+        SAGE_EMBED_LG(embed_chunk_kernel, blocks, grad_agg, ldg, dim, T.vals, T.inv_c, rowptr, rows, (const int64_t*)P->off,
+                      (const int64_t*)P->carry, P->nb, P->cap, (const int32_t*)P->item_row, P->partials);
+        SAGE_CHECK_LAUNCH("embed_chunk_kernel");
+    }
+    return SAGE_OK;
+}
+
 }  // namespace
 
 extern "C" size_t sage_embed_grad_workspace_bytes(int32_t n, int32_t k, int64_t embed_rows, int32_t dim) {
@@ -378,69 +410,20 @@ extern "C" int sage_embed_grad(const float* grad_agg, int64_t ldg, int32_t dim, 
     EmbedLayout L;
     SAGE_REQUIRE(embed_layout(n, k, embed_rows, dim, &L), "embed_grad: n = %d, k = %d, embed_rows = %lld, dim = %d out of range", n, k,
                  (long long)embed_rows, dim);
-    if (workspace_bytes < L.total || !workspace) {
-        sage_set_error("embed_grad: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
-        return SAGE_ENOSPACE;
-    }
-    SAGE_REQUIRE(sage_aligned(workspace, 256), "embed_grad: workspace not 256-byte aligned");
+    if (const int rc = csr_workspace_check("embed_grad", workspace, workspace_bytes, L.total)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    int32_t* keys_in = (int32_t*)(ws + L.keys_in);
-    int32_t* keys_out = (int32_t*)(ws + L.keys_out);
-    int32_t* vals_in = (int32_t*)(ws + L.vals_in);
-    int32_t* vals_out = (int32_t*)(ws + L.vals_out);
-    float* inv_c = (float*)(ws + L.inv_c);
-    int64_t* rowptr = (int64_t*)(ws + L.rowptr);
-    int64_t* off = (int64_t*)(ws + L.off);
-    int64_t* carry = (int64_t*)(ws + L.carry);
-    int32_t* item_row = (int32_t*)(ws + L.item_row);
-    float* partials = (float*)(ws + L.partials);
-    const int R = (int)embed_rows, nb = (int)L.nblocks;
-    size_t sort_bytes = 0;
-    if (sort_temp_bytes(L.slots, L.bits, &sort_bytes) != hipSuccess || sort_bytes > L.cub_bytes) {
-        sage_set_error("embed_grad: the radix sort asks for %zu bytes of temporary, %zu reserved", sort_bytes, L.cub_bytes);
-        return SAGE_ELAUNCH;
-    }
-
-    hipLaunchKernelGGL(embed_expand_kernel, dim3(sage_cdiv(L.slots, 256)), dim3(256), 0, st, nbr, cnt, k, n, n_dev, row_order, R, keys_in, vals_in,
-                       inv_c);
-    SAGE_CHECK_LAUNCH("embed_expand_kernel");
-    size_t cub_bytes = L.cub_bytes;
-    if (hipcub::DeviceRadixSort::SortPairs(ws + L.cub, cub_bytes, (const int32_t*)keys_in, keys_out, (const int32_t*)vals_in, vals_out, L.slots, 0,
-                                           L.bits, st) != hipSuccess) {
-        sage_set_error("embed_grad: radix sort failed");
-        return SAGE_ELAUNCH;
-    }
-    hipLaunchKernelGGL(embed_rowptr_kernel, dim3(sage_cdiv(embed_rows + 1, 256)), dim3(256), 0, st, (const int32_t*)keys_out, L.slots, R, rowptr);
+    int64_t* rowptr = (int64_t*)((char*)workspace + L.rowptr);
+    const int R = (int)embed_rows;
+    SortedTerms T;
+    if (const int rc = sort_terms("embed_grad", nbr, cnt, k, n, n_dev, row_order, R, workspace, L.s, st, &T)) return rc;
+    hipLaunchKernelGGL(embed_rowptr_kernel, dim3(sage_cdiv(embed_rows + 1, 256)), dim3(256), 0, st, T.keys, L.s.slots, R, rowptr);
     SAGE_CHECK_LAUNCH("embed_rowptr_kernel");
-    hipLaunchKernelGGL(csr_count_kernel, dim3(nb), dim3(kCountThreads), 0, st, (const int64_t*)rowptr, embed_rows, (const int32_t*)nullptr, R, off,
-                       carry);
-    SAGE_CHECK_LAUNCH("csr_count_kernel");
-    hipLaunchKernelGGL(csr_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, carry, nb);
-    SAGE_CHECK_LAUNCH("csr_carry_kernel");
-    hipLaunchKernelGGL(csr_expand_kernel, dim3(sage_cdiv(R, 256)), dim3(256), 0, st, (const int64_t*)rowptr, embed_rows, (const int32_t*)nullptr, R,
-                       off, (const int64_t*)carry, L.cap, item_row);
-    SAGE_CHECK_LAUNCH("csr_expand_kernel");
-
-    // lanes of 16 bytes per term row: a whole row per trip up to 256 floats
-    const int lg = dim >= 256 ? 64 : dim >= 128 ? 32 : dim >= 64 ? 16 : 8;
-#define SAGE_EMBED_LG(KERNEL, BLOCKS, ...)                                                                          \
-    do {                                                                                                            \
-        if (lg == 64) hipLaunchKernelGGL(KERNEL<64>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);                   \
-        else if (lg == 32) hipLaunchKernelGGL(KERNEL<32>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);              \
-        else if (lg == 16) hipLaunchKernelGGL(KERNEL<16>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);              \
-        else hipLaunchKernelGGL(KERNEL<8>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);                             \
-    } while (0)
-    if (L.cap > 0) {
-        const int blocks = (int)std::min<int64_t>((L.cap * lg + 255) / 256, kNumCU * 8);
-        SAGE_EMBED_LG(embed_chunk_kernel, blocks, grad_agg, ldg, dim, (const int32_t*)vals_out, (const float*)inv_c, (const int64_t*)rowptr, R,
-                      (const int64_t*)off, (const int64_t*)carry, nb, L.cap, (const int32_t*)item_row, partials);
-        SAGE_CHECK_LAUNCH("embed_chunk_kernel");
-    }
+    ChunkPlan P;
+    if (const int rc = chunk_pass(grad_agg, ldg, dim, T, rowptr, R, workspace, L.c, st, &P)) return rc;
+    const int lg = lane_group(dim);
     const int blocks = (int)std::min<int64_t>((embed_rows * lg + 255) / 256, kNumCU * 8);
-    SAGE_EMBED_LG(embed_row_kernel, blocks, grad_agg, ldg, dim, (const int32_t*)vals_out, (const float*)inv_c, (const int64_t*)rowptr, R,
-                  (const int64_t*)off, L.cap, (const float*)partials, grad_embed, ld);
-#undef SAGE_EMBED_LG
+    SAGE_EMBED_LG(embed_row_kernel, blocks, grad_agg, ldg, dim, T.vals, T.inv_c, (const int64_t*)rowptr, R, (const int64_t*)P.off, P.cap,
+                  (const float*)P.partials, grad_embed, ld);
     SAGE_CHECK_LAUNCH("embed_row_kernel");
     return SAGE_OK;
 }
@@ -472,82 +455,36 @@ extern "C" int sage_embed_grad_rows(const float* grad_agg, int64_t ldg, int32_t 
     RowsLayout L;
     SAGE_REQUIRE(rows_layout(n, k, embed_rows, dim, &L), "embed_grad_rows: n = %d, k = %d, embed_rows = %lld, dim = %d out of range", n, k,
                  (long long)embed_rows, dim);
-    if (workspace_bytes < L.total || !workspace) {
-        sage_set_error("embed_grad_rows: workspace of %zu bytes, %zu needed", workspace_bytes, L.total);
-        return SAGE_ENOSPACE;
-    }
-    SAGE_REQUIRE(sage_aligned(workspace, 256), "embed_grad_rows: workspace not 256-byte aligned");
+    if (const int rc = csr_workspace_check("embed_grad_rows", workspace, workspace_bytes, L.total)) return rc;
     hipStream_t st = (hipStream_t)stream;
     char* ws = (char*)workspace;
-    int32_t* keys_in = (int32_t*)(ws + L.keys_in);
-    int32_t* keys_out = (int32_t*)(ws + L.keys_out);
-    int32_t* vals_in = (int32_t*)(ws + L.vals_in);
-    int32_t* vals_out = (int32_t*)(ws + L.vals_out);
-    float* inv_c = (float*)(ws + L.inv_c);
     int32_t* run_row = (int32_t*)(ws + L.run_row);
     int64_t* runptr = (int64_t*)(ws + L.runptr);
     int64_t* heads = (int64_t*)(ws + L.heads);
     int64_t* end_pos = (int64_t*)(ws + L.end_pos);
-    int64_t* off = (int64_t*)(ws + L.off);
-    int64_t* carry = (int64_t*)(ws + L.carry);
-    int32_t* item_row = (int32_t*)(ws + L.item_row);
-    float* partials = (float*)(ws + L.partials);
-    const int R = (int)embed_rows, C = (int)L.runs_cap, nb = (int)L.nblocks, hb = (int)L.head_blocks;
-    size_t sort_bytes = 0;
-    if (sort_temp_bytes(L.slots, L.bits, &sort_bytes) != hipSuccess || sort_bytes > L.cub_bytes) {
-        sage_set_error("embed_grad_rows: the radix sort asks for %zu bytes of temporary, %zu reserved", sort_bytes, L.cub_bytes);
-        return SAGE_ELAUNCH;
-    }
-
-    hipLaunchKernelGGL(embed_expand_kernel, dim3(sage_cdiv(L.slots, 256)), dim3(256), 0, st, nbr, cnt, k, n, n_dev, row_order, R, keys_in, vals_in,
-                       inv_c);
-    SAGE_CHECK_LAUNCH("embed_expand_kernel");
-    size_t cub_bytes = L.cub_bytes;
-    if (hipcub::DeviceRadixSort::SortPairs(ws + L.cub, cub_bytes, (const int32_t*)keys_in, keys_out, (const int32_t*)vals_in, vals_out, L.slots, 0,
-                                           L.bits, st) != hipSuccess) {
-        sage_set_error("embed_grad_rows: radix sort failed");
-        return SAGE_ELAUNCH;
-    }
+    const int R = (int)embed_rows, C = (int)L.runs_cap, hb = (int)L.head_blocks;
+    SortedTerms T;
+    if (const int rc = sort_terms("embed_grad_rows", nbr, cnt, k, n, n_dev, row_order, R, workspace, L.s, st, &T)) return rc;
     // the run list: count the heads per tile, scan the tiles, write the runs, close the list
-    hipLaunchKernelGGL(embed_heads_kernel<false>, dim3(hb), dim3(kHeadThreads), 0, st, (const int32_t*)keys_out, L.slots, R, L.runs_cap, heads,
-                       run_row, runptr, end_pos);
+    hipLaunchKernelGGL(embed_heads_kernel<false>, dim3(hb), dim3(kHeadThreads), 0, st, T.keys, L.s.slots, R, L.runs_cap, heads, run_row, runptr,
+                       end_pos);
     SAGE_CHECK_LAUNCH("embed_heads_kernel (count)");
     hipLaunchKernelGGL(csr_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, heads, hb);
     SAGE_CHECK_LAUNCH("csr_carry_kernel (runs)");
-    hipLaunchKernelGGL(embed_heads_kernel<true>, dim3(hb), dim3(kHeadThreads), 0, st, (const int32_t*)keys_out, L.slots, R, L.runs_cap, heads,
-                       run_row, runptr, end_pos);
+    hipLaunchKernelGGL(embed_heads_kernel<true>, dim3(hb), dim3(kHeadThreads), 0, st, T.keys, L.s.slots, R, L.runs_cap, heads, run_row, runptr,
+                       end_pos);
     SAGE_CHECK_LAUNCH("embed_heads_kernel (scatter)");
     hipLaunchKernelGGL(embed_runs_fill_kernel, dim3(sage_cdiv(L.runs_cap + 1, 256)), dim3(256), 0, st, (const int64_t*)heads, hb,
                        (const int64_t*)end_pos, L.runs_cap, runptr, num_rows_out);
     SAGE_CHECK_LAUNCH("embed_runs_fill_kernel");
     // the chunk split over the runs: sage_embed_grad's launches with the run list as the row pointer
-    hipLaunchKernelGGL(csr_count_kernel, dim3(nb), dim3(kCountThreads), 0, st, (const int64_t*)runptr, L.runs_cap, (const int32_t*)nullptr, C, off,
-                       carry);
-    SAGE_CHECK_LAUNCH("csr_count_kernel");
-    hipLaunchKernelGGL(csr_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, carry, nb);
-    SAGE_CHECK_LAUNCH("csr_carry_kernel");
-    hipLaunchKernelGGL(csr_expand_kernel, dim3(sage_cdiv(C, 256)), dim3(256), 0, st, (const int64_t*)runptr, L.runs_cap, (const int32_t*)nullptr, C,
-                       off, (const int64_t*)carry, L.cap, item_row);
-    SAGE_CHECK_LAUNCH("csr_expand_kernel");
-
-    const int lg = dim >= 256 ? 64 : dim >= 128 ? 32 : dim >= 64 ? 16 : 8;
-#define SAGE_EMBED_LG(KERNEL, BLOCKS, ...)                                                                          \
-    do {                                                                                                            \
-        if (lg == 64) hipLaunchKernelGGL(KERNEL<64>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);                   \
-        else if (lg == 32) hipLaunchKernelGGL(KERNEL<32>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);              \
-        else if (lg == 16) hipLaunchKernelGGL(KERNEL<16>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);              \
-        else hipLaunchKernelGGL(KERNEL<8>, dim3(BLOCKS), dim3(256), 0, st, __VA_ARGS__);                             \
-    } while (0)
-    if (L.cap > 0) {
-        const int blocks = (int)std::min<int64_t>((L.cap * lg + 255) / 256, kNumCU * 8);
-        SAGE_EMBED_LG(embed_chunk_kernel, blocks, grad_agg, ldg, dim, (const int32_t*)vals_out, (const float*)inv_c, (const int64_t*)runptr, C,
-                      (const int64_t*)off, (const int64_t*)carry, nb, L.cap, (const int32_t*)item_row, partials);
-        SAGE_CHECK_LAUNCH("embed_chunk_kernel");
-    }
+    ChunkPlan P;
+    if (const int rc = chunk_pass(grad_agg, ldg, dim, T, runptr, C, workspace, L.c, st, &P)) return rc;
+    const int lg = lane_group(dim);
     const int blocks = (int)std::min<int64_t>((L.runs_cap * lg + 255) / 256, kNumCU * 8);
-    SAGE_EMBED_LG(embed_runs_row_kernel, blocks, grad_agg, ldg, dim, (const int32_t*)vals_out, (const float*)inv_c, (const int64_t*)runptr, C,
-                  (const int64_t*)(heads + hb), (const int64_t*)off, L.cap, (const float*)partials, (const int32_t*)run_row, rows_out, grad_rows,
-                  max_rows, ldr, embed, lde, R, lr);
+    SAGE_EMBED_LG(embed_runs_row_kernel, blocks, grad_agg, ldg, dim, T.vals, T.inv_c, (const int64_t*)runptr, C, (const int64_t*)(heads + hb),
+                  (const int64_t*)P.off, P.cap, (const float*)P.partials, (const int32_t*)run_row, rows_out, grad_rows, max_rows, ldr, embed, lde, R,
+                  lr);
 #undef SAGE_EMBED_LG
     SAGE_CHECK_LAUNCH("embed_runs_row_kernel");
     return SAGE_OK;
