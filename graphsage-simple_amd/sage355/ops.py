@@ -337,6 +337,92 @@ def csr_mean(rowptr, col, table, nodes=None, self_loop=False, any_nonempty=None,
     return out
 
 
+def csr_frontier_workspace_bytes(n, max_edges):
+    """Bytes of the workspace sage_csr_frontier needs (host arithmetic; 0 = shape out of range)."""
+    return int(native.lib().sage_csr_frontier_workspace_bytes(int(n), int(max_edges)))
+
+
+class CsrFrontier:
+    """The state of sage_csr_frontier for one graph: `pos` int32 [num_nodes], the id -> row map (filled with -1 ONCE, here; clear()
+    afterwards takes back the rows that were handed out and nothing else), `nodes` int32 [max_nodes], `count` int32 [1] and a workspace
+    that grows with the calls.  max_nodes: rows of `nodes` (default num_nodes, which no set outgrows); reserve() grows it.
+    pos is what csr_mean(index=...) and linear_act(self_index=...) take to read compact rows by node id."""
+
+    def __init__(self, num_nodes, device, max_nodes=None):
+        _need_gpu()
+        self.num_nodes = int(num_nodes)
+        self.max_nodes = self.num_nodes if max_nodes is None else int(max_nodes)
+        if self.num_nodes < 0 or self.num_nodes >= 1 << 31 or self.max_nodes < 0:
+            raise native.SageError(f"CsrFrontier: num_nodes = {num_nodes}, max_nodes = {max_nodes}")
+        self.pos = torch.full((max(self.num_nodes, 1),), -1, dtype=torch.int32, device=device)
+        self.nodes = torch.full((max(self.max_nodes, 1),), -1, dtype=torch.int32, device=device)
+        self.count = torch.zeros(1, dtype=torch.int32, device=device)
+        self.workspace = None
+
+    def reserve(self, max_nodes):
+        """Room for max_nodes rows in `nodes`; the rows it holds are kept."""
+        max_nodes = int(max_nodes)
+        if max_nodes > self.nodes.numel():
+            grown = torch.full((max_nodes,), -1, dtype=torch.int32, device=self.nodes.device)
+            grown[: self.nodes.numel()] = self.nodes
+            self.nodes = grown
+        self.max_nodes = max(self.max_nodes, max_nodes)
+
+    def clear(self, first_row=0):
+        """pos := -1 where this frontier's rows point (sage_csr_frontier_clear, no O(num_nodes) fill), count := first_row."""
+        native.check(native.lib().sage_csr_frontier_clear(native.ptr(self.pos), native.ptr(self.nodes), native.ptr(self.count),
+                                                          min(self.max_nodes, self.nodes.numel()), native.stream_handle()), "csr_frontier_clear")
+        self.count.fill_(int(first_row))
+
+    def refill(self):
+        """pos := -1 everywhere, count := 0: after an overflow, when `nodes` no longer names every row of pos."""
+        self.pos.fill_(-1)
+        self.count.zero_()
+
+    def size(self):
+        return int(self.count.item())   # host read
+
+    def node_list(self):
+        n = self.size()
+        if n > self.max_nodes:
+            raise native.SageError(f"CsrFrontier: {n} rows for max_nodes = {self.max_nodes}")
+        return self.nodes[:n]
+
+
+def csr_frontier(rowptr, col, seeds, frontier, max_edges=None):
+    """aggregators.py:47-53 with num_sample=None, from the CSR: every distinct id among `seeds` (int32, device; may repeat) and all
+    their neighbours joins `frontier` (a CsrFrontier of this graph, cleared) -- frontier.nodes[:count] in arbitrary order,
+    frontier.pos[id] = its row.  max_edges: upper bound on the edges of the seeds' rows, default len(col) (a smaller bound only costs
+    speed).  Nothing is read back: frontier.size() is the host read, and a size above frontier.max_nodes means the set did not fit."""
+    _need_gpu()
+    _chk(rowptr, torch.int64, "rowptr", 1)
+    _chk(col, torch.int32, "col", 1)
+    _chk(seeds, torch.int32, "seeds", 1)
+    if not isinstance(frontier, CsrFrontier):
+        raise native.SageError("csr_frontier: frontier must be a CsrFrontier")
+    num_nodes = rowptr.shape[0] - 1
+    if num_nodes != frontier.num_nodes:
+        raise native.SageError(f"csr_frontier: the frontier maps {frontier.num_nodes} nodes, the CSR has {num_nodes}")
+    n = seeds.shape[0]
+    if n == 0:
+        return frontier
+    dev = frontier.pos.device
+    if col.numel() == 0:                                  # an empty tensor may have no storage address: the kernel reads none of it
+        col = torch.zeros(1, dtype=torch.int32, device=dev)
+    max_edges = col.numel() if max_edges is None else int(max_edges)
+    need = csr_frontier_workspace_bytes(n, max_edges)
+    if need == 0:
+        raise native.SageError(f"csr_frontier: n = {n}, max_edges = {max_edges} out of range")
+    if frontier.workspace is None or frontier.workspace.numel() < need:
+        frontier.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    rc = native.lib().sage_csr_frontier(native.ptr(rowptr), native.ptr(col), num_nodes, native.ptr(seeds), n, max_edges,
+                                        native.ptr(frontier.pos), native.ptr(frontier.nodes), min(frontier.max_nodes, frontier.nodes.numel()),
+                                        native.ptr(frontier.count), native.ptr(frontier.workspace), frontier.workspace.numel(),
+                                        native.stream_handle())
+    native.check(rc, "csr_frontier")
+    return frontier
+
+
 def csr_transpose(rowptr, col):
     """(rowptr_t int64 [N + 1], col_t int32 [E]) of a CSR over N = len(rowptr) - 1 nodes: for every entry (v -> u) row u of the
     transpose holds one entry v, in ascending v (duplicates kept) -- what csr_mean_backward sums over.  Torch ops (a stable sort by

@@ -220,6 +220,8 @@ class EngineTrainer:
         self.engine.keep_means = True        # the backward reads the layer-1 means of the forward from the workspace
         self.engine.invalidate_weights()
         self._native, self._ops = native, ops
+        # the caller's graph and table (the engine may work on renumbered copies): what embed_exact reads
+        self._exact = {"rowptr": rowptr, "col": col, "table": table, "index": embed_index, "frontier": None}
         self._out_q = None
         self._step_graph = None
         self._head = None
@@ -256,11 +258,34 @@ class EngineTrainer:
         it from the embeddings in one launch (the inference form of sage_xent_head); the torch head takes scores().argmax(1)."""
         if self.head != "native":
             return self.scores(seeds, key).argmax(1).to(torch.int32)
-        emb = self.embed(seeds, key)
+        return self._predict_of(self.embed(seeds, key))
+
+    def _predict_of(self, emb):
+        """predict()'s rule on given embeddings."""
+        if self.head != "native":
+            return (emb @ self.w_cls.t()).argmax(1).to(torch.int32)
         if emb.shape[0] > self._head["rows"]:
             self._head_reserve(emb.shape[0])
         hd = self._head
         return self._ops.xent_head(emb, self.w_cls, grads=False, pred=True, workspace=hd["workspace"], out={"pred": hd["pred"]})["pred"].clone()
+
+    def embed_exact(self, seeds):
+        """[B, hidden2] embeddings over the FULL neighbourhoods at both hops (aggregators.py:47-48, num_sample=None): no sampler key, the
+        same bits on every call -- inference.embed_nodes on the trainer's own weights and its table (the embedding through embed_index
+        on an embedding trainer), in the caller's node ids.  The [N] frontier map is built at the first call and kept; two host reads
+        per call (embed_nodes)."""
+        from .inference import embed_nodes
+        ex, eng = self._exact, self.engine
+        if ex["frontier"] is None:
+            ex["frontier"] = self._ops.CsrFrontier(ex["rowptr"].shape[0] - 1, self.w1.device, max_nodes=0)
+        with torch.no_grad():
+            return embed_nodes(ex["rowptr"], ex["col"], ex["table"] if ex["index"] is None else self.embed_weight, self.w1, self.w2, seeds,
+                               concat=self.concat, agg_self_loop=eng.agg_self_loop, act1=eng.act1, act2=eng.act2, nan_empty=eng.nan_empty,
+                               index=ex["index"], frontier=ex["frontier"])
+
+    def predict_exact(self, seeds):
+        """predict() on embed_exact's embeddings: int32 [B], identical on every call."""
+        return self._predict_of(self.embed_exact(seeds))
 
     def grads(self, seeds, labels, key, global_batch=None, _embed_lr=None):
         """loss (device scalar) and the gradients of (w1, w2, w_cls) -- and of embed_weight, a fourth entry, on an embedding trainer
@@ -381,13 +406,14 @@ class EngineTrainer:
 
 def run_engine_training(graph, feat_data, labels, num_classes, seed=1, epochs=1, batch_size=128, ref_batching=False, lr=0.7,
                         sample_seed=0, hidden1=50, hidden2=128, num_sample1=10, num_sample2=10, gcn=True, head="torch", initializer=None,
-                        embed_dim=100, sparse_embed=False):
+                        embed_dim=100, sparse_embed=False, exact_eval=False):
     """run_model (model.py:184-259) on the engine path: same split, shuffles, batching and optimiser as run_training above, every
     step through EngineTrainer.  -> dict(f1_micro, f1_macro, mean_step_time, losses, trainer).
     initializer: None (or "None") -- the frozen table feat_data; "1hot" -- a trainable embedding row per node, ReLU; "node_degree" -- a
     row per degree, SIGMOID at layer 1 (encoders.py:58-59).  feat_data is not read for the last two and may be None; embed_dim is
     the embedding's width (the reference's --feature_dim default), a multiple of 4.  sparse_embed: EngineTrainer's (an initializer
-    only): update the touched embedding rows alone."""
+    only): update the touched embedding rows alone.  exact_eval: the validation predictions come from predict_exact (full
+    neighbourhoods, no sampler key) instead of one sampled forward; training is the same either way."""
     from sklearn.metrics import f1_score
     from . import native
     from .fullgraph import degree_index, one_hot_index
@@ -429,7 +455,10 @@ def run_engine_training(graph, feat_data, labels, num_classes, seed=1, epochs=1,
     elapsed = time.time() - t0
     with torch.no_grad():
         val_ids = torch.as_tensor(val.astype(np.int32)).to(dev)
-        pred = (tr.predict(val_ids, key=key) if head == "native" else tr.scores(val_ids, key=key).argmax(1)).cpu().numpy()
+        if exact_eval:
+            pred = tr.predict_exact(val_ids).cpu().numpy()
+        else:
+            pred = (tr.predict(val_ids, key=key) if head == "native" else tr.scores(val_ids, key=key).argmax(1)).cpu().numpy()
     truth = np.asarray(labels)[val].reshape(-1)
     return {"f1_micro": float(f1_score(truth, pred, average="micro")), "f1_macro": float(f1_score(truth, pred, average="macro")),
             "mean_step_time": elapsed / max(steps, 1), "losses": [float(x) for x in losses], "trainer": tr}

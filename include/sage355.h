@@ -211,6 +211,51 @@ int sage_csr_mean_indexed(const int64_t* rowptr, const int32_t* col, int64_t num
                           float* out, int64_t ldo, void* workspace, size_t workspace_bytes, sage_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * sage_csr_frontier (additive, ABI 9) -- the frontier of a FULL-neighbourhood
+ * hop: aggregators.py:47-53 with num_sample=None, `samp_neighs = to_neighs`
+ * (+ the node itself), `unique_nodes_list = list(set.union(*samp_neighs))` and
+ * the `unique_nodes` dict, straight from the CSR.  The hash frontier above
+ * takes padded [n, k] lists with k <= SAGE_MAX_FANOUT; a whole row has no such
+ * bound, so the id -> row map here is a plain array:
+ *   pos    int32 [num_nodes], -1 = "not in the set"; holds -1 everywhere on
+ *          entry (ids that already hold a row keep it and are not added again)
+ *   count  int32 [1] on the device; on entry the first free row
+ * On return nodes_out[0 .. *count) holds every distinct id among seeds[0..n)
+ * and col[rowptr[v] .. rowptr[v+1]) for each seed v, each once, in ARBITRARY
+ * order (as sage_frontier_t's nodes[]), pos[nodes_out[i]] == i, and pos is
+ * unchanged elsewhere: pos is the `index` sage_csr_mean_indexed reads the
+ * compact rows of the next layer through.  Seeds may repeat.
+ * Seed ids outside [0, num_nodes) are empty rows and are not inserted;
+ * neighbour ids outside it are skipped; row pointers are clamped as
+ * sage_csr_mean clamps them.  Nothing is written outside pos[0..num_nodes) and
+ * nodes_out[0..max_nodes): a row index >= max_nodes is not stored in
+ * nodes_out, but *count keeps counting, so *count > max_nodes tells the caller
+ * of the overflow (pos then names rows that nodes_out does not hold: refill it).
+ * Load balance is sage_csr_mean's: a seed row longer than SAGE_CSR_MEAN_CHUNK
+ * entries is cut into chunks walked by separate waves; max_edges bounds the
+ * edges of the seeds' rows and sizes the workspace exactly as there, and a
+ * bound that is too small gives the same set, more slowly.  One integer
+ * compare-and-swap per id decides who adds it, one integer add per wave
+ * reserves the rows; no float atomics, no host synchronisation.
+ * Validation, before any launch: num_nodes in [0, 2^31), n >= 0,
+ * max_nodes >= 0, max_edges >= 0, then NULL arrays (SAGE_EINVAL), then the
+ * workspace (short or missing: SAGE_ENOSPACE; 256-byte aligned).  n == 0
+ * returns SAGE_OK without a launch.  The size query is host arithmetic (0 =
+ * shape out of range).
+ * sage_csr_frontier_clear: pos[nodes_out[i]] = -1 for i < min(*count,
+ * max_nodes), so a persistent map is reused without an O(num_nodes) fill.
+ * *count is left as it is.  Rows below the first free row of the insert are
+ * the caller's: they must hold node ids or negative values (skipped).
+ * ------------------------------------------------------------------------- */
+size_t sage_csr_frontier_workspace_bytes(int32_t n, int64_t max_edges);
+int sage_csr_frontier(const int64_t* rowptr, const int32_t* col, int64_t num_nodes,
+                      const int32_t* seeds, int32_t n, int64_t max_edges,
+                      int32_t* pos, int32_t* nodes_out, int32_t max_nodes, int32_t* count,
+                      void* workspace, size_t workspace_bytes, sage_stream_t stream);
+int sage_csr_frontier_clear(int32_t* pos, const int32_t* nodes_out, const int32_t* count,
+                            int32_t max_nodes, sage_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * sage_csr_mean_backward (additive, ABI 9) -- the adjoint of
  * sage_csr_mean(nodes = NULL, n = num_nodes) with respect to `table`.  With the
  * forward's own definitions
