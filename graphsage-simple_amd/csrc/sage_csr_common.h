@@ -86,26 +86,14 @@ template <bool UNIFORM> __device__ inline int64_t first_item(const int64_t* __re
     return k > 0 ? bcast<UNIFORM>(off[r]) : 0;
 }
 
-// 1. per-thread kCountIpt consecutive rows; off[r] := block-local exclusive offset, carry[block] := the block's chunk sum
-__global__ __launch_bounds__(kCountThreads) void csr_count_kernel(const int64_t* __restrict__ rowptr, int64_t num_nodes,
-                                                                   const int32_t* __restrict__ nodes, int n, int64_t* __restrict__ off,
-                                                                   int64_t* __restrict__ carry) {
+// The block scan of a count kernel (kCountThreads threads): every thread holds the counts c[] of kCountIpt consecutive rows from row
+// r0 on (0 at or past n); off[r] := block-local exclusive offset, carry[block] := the block's sum.  Within the wave by shuffles,
+// then across the 4 waves.
+__device__ inline void count_block_scan(const int64_t (&c)[kCountIpt], int r0, int n, int64_t* __restrict__ off, int64_t* __restrict__ carry) {
     __shared__ int64_t wave_sum[kCountThreads / kWave];
-    const int64_t total = rowptr[num_nodes];
-    const int r0 = blockIdx.x * kCountTile + threadIdx.x * kCountIpt;
-    int64_t c[kCountIpt], s = 0;
+    int64_t s = 0;
 #pragma unroll
-    for (int i = 0; i < kCountIpt; ++i) {
-        c[i] = 0;
-        if (r0 + i < n) {
-            int32_t v;
-            int64_t b, e;
-            row_span(rowptr, num_nodes, nodes, r0 + i, total, v, b, e);
-            c[i] = long_chunks(e - b);
-        }
-        s += c[i];
-    }
-    // block exclusive scan of the thread sums: within the wave by shuffles, then across the 4 waves
+    for (int i = 0; i < kCountIpt; ++i) s += c[i];
     const int lane = sage_lane(), w = threadIdx.x / kWave;
     int64_t incl = s;
 #pragma unroll
@@ -128,6 +116,26 @@ __global__ __launch_bounds__(kCountThreads) void csr_count_kernel(const int64_t*
         run += c[i];
     }
     if (threadIdx.x == 0) carry[blockIdx.x] = block;
+}
+
+// 1. per-thread kCountIpt consecutive rows; off[r] := block-local exclusive offset, carry[block] := the block's chunk sum
+__global__ __launch_bounds__(kCountThreads) void csr_count_kernel(const int64_t* __restrict__ rowptr, int64_t num_nodes,
+                                                                   const int32_t* __restrict__ nodes, int n, int64_t* __restrict__ off,
+                                                                   int64_t* __restrict__ carry) {
+    const int64_t total = rowptr[num_nodes];
+    const int r0 = blockIdx.x * kCountTile + threadIdx.x * kCountIpt;
+    int64_t c[kCountIpt];
+#pragma unroll
+    for (int i = 0; i < kCountIpt; ++i) {
+        c[i] = 0;
+        if (r0 + i < n) {
+            int32_t v;
+            int64_t b, e;
+            row_span(rowptr, num_nodes, nodes, r0 + i, total, v, b, e);
+            c[i] = long_chunks(e - b);
+        }
+    }
+    count_block_scan(c, r0, n, off, carry);
 }
 
 // 2. one block: carry[0..nb) := exclusive scan of itself, carry[nb] := total chunks

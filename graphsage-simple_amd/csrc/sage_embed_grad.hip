@@ -20,9 +20,7 @@
 // run of more than one chunk, out = p_0 for any other.  The terms are weighted_sum's; the item check of step 7 and a row's total are
 // sage_csr_common.h's chunk_item and chunked_row_sum (through run_sum), shared with the three CSR files, here with one lane GROUP per
 // item or row and therefore without their wave broadcasts.  No float atomics, no host synchronisation, no allocation.
-#include <hipcub/hipcub.hpp>
-
-#include "sage_csr_common.h"
+#include "sage_sorted_terms.h"
 
 namespace {
 
@@ -36,8 +34,7 @@ struct SortWs {
 bool sort_ws(int32_t n, int32_t k, int64_t embed_rows, int32_t dim, WsCursor& cur, SortWs* S) {
     if (n < 1 || k < 1 || dim < 1 || embed_rows < 1 || embed_rows >= (1ll << 31) || (int64_t)n * k >= (1ll << 31)) return false;
     S->slots = n * k;
-    S->bits = 1;
-    while ((1ll << S->bits) <= embed_rows) ++S->bits;              // keys are in [0, embed_rows] (the sentinel included)
+    S->bits = sort_key_bits(embed_rows);                           // keys are in [0, embed_rows] (the sentinel included)
     S->keys_in = cur.take((size_t)S->slots * 4);
     S->keys_out = cur.take((size_t)S->slots * 4);
     S->vals_in = cur.take((size_t)S->slots * 4);
@@ -48,7 +45,7 @@ bool sort_ws(int32_t n, int32_t k, int64_t embed_rows, int32_t dim, WsCursor& cu
     // into: a second key and value array (8 bytes per slot), one look-back word per digit (256) and block of at least 512 slots
     // (at most 4 bytes per slot at 8 bytes a word), digit histograms of a few KiB.  sort_terms asks the library before it sorts
     // and refuses (SAGE_ELAUNCH, nothing sorted) if it ever wanted more.
-    S->cub_bytes = (size_t)S->slots * 16 + 65536;
+    S->cub_bytes = sort_temp_reserve(S->slots);
     S->cub = cur.take(S->cub_bytes);
     return true;
 }
@@ -66,12 +63,6 @@ bool embed_layout(int32_t n, int32_t k, int64_t embed_rows, int32_t dim, EmbedLa
     if (!chunk_ws(embed_rows, L->s.slots, dim, cur, &L->c)) return false;     // every long run's chunks fit: at most slots terms in all
     L->total = cur.off;
     return true;
-}
-
-hipError_t sort_temp_bytes(int slots, int bits, size_t* bytes) {
-    *bytes = 0;
-    return hipcub::DeviceRadixSort::SortPairs(nullptr, *bytes, (const int32_t*)nullptr, (int32_t*)nullptr, (const int32_t*)nullptr,
-                                              (int32_t*)nullptr, slots, 0, bits, (hipStream_t)0);
 }
 
 // 1. one thread per slot, slots in row_order POSITION: slot p * k + j is term j of row t = row_order[p]
@@ -94,20 +85,6 @@ __global__ __launch_bounds__(256) void embed_expand_kernel(const int32_t* __rest
     }
     keys[i] = key;
     vals[i] = live ? t : 0;
-}
-
-// 3. rowptr[e] = the first position of the sorted list whose key is >= e, e in [0, embed_rows]: rowptr[embed_rows] = the terms
-__global__ __launch_bounds__(256) void embed_rowptr_kernel(const int32_t* __restrict__ keys, int slots, int embed_rows,
-                                                           int64_t* __restrict__ rowptr) {
-    const int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (e > embed_rows) return;
-    int lo = 0, hi = slots;
-    while (lo < hi) {
-        const int mid = lo + (hi - lo) / 2;
-        if (keys[mid] < e) lo = mid + 1;
-        else hi = mid;
-    }
-    rowptr[e] = lo;
 }
 
 using V4 = float4;
@@ -416,8 +393,8 @@ extern "C" int sage_embed_grad(const float* grad_agg, int64_t ldg, int32_t dim, 
     const int R = (int)embed_rows;
     SortedTerms T;
     if (const int rc = sort_terms("embed_grad", nbr, cnt, k, n, n_dev, row_order, R, workspace, L.s, st, &T)) return rc;
-    hipLaunchKernelGGL(embed_rowptr_kernel, dim3(sage_cdiv(embed_rows + 1, 256)), dim3(256), 0, st, T.keys, L.s.slots, R, rowptr);
-    SAGE_CHECK_LAUNCH("embed_rowptr_kernel");
+    hipLaunchKernelGGL(sorted_rowptr_kernel, dim3(sage_cdiv(embed_rows + 1, 256)), dim3(256), 0, st, T.keys, L.s.slots, R, rowptr);
+    SAGE_CHECK_LAUNCH("sorted_rowptr_kernel");
     ChunkPlan P;
     if (const int rc = chunk_pass(grad_agg, ldg, dim, T, rowptr, R, workspace, L.c, st, &P)) return rc;
     const int lg = lane_group(dim);

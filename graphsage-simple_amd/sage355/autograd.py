@@ -3,7 +3,7 @@
 The reference gets its gradients from stock autograd through mm / div / cat /
 relu; here each operator carries its own backward kernel
 (include/sage355.h: sage_linear_act_backward, sage_gather_mean_backward, sage_csr_mean_backward, sage_csr_sum,
-sage_csr_mean_backward_grouped).
+sage_csr_mean_backward_grouped, sage_csr_mean_backward_rows).
 """
 import torch
 
@@ -72,6 +72,33 @@ class _CsrMeanIndexed(torch.autograd.Function):
         rowptr, col, rowptr_gt, col_gt = ctx.saved_tensors
         grouped = ops.GroupedTranspose(rowptr_gt, col_gt, ctx.self_loop)
         return ops.csr_mean_backward_grouped(rowptr, col, grouped, grad_out.contiguous()), None, None, None, None, None
+
+
+class _CsrMeanRows(torch.autograd.Function):
+    """The full-neighbourhood mean of a seed batch (ops.csr_mean(nodes=..., index=...)) and its adjoint with respect to the table
+    it reads (ops.csr_mean_backward_rows): the rows may repeat and may share neighbours, nothing [N, dim] is built."""
+
+    @staticmethod
+    def forward(ctx, table, rowptr, col, nodes, index, self_loop, any_nonempty, max_edges):
+        out = ops.csr_mean(rowptr, col, table, nodes=nodes, self_loop=self_loop, any_nonempty=any_nonempty, index=index,
+                           max_edges=max_edges)
+        ctx.save_for_backward(rowptr, col, nodes, index)
+        ctx.self_loop, ctx.table_rows, ctx.max_edges = self_loop, table.shape[0], max_edges
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        rowptr, col, nodes, index = ctx.saved_tensors
+        n = rowptr.shape[0] - 1
+        rows = ctx.table_rows
+        if index is None and rows > n:                    # rows at or past num_nodes belong to no node: zero gradient
+            grad_table = torch.zeros((rows, grad_out.shape[1]), dtype=torch.float32, device=grad_out.device)
+            ops.csr_mean_backward_rows(rowptr, col, nodes, grad_out.contiguous(), self_loop=ctx.self_loop, out=grad_table[:n],
+                                       max_edges=ctx.max_edges)
+        else:
+            grad_table = ops.csr_mean_backward_rows(rowptr, col, nodes, grad_out.contiguous(), index=index, num_rows=rows,
+                                                    self_loop=ctx.self_loop, max_edges=ctx.max_edges)
+        return grad_table, None, None, None, None, None, None, None
 
 
 class _EmbedRows(torch.autograd.Function):
@@ -193,6 +220,22 @@ def csr_mean(rowptr, col, table, transpose=None, self_loop=False, any_nonempty=N
         return _CsrMeanIndexed.apply(table, rowptr, col, index, grouped, any_nonempty)
     rowptr_t, col_t = ops.csr_transpose(rowptr, col) if transpose is None else transpose
     return _CsrMean.apply(table, rowptr, col, rowptr_t, col_t, bool(self_loop), any_nonempty)
+
+
+def csr_mean_rows(rowptr, col, table, nodes, index=None, self_loop=False, any_nonempty=None, max_edges=None):
+    """ops.csr_mean(rowptr, col, table, nodes=nodes, index=index), differentiable with respect to `table`: row r is the
+    full-neighbourhood mean of node nodes[r] (int32 on the device; the rows may repeat and share neighbours), read from `table`
+    by node id, or through index (int32 [N]: a frontier's id -> row map, an embedding index) from a [K, dim] table.  The gradient
+    is [table.shape[0], dim], ops.csr_mean_backward_rows: the batch's terms in a fixed order, no float atomics, the same bits
+    every run.  max_edges: an upper bound on the entries of the rows `nodes` for BOTH directions (a bound below the truth would
+    drop terms of the gradient); None reads the count on the host in the backward.  Without grad mode, or with a table that
+    needs no gradient, it is the plain operator."""
+    if not (torch.is_grad_enabled() and table.requires_grad):
+        return ops.csr_mean(rowptr, col, table.detach(), nodes=nodes, self_loop=self_loop, any_nonempty=any_nonempty, index=index,
+                            max_edges=max_edges)
+    if nodes is None:
+        raise native.SageError("autograd.csr_mean_rows: nodes is required (the whole-graph form is autograd.csr_mean)")
+    return _CsrMeanRows.apply(table, rowptr, col, nodes, index, bool(self_loop), any_nonempty, max_edges)
 
 
 def embed_rows(weight, index, groups=None):

@@ -1,0 +1,214 @@
+"""Exact mini-batch training: one SGD step of SupervisedGraphSage (model.py:52-69, 240-252) on a SEED BATCH embedded from the FULL
+neighbourhoods of its nodes (num_sample=None, aggregators.py:47-48) -- the computation inference.embed_nodes serves, differentiated.
+
+fullgraph.FullGraphTrainer differentiates the same expression for every node and touches all N rows in every step, however small the
+training batch.  Here a step costs what the batch's two-hop neighbourhood costs: the frontier F of the seeds' outer rows
+(ops.csr_frontier), layer 1 for the |F| rows, layer 2 for the seeds through the frontier's id -> row map, and backwards the adjoint of
+that indexed mean with respect to the compact h1_F (ops.csr_mean_backward_rows).  No float array has N rows; the trainer owns one
+int32 [N] map.  Nothing is drawn, the gradient is exact, and two runs give the same bits: no float atomics anywhere on the path.
+The feature table is frozen (model.py:214-215).  Single process.
+"""
+import random
+import time
+
+import numpy as np
+import torch
+from torch.nn import init
+
+from . import dist, ops
+from .fullgraph import FullGraphTrainer
+from .inference import _row_edges
+from .native import ACT_RELU, ACT_SIGMOID, SageError
+from .train import _sum_over_batch
+
+
+class ExactBatchTrainer:
+    """The frozen-table form of FullGraphTrainer for seed batches: the same arguments, the weights w1, w2, w_cls drawn in the same
+    order (one torch seed gives both trainers the same start), the ZEROS rule for empty rows, the same two heads.
+
+    forward(seeds) is bit-identical to embed_nodes(..., nan_empty=False) and to FullGraphTrainer.forward()[seeds]; the loss and the
+    gradient of w_cls of grads(seeds, labels) are bit-identical to FullGraphTrainer.grads(seeds, labels) (the head sees the same rows
+    in the same order); the gradients of w1 and w2 are the same sums over fewer rows in another association: equal to rounding.
+
+    seeds: DISTINCT int32 node ids on the device, as FullGraphTrainer.grads requires of train_ids (the concat encoder's own-row
+    gradient is placed with index_copy_, never with an atomic scatter).  An id outside the graph raises.
+    Host reads per step: embed_nodes' two (the seeds' outer edge count with their range; |F| with F's inner edge count).
+    The trainer owns one persistent ops.CsrFrontier; its map is cleared after the backward has read it, also when a step raises.
+    The frontier's rows are put in ascending id order before layer 1 runs, so two runs of a step give the same bits."""
+
+    def __init__(self, rowptr, col, table, num_classes, hidden1=50, hidden2=128, gcn=True, lr=0.7, agg_self_loop=False, head="native",
+                 rowptr_outer=None, col_outer=None, act1=ACT_RELU):
+        if head not in ("torch", "native"):
+            raise SageError(f"ExactBatchTrainer: head = {head!r}, expected 'torch' or 'native'")
+        if act1 not in (ACT_RELU, ACT_SIGMOID):
+            raise SageError(f"ExactBatchTrainer: act1 = {act1!r}, expected ACT_RELU or ACT_SIGMOID")
+        ops._need_gpu()
+        if head == "native" and not ops.xent_head_supported(hidden2, num_classes):
+            raise SageError(f"ExactBatchTrainer: head='native' has no kernel for hidden2 = {hidden2}, num_classes = {num_classes}")
+        ops._chk(rowptr, torch.int64, "rowptr", 1)
+        ops._chk(col, torch.int32, "col", 1)
+        table, _ = ops._row_major(table, "table")
+        self.rowptr, self.col = rowptr, col
+        self.rowptr2 = rowptr if rowptr_outer is None else ops._chk(rowptr_outer, torch.int64, "rowptr_outer", 1)
+        self.col2 = col if col_outer is None else ops._chk(col_outer, torch.int32, "col_outer", 1)
+        if self.rowptr2.shape[0] != rowptr.shape[0]:
+            raise SageError("inner and outer CSR must cover the same node ids")
+        self.n = rowptr.shape[0] - 1
+        if self.n < 1 or table.shape[0] < self.n:
+            raise SageError(f"ExactBatchTrainer: table has {table.shape[0]} rows for {self.n} nodes")
+        self.table, self.dev = table, table.device
+        self.head, self.lr, self.concat, self.self_loop, self.act1 = head, float(lr), not gcn, bool(agg_self_loop), act1
+        m = 1 if gcn else 2
+        self.d0, self.h1, self.h2 = table.shape[1], int(hidden1), int(hidden2)
+        self.w1 = torch.empty(hidden1, m * self.d0, device=self.dev)
+        self.w2 = torch.empty(hidden2, m * hidden1, device=self.dev)
+        self.w_cls = torch.empty(num_classes, hidden2, device=self.dev)
+        for w in (self.w1, self.w2, self.w_cls):
+            init.xavier_uniform_(w)
+        dist.broadcast_params(self.parameters())
+        self.frontier = ops.CsrFrontier(self.n, self.dev, max_nodes=0)
+        self._ws, self._refill = {}, False
+
+    def parameters(self):
+        return [self.w1, self.w2, self.w_cls]
+
+    _scratch = FullGraphTrainer._scratch
+    _linear_backward = FullGraphTrainer._linear_backward     # sage_linear_act_backward_ws over the rows it is given
+
+    def _forward(self, seeds):
+        """The forward of one batch; the frontier's map stays FILLED for the backward (the callers clear it in a finally).
+        -> dict of what the backward reads: the frontier's nodes, the seeds' rows, agg1, h1_F, agg2, out and the two edge counts."""
+        ops._chk(seeds, torch.int32, "seeds", 1)
+        m, fr = seeds.shape[0], self.frontier
+        if m < 1:
+            raise SageError("ExactBatchTrainer: no seeds")
+        # host read 1: the seeds' outer edges, and their range (sage_linear_act does not clamp the own-row index)
+        e2, lo, hi = torch.stack([_row_edges(self.rowptr2, seeds), seeds.min().long(), seeds.max().long()]).tolist()
+        if lo < 0 or hi >= self.n:
+            raise SageError(f"ExactBatchTrainer: seed id {lo if lo < 0 else hi} outside [0, {self.n})")
+        bound = min(self.n, m + e2)
+        fr.reserve(bound)
+        ops.csr_frontier(self.rowptr2, self.col2, seeds, fr, max_edges=e2)
+        # host read 2: |F| and the inner edges of F's rows
+        size, e1 = torch.stack([fr.count[0].long(), _row_edges(self.rowptr, fr.nodes[:bound], live=fr.count[0])]).tolist()
+        if size > bound:
+            self._refill = size > fr.max_nodes               # overflow: `nodes` no longer names every row of the map
+            raise SageError(f"ExactBatchTrainer: the frontier holds {size} ids, {bound} at most are the seeds': it was not clear")
+        # The frontier hands its rows out in whatever order its waves won them.  The rows' values do not depend on that, but dW1 adds
+        # the rows up in row order: put F in ascending id order (|F| integers sorted, the map rewritten), so that a step's bits
+        # depend on the seeds alone.
+        f_nodes = fr.nodes[:size]
+        f_nodes.copy_(torch.sort(f_nodes).values)
+        fr.pos.index_copy_(0, f_nodes.long(), torch.arange(size, dtype=torch.int32, device=self.dev))
+        ws = self._scratch("mean", max(ops.csr_mean_workspace_bytes(size, e1, self.d0), ops.csr_mean_workspace_bytes(m, e2, self.h1)))
+        agg1 = ops.csr_mean(self.rowptr, self.col, self.table, nodes=f_nodes, self_loop=self.self_loop, max_edges=e1, workspace=ws)
+        h1_f = ops.linear_act(agg1, self.w1, self.act1, self_tab=self.table if self.concat else None,
+                              self_index=f_nodes if self.concat else None)
+        agg2 = ops.csr_mean(self.rowptr2, self.col2, h1_f, nodes=seeds, self_loop=self.self_loop, max_edges=e2, workspace=ws, index=fr.pos)
+        rows = fr.pos[seeds.long()] if self.concat else None           # the seeds' rows of h1_F
+        out = ops.linear_act(agg2, self.w2, ACT_RELU, self_tab=h1_f if self.concat else None, self_index=rows)
+        return dict(f_nodes=f_nodes, rows=rows, agg1=agg1, h1_f=h1_f, agg2=agg2, out=out, e2=e2)
+
+    def _clear(self):
+        if self._refill:
+            self.frontier.refill()
+            self._refill = False
+        else:
+            self.frontier.clear()
+
+    def forward(self, seeds):
+        """[len(seeds), h2] embeddings of the nodes `seeds` (int32 on the device; here they may repeat)."""
+        try:
+            return self._forward(seeds)["out"]
+        finally:
+            self._clear()
+
+    def grads(self, seeds, labels):
+        """loss (device scalar) and the gradients of (w1, w2, w_cls) on the batch; nothing is updated.
+        seeds: DISTINCT int32 node ids on the device, labels int64 [len(seeds)]."""
+        ops._chk(seeds, torch.int32, "seeds", 1)
+        ops._chk(labels, torch.int64, "labels", 1)
+        b = seeds.shape[0]
+        if b < 1 or labels.shape[0] != b:
+            raise SageError(f"ExactBatchTrainer.grads: {b} seeds, {labels.shape[0]} labels")
+        try:
+            f = self._forward(seeds)
+            emb = f["out"]                                   # row r = node seeds[r]: what FullGraphTrainer selects out of its [N, h2]
+            if self.head == "native":
+                r = ops.xent_head(emb, self.w_cls, labels, scale=1.0 / b,
+                                  workspace=self._scratch("head", ops.xent_head_workspace_bytes(b, self.h2, self.w_cls.shape[0])))
+                loss, g_emb, g_cls = r["loss"][0], r["grad_emb"], r["grad_w"]
+            else:
+                scores = (emb @ self.w_cls.t()).requires_grad_(True)
+                loss = torch.nn.functional.cross_entropy(scores, labels)
+                (g_scores,) = torch.autograd.grad(loss, (scores,))
+                loss = loss.detach()
+                g_emb = g_scores @ self.w_cls
+                g_cls = _sum_over_batch(g_scores, emb)
+            # layer 2 over the seed rows: dW2 and d[h1_self | agg2]
+            g_w2, g_x2 = self._linear_backward(f["h1_f"] if self.concat else None, f["agg2"], self.w2, ACT_RELU, emb, g_emb, True,
+                                               "linear_act_backward (layer 2)", self_index=f["rows"])
+            ds = self.h1 if self.concat else 0
+            size = f["f_nodes"].shape[0]
+            ws = self._scratch("mean2_bwd", ops.csr_mean_backward_rows_workspace_bytes(b, f["e2"], size, self.h1))
+            g_h1 = ops.csr_mean_backward_rows(self.rowptr2, self.col2, seeds, g_x2[:, ds:], index=self.frontier.pos, num_rows=size,
+                                              self_loop=self.self_loop, max_edges=f["e2"], workspace=ws)
+            if self.concat:                                  # the own-row part, onto the seeds' rows of h1_F: distinct, so no two writers
+                rows = f["rows"].long()
+                g_h1.index_copy_(0, rows, g_h1.index_select(0, rows) + g_x2[:, :ds])
+            # layer 1 over the frontier's rows: only dW1, the table is frozen
+            g_w1, _ = self._linear_backward(self.table if self.concat else None, f["agg1"], self.w1, self.act1, f["h1_f"], g_h1, False,
+                                            "linear_act_backward (layer 1)", self_index=f["f_nodes"] if self.concat else None)
+            return loss, (g_w1, g_w2, g_cls)
+        finally:
+            self._clear()
+
+    def step(self, seeds, labels):
+        """forward + backward + in-place SGD; -> the loss as a device scalar."""
+        loss, g = self.grads(seeds, labels)
+        for w, gw in zip(self.parameters(), g):
+            w.add_(gw, alpha=-self.lr)
+        return loss
+
+    def predict(self, ids):
+        """int32 classes of the nodes `ids` (int32 on the device): the class of the highest score (model.py:256)."""
+        emb = self.forward(ids)
+        if self.head != "native":
+            return (emb @ self.w_cls.t()).argmax(1).to(torch.int32)
+        return ops.xent_head(emb, self.w_cls, grads=False, pred=True)["pred"]
+
+
+def run_exact_batch_training(graph, feat_data, labels, num_classes, seed=1, epochs=1, batch_size=128, ref_batching=False, lr=0.7,
+                             hidden1=50, hidden2=128, gcn=True, agg_self_loop=False, head="native"):
+    """run_model (model.py:184-259) with num_sample=None batches: the same split, shuffles, batching and SGD as
+    train.run_engine_training, every step through ExactBatchTrainer, validation by its predict (full neighbourhoods as well).
+    -> dict(f1_micro, f1_macro, mean_step_time, losses, trainer), as train.run_engine_training."""
+    from sklearn.metrics import f1_score
+    dev = torch.device("cuda")
+    np.random.seed(seed)
+    rowptr, col = graph.to(dev)
+    n = graph.num_nodes
+    table = torch.as_tensor(feat_data, dtype=torch.float32).to(dev)
+    rand_indices = np.random.permutation(n)
+    val = rand_indices[int(0.1 * n):int(0.2 * n)]
+    train = list(rand_indices[int(0.2 * n):])
+    tr = ExactBatchTrainer(rowptr, col, table, num_classes, hidden1, hidden2, gcn=gcn, lr=lr, agg_self_loop=agg_self_loop, head=head)
+    labels_dev = torch.as_tensor(np.asarray(labels).reshape(-1), dtype=torch.int64).to(dev)
+    shuffler = random.Random(seed)
+    losses, steps = [], 0
+    torch.cuda.synchronize()
+    t0 = time.time()
+    for _ in range(epochs):
+        shuffler.shuffle(train)
+        order = torch.as_tensor(np.asarray(train), dtype=torch.int32).to(dev)
+        for lo in range(0, len(train), batch_size):
+            hi = max(len(train), lo + batch_size) if ref_batching else min(len(train), lo + batch_size)
+            ids = order[lo:hi].contiguous()
+            losses.append(tr.step(ids, labels_dev[ids.long()]))
+            steps += 1
+    torch.cuda.synchronize()
+    elapsed = time.time() - t0
+    pred = tr.predict(torch.as_tensor(val.astype(np.int32)).to(dev)).cpu().numpy()
+    truth = np.asarray(labels)[val].reshape(-1)
+    return {"f1_micro": float(f1_score(truth, pred, average="micro")), "f1_macro": float(f1_score(truth, pred, average="macro")),
+            "mean_step_time": elapsed / max(steps, 1), "losses": [float(x) for x in losses], "trainer": tr}

@@ -595,6 +595,75 @@ def csr_mean_backward_grouped(rowptr, col, grouped, grad_out, out=None, max_edge
     return out
 
 
+def csr_mean_backward_rows_workspace_bytes(n, max_edges, num_rows, dim):
+    """Bytes of the workspace sage_csr_mean_backward_rows needs (host arithmetic; 0 = shape out of range)."""
+    return int(native.lib().sage_csr_mean_backward_rows_workspace_bytes(int(n), int(max_edges), int(num_rows), int(dim)))
+
+
+def csr_mean_backward_rows(rowptr, col, nodes, grad_out, index=None, num_rows=None, self_loop=False, out=None, max_edges=None,
+                           workspace=None, total_terms=None):
+    """The adjoint of csr_mean(rowptr, col, table, nodes=nodes, index=index) with respect to `table`: [num_rows, dim], the
+    gradient of every row of the table the seed batch read (sage_csr_mean_backward_rows: the batch's terms sorted by table row,
+    512-term chunks, fixed order, no float atomics).  nodes: int32 [n] on the device, may repeat; grad_out [n, dim], by seed ROW.
+    index: int32 [num_nodes] -- a frontier's id -> row map (CsrFrontier.pos) or an embedding index; num_rows = the table's rows,
+    default num_nodes without an index, required with one.  Stored, not accumulated: a row nobody read is zeros.
+    max_edges: upper bound on the entries of the seeds' rows; None costs one host read of their count.  A bound below the truth
+    DROPS the terms past it: total_terms (int64 [1] on the device) receives the true term count (entries + self terms).
+    workspace: a uint8 device tensor to reuse."""
+    _need_gpu()
+    _chk(rowptr, torch.int64, "rowptr", 1)
+    _chk(col, torch.int32, "col", 1)
+    _chk(nodes, torch.int32, "nodes", 1)
+    grad_out, ldg = _row_major(grad_out, "grad_out")
+    num_nodes = rowptr.shape[0] - 1
+    if num_nodes < 0:
+        raise native.SageError("csr_mean_backward_rows: rowptr is empty")
+    n, dim = nodes.shape[0], grad_out.shape[1]
+    if grad_out.shape[0] < n:
+        raise native.SageError(f"csr_mean_backward_rows: grad_out has {grad_out.shape[0]} rows for {n} seed rows")
+    if index is not None:
+        _chk(index, torch.int32, "index", 1)
+        if index.shape[0] != num_nodes:
+            raise native.SageError(f"csr_mean_backward_rows: index has {index.shape[0]} entries for {num_nodes} nodes")
+        if num_rows is None:
+            raise native.SageError("csr_mean_backward_rows: num_rows is required with an index")
+    rows = num_nodes if num_rows is None else int(num_rows)
+    if rows < 0 or (rows == 0 and n > 0):
+        raise native.SageError(f"csr_mean_backward_rows: num_rows = {rows} with {n} seed rows")
+    dev = grad_out.device
+    if out is None:
+        out = torch.empty((rows, dim), dtype=torch.float32, device=dev)
+    out, ldgt = _row_major(out, "out")
+    if out.shape[0] < rows or out.shape[1] != dim:
+        raise native.SageError(f"csr_mean_backward_rows: out is {tuple(out.shape)}, expected ({rows}, {dim})")
+    if total_terms is not None:
+        _chk(total_terms, torch.int64, "total_terms", 1)
+    if rows == 0:
+        return out
+    if max_edges is None:                                 # the host read: the entries of the seeds' rows (ids clamped into the graph)
+        v = nodes.long().clamp_(0, max(num_nodes - 1, 0))
+        max_edges = int((rowptr[v + 1] - rowptr[v]).clamp_(min=0).sum()) if n > 0 and num_nodes > 0 else 0
+    max_edges = int(max_edges)
+    # an empty tensor may have no storage address: the kernels read none of it
+    if col.numel() == 0:
+        col = torch.zeros(1, dtype=torch.int32, device=dev)
+    if n == 0:
+        nodes, grad_out, ldg = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros((1, dim), dtype=torch.float32, device=dev), dim
+    if index is not None and index.numel() == 0:
+        index = torch.zeros(1, dtype=torch.int32, device=dev)
+    need = csr_mean_backward_rows_workspace_bytes(n, max_edges, rows, dim)
+    if need == 0:
+        raise native.SageError(f"csr_mean_backward_rows: n = {n}, max_edges = {max_edges}, num_rows = {rows}, dim = {dim} out of range")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    rc = native.lib().sage_csr_mean_backward_rows(native.ptr(rowptr), native.ptr(col), num_nodes, native.ptr(nodes), n, max_edges,
+                                                  native.ptr(index), rows, native.ptr(grad_out), ldg, dim, 1 if self_loop else 0,
+                                                  native.ptr(out), ldgt, native.ptr(total_terms), native.ptr(workspace), workspace.numel(),
+                                                  native.stream_handle())
+    native.check(rc, "csr_mean_backward_rows")
+    return out
+
+
 def group_rows(index, num_groups):
     """(rowptr_g int64 [K + 1], col_g int32 [N]) of an index [N] with values in [0, K = num_groups): row k of this rectangular
     CSR holds the positions v with index[v] == k, ascending -- what csr_sum adds up for row k of a shared embedding

@@ -338,6 +338,63 @@ int sage_csr_mean_backward_grouped(const int64_t* rowptr, const int32_t* col,
                                    void* workspace, size_t workspace_bytes, sage_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * sage_csr_mean_backward_rows (additive, ABI 9) -- the adjoint, with respect
+ * to `table` ([num_rows, dim]), of sage_csr_mean_indexed(nodes, n, index), or
+ * of sage_csr_mean(nodes, n) when index is NULL: the backward of a SEED BATCH
+ * embedded from its full neighbourhoods (aggregators.py:47-48 num_sample=None)
+ * through the compact rows of sage_csr_frontier.  The transposed sub-graph it
+ * sums over exists for this batch only and is built inside the call.
+ * With the forward's own definitions, for seed row r, v = nodes[r]:
+ *     extra_r = self_loop && v is not an entry of its own row   (set union)
+ *     c_r     = deg(v) + extra_r         (entries counted with multiplicity)
+ *     w_r     = c_r > 0 ? 1.0f / (float)c_r : 0         (the forward's float)
+ * the TERMS of the batch are, in this order: for r = 0 .. n-1 the entries of
+ * row v in stored order, then v itself if extra_r.  A term with node id `id`
+ * goes to table row
+ *     key = clamp(index ? index[clamp(id, 0, num_nodes-1)] : id, 0, num_rows-1)
+ * -- exactly the forward's clamps, so the result is the adjoint of what the
+ * forward computed even for a bad map, and no read or write leaves an array.
+ *     grad_table[f, :] = the terms with key == f in the order above (ascending
+ *                        r, then position inside the row), each as ONE
+ *                        fma(w_r, grad_out[r, :], acc); more than
+ *                        SAGE_CSR_MEAN_CHUNK terms: chunks summed separately,
+ *                        partials added in chunk order
+ * which is sage_csr_mean_backward_grouped's arithmetic over the sorted term
+ * list (the terms are laid out by position, sorted by key with a stable radix
+ * sort, and summed by that entry's kernels).
+ * grad_out is [n, dim], indexed by seed ROW (not by node id), leading dimension
+ * ldg; nodes may repeat, each row is a term source of its own; a node id
+ * outside [0, num_nodes) is an empty row without a self term.  grad_table,
+ * leading dimension ldgt, is STORED, not accumulated: a row with no term is
+ * exact zeros; columns [dim, ldgt) are not written.  No float atomics: a row's
+ * bits depend only on its own term sequence -- not on where the frontier put
+ * the row, not on the other rows, not on the run.
+ * max_edges bounds the entries of the selected rows.  The terms get
+ * max_edges + (self_loop ? n : 0) positions, and HERE a bound that is too small
+ * is not "slower only": terms at positions past that capacity are DROPPED
+ * (nothing is written out of range).  *total_terms (int64 on the device,
+ * nullable) receives the true term count, so the caller can tell.
+ * max_edges + n must stay below 2^31 (the workspace serves either self_loop).
+ * Any dim >= 1, ldg >= dim, ldgt >= dim; 16-byte accesses when dim, ldg, ldgt
+ * are multiples of 4 and both arrays are 16-byte aligned.
+ * Validation, before any launch: shapes (num_nodes in [0, 2^31), n >= 0,
+ * max_edges >= 0, num_rows in [0, 2^31 - 1), num_rows == 0 only with n == 0,
+ * dim and leading dimensions, self_loop 0 / 1), then NULL arrays (rowptr, col,
+ * nodes, grad_out, grad_table: SAGE_EINVAL), then the workspace (short or
+ * missing: SAGE_ENOSPACE; 256-byte aligned).  num_rows == 0 returns SAGE_OK
+ * without a launch; n == 0 stores zeros in all num_rows rows.  The size query
+ * is host arithmetic and returns 0 for a shape out of range.
+ * ------------------------------------------------------------------------- */
+size_t sage_csr_mean_backward_rows_workspace_bytes(int32_t n, int64_t max_edges, int64_t num_rows, int32_t dim);
+int sage_csr_mean_backward_rows(const int64_t* rowptr, const int32_t* col, int64_t num_nodes,
+                                const int32_t* nodes, int32_t n, int64_t max_edges,
+                                const int32_t* index /* nullable */, int64_t num_rows,
+                                const float* grad_out, int64_t ldg, int32_t dim, int32_t self_loop,
+                                float* grad_table, int64_t ldgt,
+                                int64_t* total_terms /* nullable, device */,
+                                void* workspace, size_t workspace_bytes, sage_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * sage_csr_sum (additive, ABI 9) -- the gradient of a shared embedding row.
  * aggregators.py:68-71 looks features up in a trainable nn.Embedding: node v
  * reads row index[v] (its own row for 1hot, its degree's row for node_degree),
