@@ -532,7 +532,7 @@ class TwoHopEngine:
         dev = self.device
         if self._bwd is None or self._bwd["max_s1"] != L.max_s1:
             self._bwd = {"max_s1": L.max_s1, "nlive": torch.zeros(1, dtype=torch.int32, device=dev),
-                         "agg1": None,
+                         "agg1": None, "scratch": ops.Scratch(dev),
                          "any": torch.ones(1, dtype=torch.int32, device=dev)}
         sc = self._bwd
         first = b if self.concat else 0
@@ -544,24 +544,16 @@ class TwoHopEngine:
         w1p, w2p = self._weights()
         h1, row2, cnt2, nbr1, cnt1, s1_nodes = ws("h1"), ws("row2"), ws("cnt2"), ws("nbr1"), ws("cnt1"), ws("s1_nodes")
         self_row2 = ws("self_row2") if self.agg_self_loop else None
-        def scratch(name, nbytes):
-            t = sc.get(name)
-            if t is None or t.numel() < nbytes:
-                t = sc[name] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=dev)
-            return t
+        scratch = sc["scratch"].get
 
         # ---- layer 2 backward: agg2 is recomputed (one small gather), then dW2 and d[h1_self | agg2].  The *_ws entry points are
         #      the reproducible forms (partial tiles added in a fixed order; inverted index instead of atomics): two runs of one
         #      schedule give the same bits, and a captured step equals the eager one bit for bit
         agg2 = ops.gather_mean(h1, row2, cnt2, self_row=self_row2, any_nonempty=sc["any"])
         mult = 2 if self.concat else 1
-        g_w2p = torch.zeros_like(w2p)
-        g_x2 = torch.empty(b, mult * h1p, device=dev)
-        ws2 = scratch("ws_dw2", lib.sage_linear_act_backward_workspace_bytes(b, h1p, int(self.concat), self.h2))
-        native.check(lib.sage_linear_act_backward_ws(P(h1) if self.concat else None, h1p, None, P(agg2), agg2.stride(0), h1p, P(w2p),
-                                                     w2p.stride(0), self.h2, self.act2, P(out), out.stride(0), P(grad_out), grad_out.stride(0), b, None,
-                                                     P(g_w2p), g_w2p.stride(0), P(g_x2) if (need_w1 or need_embed) else None, g_x2.stride(0), None,
-                                                     P(ws2), ws2.numel(), st), "linear_act_backward (layer 2)")
+        g_w2p, g_x2 = ops.linear_act_backward(agg2, w2p, self.act2, out, grad_out, self_tab=h1 if self.concat else None,
+                                              need_x=bool(need_w1 or need_embed),
+                                              workspace=scratch("ws_dw2", ops.linear_act_backward_workspace_bytes(b, h1p, self.concat, self.h2)))
         g_w1p = None
         if need_w1 or need_embed:
             # ---- layer 1 backward: only dW1 (the table is frozen), summed over the OUTER EDGES (sage_two_hop_grad_w1): the terms
@@ -596,18 +588,15 @@ class TwoHopEngine:
         n1, k1, rows = L.max_s1, self.k1, self.embed_rows
         if sc.get("g_h1") is None:
             sc["g_h1"] = torch.empty(n1, h1p, device=dev)
-            sc["g_agg1"] = torch.empty(n1, d0p, device=dev)
             sc["order"] = torch.empty(n1, dtype=torch.int32, device=dev)
-        g_h1, g_agg1, order = sc["g_h1"], sc["g_agg1"], sc["order"]
+        g_h1, order = sc["g_h1"], sc["order"]
         # 1. d loss / d h1: the layer-2 mean's backward over the outer samples, terms in (seed, slot) order; rows [0, nlive) are stored
         wsg = scratch("ws_gh1", lib.sage_gather_mean_backward_workspace_bytes(b, k2, n1))
         native.check(lib.sage_gather_mean_backward_ws(P(g_x2), g_x2.stride(0), h1p, P(row2), P(cnt2), k2, b, None, None, None, P(g_h1), n1,
                                                       P(sc["nlive"]), h1p, P(wsg), wsg.numel(), st), "gather_mean_backward_ws (layer 2)")
         # 2. d loss / d layer-1 means: layer 1's grad_x on the kept means (per row: no order to fix, and without a weight gradient
         #    the entry point takes no workspace)
-        native.check(lib.sage_linear_act_backward_ws(None, d0p, None, P(agg1), agg1.stride(0), d0p, P(w1p), w1p.stride(0), h1p, self.act1, P(h1),
-                                                     h1p, P(g_h1), h1p, n1, P(sc["nlive"]), None, w1p.stride(0), P(g_agg1), d0p, None,
-                                                     None, 0, st), "linear_act_backward (layer 1, grad_x)")
+        _, g_agg1 = ops.linear_act_backward(agg1, w1p, self.act1, h1, g_h1, n_dev=sc["nlive"], need_w=False)
         # 3. the frontier's rows by ascending node id, 4. the chunked sum over the sampled sets, which hold embedding rows
         wso = scratch("ws_order", lib.sage_row_order_workspace_bytes(n1))
         native.check(lib.sage_row_order(P(s1_nodes), n1, P(sc["nlive"]), 0, P(order), P(wso), wso.numel(), st), "row_order")

@@ -13,18 +13,17 @@ import time
 
 import numpy as np
 import torch
-from torch.nn import init
 
 from . import dist, ops
-from .fullgraph import FullGraphTrainer
-from .inference import _row_edges
-from .native import ACT_RELU, ACT_SIGMOID, SageError
-from .train import _sum_over_batch
+from .head import head_grads, head_predict
+from .inference import _seed_frontier
+from .native import ACT_RELU, SageError
+from .train import _batches, _split, _validation_result, check_trainer_args, csr_pair, init_parameters
 
 
 class ExactBatchTrainer:
-    """The frozen-table form of FullGraphTrainer for seed batches: the same arguments, the weights w1, w2, w_cls drawn in the same
-    order (one torch seed gives both trainers the same start), the ZEROS rule for empty rows, the same two heads.
+    """The frozen-table form of FullGraphTrainer for seed batches: the same arguments, the weights w1, w2, w_cls drawn by the same
+    train.init_parameters (one torch seed gives both trainers the same start), the ZEROS rule for empty rows, the same two heads.
 
     forward(seeds) is bit-identical to embed_nodes(..., nan_empty=False) and to FullGraphTrainer.forward()[seeds]; the loss and the
     gradient of w_cls of grads(seeds, labels) are bit-identical to FullGraphTrainer.grads(seeds, labels) (the head sees the same rows
@@ -38,42 +37,24 @@ class ExactBatchTrainer:
 
     def __init__(self, rowptr, col, table, num_classes, hidden1=50, hidden2=128, gcn=True, lr=0.7, agg_self_loop=False, head="native",
                  rowptr_outer=None, col_outer=None, act1=ACT_RELU):
-        if head not in ("torch", "native"):
-            raise SageError(f"ExactBatchTrainer: head = {head!r}, expected 'torch' or 'native'")
-        if act1 not in (ACT_RELU, ACT_SIGMOID):
-            raise SageError(f"ExactBatchTrainer: act1 = {act1!r}, expected ACT_RELU or ACT_SIGMOID")
+        check_trainer_args("ExactBatchTrainer", head, act1, hidden2, num_classes)
         ops._need_gpu()
-        if head == "native" and not ops.xent_head_supported(hidden2, num_classes):
-            raise SageError(f"ExactBatchTrainer: head='native' has no kernel for hidden2 = {hidden2}, num_classes = {num_classes}")
-        ops._chk(rowptr, torch.int64, "rowptr", 1)
-        ops._chk(col, torch.int32, "col", 1)
-        table, _ = ops._row_major(table, "table")
         self.rowptr, self.col = rowptr, col
-        self.rowptr2 = rowptr if rowptr_outer is None else ops._chk(rowptr_outer, torch.int64, "rowptr_outer", 1)
-        self.col2 = col if col_outer is None else ops._chk(col_outer, torch.int32, "col_outer", 1)
-        if self.rowptr2.shape[0] != rowptr.shape[0]:
-            raise SageError("inner and outer CSR must cover the same node ids")
+        self.rowptr2, self.col2 = csr_pair(rowptr, col, rowptr_outer, col_outer)
+        table, _ = ops._row_major(table, "table")
         self.n = rowptr.shape[0] - 1
         if self.n < 1 or table.shape[0] < self.n:
             raise SageError(f"ExactBatchTrainer: table has {table.shape[0]} rows for {self.n} nodes")
         self.table, self.dev = table, table.device
         self.head, self.lr, self.concat, self.self_loop, self.act1 = head, float(lr), not gcn, bool(agg_self_loop), act1
-        m = 1 if gcn else 2
         self.d0, self.h1, self.h2 = table.shape[1], int(hidden1), int(hidden2)
-        self.w1 = torch.empty(hidden1, m * self.d0, device=self.dev)
-        self.w2 = torch.empty(hidden2, m * hidden1, device=self.dev)
-        self.w_cls = torch.empty(num_classes, hidden2, device=self.dev)
-        for w in (self.w1, self.w2, self.w_cls):
-            init.xavier_uniform_(w)
+        self.w1, self.w2, self.w_cls, _ = init_parameters(self.dev, self.d0, hidden1, hidden2, num_classes, gcn)
         dist.broadcast_params(self.parameters())
         self.frontier = ops.CsrFrontier(self.n, self.dev, max_nodes=0)
-        self._ws, self._refill = {}, False
+        self.scratch = ops.Scratch(self.dev)
 
     def parameters(self):
         return [self.w1, self.w2, self.w_cls]
-
-    _scratch = FullGraphTrainer._scratch
-    _linear_backward = FullGraphTrainer._linear_backward     # sage_linear_act_backward_ws over the rows it is given
 
     def _forward(self, seeds):
         """The forward of one batch; the frontier's map stays FILLED for the backward (the callers clear it in a finally).
@@ -82,25 +63,14 @@ class ExactBatchTrainer:
         m, fr = seeds.shape[0], self.frontier
         if m < 1:
             raise SageError("ExactBatchTrainer: no seeds")
-        # host read 1: the seeds' outer edges, and their range (sage_linear_act does not clamp the own-row index)
-        e2, lo, hi = torch.stack([_row_edges(self.rowptr2, seeds), seeds.min().long(), seeds.max().long()]).tolist()
-        if lo < 0 or hi >= self.n:
-            raise SageError(f"ExactBatchTrainer: seed id {lo if lo < 0 else hi} outside [0, {self.n})")
-        bound = min(self.n, m + e2)
-        fr.reserve(bound)
-        ops.csr_frontier(self.rowptr2, self.col2, seeds, fr, max_edges=e2)
-        # host read 2: |F| and the inner edges of F's rows
-        size, e1 = torch.stack([fr.count[0].long(), _row_edges(self.rowptr, fr.nodes[:bound], live=fr.count[0])]).tolist()
-        if size > bound:
-            self._refill = size > fr.max_nodes               # overflow: `nodes` no longer names every row of the map
-            raise SageError(f"ExactBatchTrainer: the frontier holds {size} ids, {bound} at most are the seeds': it was not clear")
+        e2, size, e1 = _seed_frontier(self.rowptr, self.rowptr2, self.col2, seeds, fr, "ExactBatchTrainer")
         # The frontier hands its rows out in whatever order its waves won them.  The rows' values do not depend on that, but dW1 adds
         # the rows up in row order: put F in ascending id order (|F| integers sorted, the map rewritten), so that a step's bits
         # depend on the seeds alone.
         f_nodes = fr.nodes[:size]
         f_nodes.copy_(torch.sort(f_nodes).values)
         fr.pos.index_copy_(0, f_nodes.long(), torch.arange(size, dtype=torch.int32, device=self.dev))
-        ws = self._scratch("mean", max(ops.csr_mean_workspace_bytes(size, e1, self.d0), ops.csr_mean_workspace_bytes(m, e2, self.h1)))
+        ws = self.scratch.get("mean", max(ops.csr_mean_workspace_bytes(size, e1, self.d0), ops.csr_mean_workspace_bytes(m, e2, self.h1)))
         agg1 = ops.csr_mean(self.rowptr, self.col, self.table, nodes=f_nodes, self_loop=self.self_loop, max_edges=e1, workspace=ws)
         h1_f = ops.linear_act(agg1, self.w1, self.act1, self_tab=self.table if self.concat else None,
                               self_index=f_nodes if self.concat else None)
@@ -109,19 +79,12 @@ class ExactBatchTrainer:
         out = ops.linear_act(agg2, self.w2, ACT_RELU, self_tab=h1_f if self.concat else None, self_index=rows)
         return dict(f_nodes=f_nodes, rows=rows, agg1=agg1, h1_f=h1_f, agg2=agg2, out=out, e2=e2)
 
-    def _clear(self):
-        if self._refill:
-            self.frontier.refill()
-            self._refill = False
-        else:
-            self.frontier.clear()
-
     def forward(self, seeds):
         """[len(seeds), h2] embeddings of the nodes `seeds` (int32 on the device; here they may repeat)."""
         try:
             return self._forward(seeds)["out"]
         finally:
-            self._clear()
+            self.frontier.clear()
 
     def grads(self, seeds, labels):
         """loss (device scalar) and the gradients of (w1, w2, w_cls) on the batch; nothing is updated.
@@ -134,34 +97,27 @@ class ExactBatchTrainer:
         try:
             f = self._forward(seeds)
             emb = f["out"]                                   # row r = node seeds[r]: what FullGraphTrainer selects out of its [N, h2]
-            if self.head == "native":
-                r = ops.xent_head(emb, self.w_cls, labels, scale=1.0 / b,
-                                  workspace=self._scratch("head", ops.xent_head_workspace_bytes(b, self.h2, self.w_cls.shape[0])))
-                loss, g_emb, g_cls = r["loss"][0], r["grad_emb"], r["grad_w"]
-            else:
-                scores = (emb @ self.w_cls.t()).requires_grad_(True)
-                loss = torch.nn.functional.cross_entropy(scores, labels)
-                (g_scores,) = torch.autograd.grad(loss, (scores,))
-                loss = loss.detach()
-                g_emb = g_scores @ self.w_cls
-                g_cls = _sum_over_batch(g_scores, emb)
-            # layer 2 over the seed rows: dW2 and d[h1_self | agg2]
-            g_w2, g_x2 = self._linear_backward(f["h1_f"] if self.concat else None, f["agg2"], self.w2, ACT_RELU, emb, g_emb, True,
-                                               "linear_act_backward (layer 2)", self_index=f["rows"])
-            ds = self.h1 if self.concat else 0
+            ws = self.scratch.get("head", ops.xent_head_workspace_bytes(b, self.h2, self.w_cls.shape[0])) if self.head == "native" else None
+            loss, g_emb, g_cls = head_grads(emb, self.w_cls, labels, self.head, b, workspace=ws)
             size = f["f_nodes"].shape[0]
-            ws = self._scratch("mean2_bwd", ops.csr_mean_backward_rows_workspace_bytes(b, f["e2"], size, self.h1))
+            dw = self.scratch.get("dw", max(ops.linear_act_backward_workspace_bytes(b, self.h1, self.concat, self.h2),
+                                            ops.linear_act_backward_workspace_bytes(size, self.d0, self.concat, self.h1)))
+            # layer 2 over the seed rows: dW2 and d[h1_self | agg2]
+            g_w2, g_x2 = ops.linear_act_backward(f["agg2"], self.w2, ACT_RELU, emb, g_emb, self_tab=f["h1_f"] if self.concat else None,
+                                                 self_index=f["rows"], workspace=dw)
+            ds = self.h1 if self.concat else 0
+            ws = self.scratch.get("mean2_bwd", ops.csr_mean_backward_rows_workspace_bytes(b, f["e2"], size, self.h1))
             g_h1 = ops.csr_mean_backward_rows(self.rowptr2, self.col2, seeds, g_x2[:, ds:], index=self.frontier.pos, num_rows=size,
                                               self_loop=self.self_loop, max_edges=f["e2"], workspace=ws)
             if self.concat:                                  # the own-row part, onto the seeds' rows of h1_F: distinct, so no two writers
                 rows = f["rows"].long()
                 g_h1.index_copy_(0, rows, g_h1.index_select(0, rows) + g_x2[:, :ds])
             # layer 1 over the frontier's rows: only dW1, the table is frozen
-            g_w1, _ = self._linear_backward(self.table if self.concat else None, f["agg1"], self.w1, self.act1, f["h1_f"], g_h1, False,
-                                            "linear_act_backward (layer 1)", self_index=f["f_nodes"] if self.concat else None)
+            g_w1, _ = ops.linear_act_backward(f["agg1"], self.w1, self.act1, f["h1_f"], g_h1, self_tab=self.table if self.concat else None,
+                                              self_index=f["f_nodes"] if self.concat else None, need_x=False, workspace=dw)
             return loss, (g_w1, g_w2, g_cls)
         finally:
-            self._clear()
+            self.frontier.clear()
 
     def step(self, seeds, labels):
         """forward + backward + in-place SGD; -> the loss as a device scalar."""
@@ -173,9 +129,7 @@ class ExactBatchTrainer:
     def predict(self, ids):
         """int32 classes of the nodes `ids` (int32 on the device): the class of the highest score (model.py:256)."""
         emb = self.forward(ids)
-        if self.head != "native":
-            return (emb @ self.w_cls.t()).argmax(1).to(torch.int32)
-        return ops.xent_head(emb, self.w_cls, grads=False, pred=True)["pred"]
+        return head_predict(emb, self.w_cls, self.head)
 
 
 def run_exact_batch_training(graph, feat_data, labels, num_classes, seed=1, epochs=1, batch_size=128, ref_batching=False, lr=0.7,
@@ -183,32 +137,18 @@ def run_exact_batch_training(graph, feat_data, labels, num_classes, seed=1, epoc
     """run_model (model.py:184-259) with num_sample=None batches: the same split, shuffles, batching and SGD as
     train.run_engine_training, every step through ExactBatchTrainer, validation by its predict (full neighbourhoods as well).
     -> dict(f1_micro, f1_macro, mean_step_time, losses, trainer), as train.run_engine_training."""
-    from sklearn.metrics import f1_score
     dev = torch.device("cuda")
-    np.random.seed(seed)
     rowptr, col = graph.to(dev)
-    n = graph.num_nodes
     table = torch.as_tensor(feat_data, dtype=torch.float32).to(dev)
-    rand_indices = np.random.permutation(n)
-    val = rand_indices[int(0.1 * n):int(0.2 * n)]
-    train = list(rand_indices[int(0.2 * n):])
+    _, val, train = _split(graph.num_nodes, seed)
     tr = ExactBatchTrainer(rowptr, col, table, num_classes, hidden1, hidden2, gcn=gcn, lr=lr, agg_self_loop=agg_self_loop, head=head)
     labels_dev = torch.as_tensor(np.asarray(labels).reshape(-1), dtype=torch.int64).to(dev)
-    shuffler = random.Random(seed)
-    losses, steps = [], 0
+    losses = []
     torch.cuda.synchronize()
     t0 = time.time()
-    for _ in range(epochs):
-        shuffler.shuffle(train)
-        order = torch.as_tensor(np.asarray(train), dtype=torch.int32).to(dev)
-        for lo in range(0, len(train), batch_size):
-            hi = max(len(train), lo + batch_size) if ref_batching else min(len(train), lo + batch_size)
-            ids = order[lo:hi].contiguous()
-            losses.append(tr.step(ids, labels_dev[ids.long()]))
-            steps += 1
+    for ids in _batches(list(train), random.Random(seed), epochs, batch_size, ref_batching, dev):
+        losses.append(tr.step(ids, labels_dev[ids.long()]))
     torch.cuda.synchronize()
     elapsed = time.time() - t0
-    pred = tr.predict(torch.as_tensor(val.astype(np.int32)).to(dev)).cpu().numpy()
-    truth = np.asarray(labels)[val].reshape(-1)
-    return {"f1_micro": float(f1_score(truth, pred, average="micro")), "f1_macro": float(f1_score(truth, pred, average="macro")),
-            "mean_step_time": elapsed / max(steps, 1), "losses": [float(x) for x in losses], "trainer": tr}
+    pred = tr.predict(torch.as_tensor(val.astype(np.int32)).to(dev))
+    return _validation_result(labels, val, pred, elapsed, len(losses), losses, tr)

@@ -23,17 +23,17 @@ import time
 
 import numpy as np
 import torch
-from torch.nn import init
 
-from . import dist, native, ops
+from . import dist, ops
+from .head import head_grads, head_predict
 from .native import ACT_RELU, ACT_SIGMOID, SageError
-from .train import _sum_over_batch
+from .train import _split, _validation_result, check_trainer_args, csr_pair, init_parameters
 
 
 class FullGraphTrainer:
     """rowptr / col: the CSR of enc1.adj_lists (layer 1), rowptr_outer / col_outer that of enc2.adj_lists (layer 2; default the
-    same), as for inference.embed_all_nodes; table [>= N, d0] is frozen.  Weights are initialised in EngineTrainer's order (w1, w2,
-    w_cls, xavier_uniform_, dist.broadcast_params): one torch seed gives both trainers the same start.
+    same), as for inference.embed_all_nodes; table [>= N, d0] is frozen.  Weights are initialised as EngineTrainer's are
+    (train.init_parameters, then dist.broadcast_params): one torch seed gives both trainers the same start.
 
     Empty rows follow the ZEROS rule (any_nonempty=None), not the reference's per-batch 0/0 = NaN rule: the weight gradients sum
     over all N rows, and a NaN row -- though its own gradient is zero -- would poison every one of them (0 * NaN).  forward() is
@@ -58,26 +58,13 @@ class FullGraphTrainer:
 
     def __init__(self, rowptr, col, table, num_classes, hidden1=50, hidden2=128, gcn=True, lr=0.7, agg_self_loop=False, head="native",
                  rowptr_outer=None, col_outer=None, embed_index=None, embed_rows=None, embed_dim=None, act1=ACT_RELU, fused_embed=False):
-        if head not in ("torch", "native"):
-            raise SageError(f"FullGraphTrainer: head = {head!r}, expected 'torch' or 'native'")
-        if act1 not in (ACT_RELU, ACT_SIGMOID):
-            raise SageError(f"FullGraphTrainer: act1 = {act1!r}, expected ACT_RELU or ACT_SIGMOID")
-        if embed_index is not None and table is not None:
-            raise SageError("FullGraphTrainer: table and embed_index are alternatives: layer 1 reads one of them")
+        check_trainer_args("FullGraphTrainer", head, act1, hidden2, num_classes, table, embed_index, embed_rows, embed_dim)
         ops._need_gpu()
-        if head == "native" and not ops.xent_head_supported(hidden2, num_classes):
-            raise SageError(f"FullGraphTrainer: head='native' has no kernel for hidden2 = {hidden2}, num_classes = {num_classes}")
-        ops._chk(rowptr, torch.int64, "rowptr", 1)
-        ops._chk(col, torch.int32, "col", 1)
-        if embed_index is None:
-            table, _ = ops._row_major(table, "table")
         self.rowptr, self.col = rowptr, col
-        self.rowptr2 = rowptr if rowptr_outer is None else ops._chk(rowptr_outer, torch.int64, "rowptr_outer", 1)
-        self.col2 = col if col_outer is None else ops._chk(col_outer, torch.int32, "col_outer", 1)
-        if self.rowptr2.shape[0] != rowptr.shape[0]:
-            raise SageError("inner and outer CSR must cover the same node ids")
+        self.rowptr2, self.col2 = csr_pair(rowptr, col, rowptr_outer, col_outer)
         self.n = rowptr.shape[0] - 1
         if embed_index is None:
+            table, _ = ops._row_major(table, "table")
             if self.n < 1 or table.shape[0] < self.n:
                 raise SageError(f"FullGraphTrainer: table has {table.shape[0]} rows for {self.n} nodes")
             dev, d0 = table.device, table.shape[1]
@@ -85,25 +72,16 @@ class FullGraphTrainer:
             ops._chk(embed_index, torch.int32, "embed_index", 1)
             if self.n < 1 or embed_index.shape[0] != self.n:
                 raise SageError(f"FullGraphTrainer: embed_index has {embed_index.shape[0]} entries for {self.n} nodes")
-            if embed_rows is None or embed_dim is None or int(embed_rows) < 1 or int(embed_dim) < 1:
-                raise SageError(f"FullGraphTrainer: embed_rows = {embed_rows!r}, embed_dim = {embed_dim!r}")
             dev, d0 = embed_index.device, int(embed_dim)
-        self.table, self.embed_index, self.embed, self.dev = table, embed_index, None, dev
+        self.table, self.embed_index, self.dev = table, embed_index, dev
         self.head, self.lr, self.concat, self.self_loop, self.act1 = head, float(lr), not gcn, bool(agg_self_loop), act1
-        m = 1 if gcn else 2
         self.d0, self.h1, self.h2 = d0, int(hidden1), int(hidden2)
-        self.w1 = torch.empty(hidden1, m * d0, device=dev)
-        self.w2 = torch.empty(hidden2, m * hidden1, device=dev)
-        self.w_cls = torch.empty(num_classes, hidden2, device=dev)
-        for w in (self.w1, self.w2, self.w_cls):
-            init.xavier_uniform_(w)
-        if embed_index is not None:
-            self.embed = torch.empty(int(embed_rows), d0, device=dev)
-            init.normal_(self.embed)
+        self.w1, self.w2, self.w_cls, self.embed = init_parameters(dev, d0, hidden1, hidden2, num_classes, gcn,
+                                                                   None if embed_index is None else embed_rows)
         dist.broadcast_params(self.parameters())
         # the transpose of the layer-2 graph: what csr_mean's backward sums over.  Built once (a sort of the edges)
         self.rowptr2_t, self.col2_t = ops.csr_transpose(self.rowptr2, self.col2)
-        self._ws = {}
+        self.scratch = ops.Scratch(dev)
         self.agg1 = self.h1_out = self.agg2 = self.out = self.x = None
         self.fused = False
         if embed_index is None:
@@ -123,18 +101,12 @@ class FullGraphTrainer:
     def parameters(self):
         return [self.w1, self.w2, self.w_cls] + ([self.embed] if self.embed is not None else [])
 
-    def _scratch(self, name, nbytes):
-        t = self._ws.get(name)
-        if t is None or t.numel() < nbytes:
-            t = self._ws[name] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self.dev)
-        return t
-
     def refresh_table(self):
         """The layer-1 mean of the (frozen) table: computed at construction, and again here after the caller changed the table.
         With a trainable embedding there is no table to refresh: the mean is computed by every forward()."""
         if self.embed is not None:
             raise SageError("FullGraphTrainer.refresh_table: layer 1 reads a trainable embedding, not a table")
-        ws = self._scratch("mean1", ops.csr_mean_workspace_bytes(self.n, self.col.numel(), self.d0))
+        ws = self.scratch.get("mean1", ops.csr_mean_workspace_bytes(self.n, self.col.numel(), self.d0))
         self.agg1 = ops.csr_mean(self.rowptr, self.col, self.table, self_loop=self.self_loop, out=self.agg1, workspace=ws)
         return self.agg1
 
@@ -145,34 +117,18 @@ class FullGraphTrainer:
             tab = self.table[:self.n]
         elif self.fused:                                     # X = embed[embed_index] is read through the index, never built
             tab, self_index = self.embed, self.embed_index
-            ws = self._scratch("mean1", ops.csr_mean_workspace_bytes(self.n, self.col.numel(), self.d0))
+            ws = self.scratch.get("mean1", ops.csr_mean_workspace_bytes(self.n, self.col.numel(), self.d0))
             self.agg1 = ops.csr_mean(self.rowptr, self.col, tab, self_loop=self.self_loop, out=self.agg1, workspace=ws, index=self_index)
         else:
             tab = self.x = self.embed if self.identity else torch.index_select(self.embed, 0, self._index64, out=self.x)
-            ws = self._scratch("mean1", ops.csr_mean_workspace_bytes(self.n, self.col.numel(), self.d0))
+            ws = self.scratch.get("mean1", ops.csr_mean_workspace_bytes(self.n, self.col.numel(), self.d0))
             self.agg1 = ops.csr_mean(self.rowptr, self.col, tab, self_loop=self.self_loop, out=self.agg1, workspace=ws)
         self.h1_out = ops.linear_act(self.agg1, self.w1, self.act1, self_tab=tab if self.concat else None,
                                      self_index=self_index if self.concat else None, out=self.h1_out)
-        ws = self._scratch("mean2", ops.csr_mean_workspace_bytes(self.n, self.col2.numel(), self.h1))
+        ws = self.scratch.get("mean2", ops.csr_mean_workspace_bytes(self.n, self.col2.numel(), self.h1))
         self.agg2 = ops.csr_mean(self.rowptr2, self.col2, self.h1_out, self_loop=self.self_loop, out=self.agg2, workspace=ws)
         self.out = ops.linear_act(self.agg2, self.w2, ACT_RELU, self_tab=self.h1_out if self.concat else None, out=self.out)
         return self.out
-
-    def _linear_backward(self, self_tab, agg, weight, act, out, grad_out, need_x, what, self_index=None):
-        """sage_linear_act_backward_ws over all N rows of a layer with activation `act` -> (grad_weight, grad_x [N, kw] or None).
-        self_index: row r's own row is self_tab[self_index[r]] (int32 [N], values inside self_tab)."""
-        lib, P = native.lib(), native.ptr
-        n, dim = agg.shape
-        out_dim, kw = weight.shape
-        g_w = torch.zeros_like(weight)
-        g_x = torch.empty(n, kw, device=agg.device) if need_x else None
-        ws = self._scratch("dw", lib.sage_linear_act_backward_workspace_bytes(n, dim, int(self_tab is not None), out_dim))
-        rc = lib.sage_linear_act_backward_ws(P(self_tab), self_tab.stride(0) if self_tab is not None else 0, P(self_index), P(agg), agg.stride(0), dim,
-                                             P(weight), weight.stride(0), out_dim, int(act), P(out), out.stride(0), P(grad_out),
-                                             grad_out.stride(0), n, None, P(g_w), g_w.stride(0), P(g_x), kw, None,
-                                             P(ws), ws.numel(), native.stream_handle())
-        native.check(rc, what)
-        return g_w, g_x
 
     def grads(self, train_ids, labels):
         """loss (device scalar) and the gradients of (w1, w2, w_cls) -- and of embed, fourth, when layer 1 reads a trainable
@@ -187,47 +143,41 @@ class FullGraphTrainer:
         out = self.forward()
         idx = train_ids.long()
         emb = out.index_select(0, idx)
-        if self.head == "native":
-            r = ops.xent_head(emb, self.w_cls, labels, scale=1.0 / b, workspace=self._scratch("head", ops.xent_head_workspace_bytes(b, self.h2, self.w_cls.shape[0])))
-            loss, g_emb, g_cls = r["loss"][0], r["grad_emb"], r["grad_w"]
-        else:
-            scores = (emb @ self.w_cls.t()).requires_grad_(True)
-            loss = torch.nn.functional.cross_entropy(scores, labels)
-            (g_scores,) = torch.autograd.grad(loss, (scores,))
-            loss = loss.detach()
-            g_emb = g_scores @ self.w_cls                                   # [B, C] x [C, H2]: reduction over the classes
-            g_cls = _sum_over_batch(g_scores, emb)                           # [C, B] x [B, H2]: reduction over the batch, fixed order
+        ws = self.scratch.get("head", ops.xent_head_workspace_bytes(b, self.h2, self.w_cls.shape[0])) if self.head == "native" else None
+        loss, g_emb, g_cls = head_grads(emb, self.w_cls, labels, self.head, b, workspace=ws)
         g_out = torch.zeros_like(out).index_copy_(0, idx, g_emb)
         # layer 2 over all N rows (a row outside the training set adds exact zeros): dW2 and d[h1_self | agg2]
-        g_w2, g_x2 = self._linear_backward(self.h1_out if self.concat else None, self.agg2, self.w2, ACT_RELU, out, g_out, True, "linear_act_backward (layer 2)")
+        dw = self.scratch.get("dw", max(ops.linear_act_backward_workspace_bytes(self.n, self.h1, self.concat, self.h2),
+                                        ops.linear_act_backward_workspace_bytes(self.n, self.d0, self.concat, self.h1)))
+        g_w2, g_x2 = ops.linear_act_backward(self.agg2, self.w2, ACT_RELU, out, g_out, self_tab=self.h1_out if self.concat else None, workspace=dw)
         ds = self.h1 if self.concat else 0
-        ws = self._scratch("mean2_bwd", ops.csr_mean_backward_workspace_bytes(self.n, self.n, self.col2_t.numel(), self.h1))
+        ws = self.scratch.get("mean2_bwd", ops.csr_mean_backward_workspace_bytes(self.n, self.n, self.col2_t.numel(), self.h1))
         g_h1 = ops.csr_mean_backward(self.rowptr2, self.col2, self.rowptr2_t, self.col2_t, g_x2[:, ds:], self_loop=self.self_loop, workspace=ws)
         if self.concat:
             g_h1 += g_x2[:, :ds]                                             # the concat encoder's own-row part
         if self.embed is None:                                               # layer 1: only dW1, the table is frozen
-            g_w1, _ = self._linear_backward(self.table[:self.n] if self.concat else None, self.agg1, self.w1, self.act1, self.h1_out, g_h1,
-                                            False, "linear_act_backward (layer 1)")
+            g_w1, _ = ops.linear_act_backward(self.agg1, self.w1, self.act1, self.h1_out, g_h1, need_x=False, workspace=dw,
+                                              self_tab=self.table[:self.n] if self.concat else None)
             return loss, (g_w1, g_w2, g_cls)
         if self.fused:
             # layer 1 through the index: dW1 and d[X_self | agg1]; every embedding row then sums its terms of the mean's adjoint in
             # one sequence, and for concat the own-row parts of the nodes that read it (ascending node order) on top
-            g_w1, g_x1 = self._linear_backward(self.embed if self.concat else None, self.agg1, self.w1, self.act1, self.h1_out, g_h1, True,
-                                               "linear_act_backward (layer 1)", self_index=self.embed_index if self.concat else None)
+            g_w1, g_x1 = ops.linear_act_backward(self.agg1, self.w1, self.act1, self.h1_out, g_h1, workspace=dw,
+                                                 self_tab=self.embed if self.concat else None, self_index=self.embed_index if self.concat else None)
             ds = self.d0 if self.concat else 0
             k = self.embed.shape[0]
-            ws = self._scratch("mean1_bwd", ops.csr_mean_backward_grouped_workspace_bytes(self.n, k, self.grouped_t.col.numel(), self.d0))
+            ws = self.scratch.get("mean1_bwd", ops.csr_mean_backward_grouped_workspace_bytes(self.n, k, self.grouped_t.col.numel(), self.d0))
             g_embed = ops.csr_mean_backward_grouped(self.rowptr, self.col, self.grouped_t, g_x1[:, ds:], workspace=ws)
             if self.concat:
                 rowptr_g, col_g = self.groups
-                ws = self._scratch("embed_sum", ops.csr_sum_workspace_bytes(k, self.n, self.d0))
+                ws = self.scratch.get("embed_sum", ops.csr_sum_workspace_bytes(k, self.n, self.d0))
                 g_embed += ops.csr_sum(rowptr_g, col_g, g_x1[:, :ds], workspace=ws)
             return loss, (g_w1, g_w2, g_cls, g_embed)
         # layer 1 with its input's gradient: dW1 and d[X_self | agg1]; the mean's adjoint on the inner graph gives dX
-        g_w1, g_x1 = self._linear_backward(self.x if self.concat else None, self.agg1, self.w1, self.act1, self.h1_out, g_h1, True,
-                                           "linear_act_backward (layer 1)")
+        g_w1, g_x1 = ops.linear_act_backward(self.agg1, self.w1, self.act1, self.h1_out, g_h1, self_tab=self.x if self.concat else None,
+                                             workspace=dw)
         ds = self.d0 if self.concat else 0
-        ws = self._scratch("mean1_bwd", ops.csr_mean_backward_workspace_bytes(self.n, self.n, self.col_t.numel(), self.d0))
+        ws = self.scratch.get("mean1_bwd", ops.csr_mean_backward_workspace_bytes(self.n, self.n, self.col_t.numel(), self.d0))
         g_x = ops.csr_mean_backward(self.rowptr, self.col, self.rowptr_t, self.col_t, g_x1[:, ds:], self_loop=self.self_loop, workspace=ws)
         if self.concat:
             g_x += g_x1[:, :ds]                                              # the concat encoder's own-row part
@@ -235,7 +185,7 @@ class FullGraphTrainer:
             return loss, (g_w1, g_w2, g_cls, g_x)
         # every embedding row collects the rows of the nodes that read it, in ascending node order
         rowptr_g, col_g = self.groups
-        ws = self._scratch("embed_sum", ops.csr_sum_workspace_bytes(rowptr_g.shape[0] - 1, self.n, self.d0))
+        ws = self.scratch.get("embed_sum", ops.csr_sum_workspace_bytes(rowptr_g.shape[0] - 1, self.n, self.d0))
         return loss, (g_w1, g_w2, g_cls, ops.csr_sum(rowptr_g, col_g, g_x, workspace=ws))
 
     def step(self, train_ids, labels):
@@ -250,9 +200,7 @@ class FullGraphTrainer:
         emb = self.forward()
         if ids is not None:
             emb = emb.index_select(0, ids.long())
-        if self.head != "native":
-            return (emb @ self.w_cls.t()).argmax(1).to(torch.int32)
-        return ops.xent_head(emb, self.w_cls, grads=False, pred=True)["pred"]
+        return head_predict(emb, self.w_cls, self.head)
 
 
 def one_hot_index(n, device="cuda"):
@@ -267,9 +215,24 @@ def degree_index(rowptr):
     return deg.contiguous(), (int(deg.max()) + 1 if deg.numel() else 1)
 
 
+def embed_arguments(who, initializer, frozen, graph, embed_dim, dev):
+    """What a run driver `who` hands its trainer for --initializer (model.py:153-157, 209-212): None for a spelling in `frozen` (the
+    frozen feature table), else dict(embed_index, embed_rows, embed_dim, act1) -- "1hot": a row per node, ReLU; "node_degree": a row
+    per degree, SIGMOID at layer 1 (encoders.py:58-59).  Anything else is refused, before the graph is read."""
+    if initializer not in (*frozen, "1hot", "node_degree"):
+        raise SageError(f"{who}: initializer = {initializer!r}, expected {frozen[0]!r}, '1hot' or 'node_degree'")
+    if initializer in frozen:
+        return None
+    if initializer == "1hot":
+        index, rows = one_hot_index(graph.num_nodes, dev)
+    else:
+        index, rows = degree_index(torch.from_numpy(graph.rowptr))
+    return dict(embed_index=index.to(dev), embed_rows=rows, embed_dim=embed_dim, act1=ACT_SIGMOID if initializer == "node_degree" else ACT_RELU)
+
+
 def run_full_graph_training(graph, feat_data, labels, num_classes, seed=1, steps=100, lr=0.7, hidden1=50, hidden2=128, gcn=True,
                             agg_self_loop=False, head="native", initializer="None", embed_dim=100, fused_embed=False):
-    """run_model (model.py:184-259) with full neighbourhoods: the same 10 / 10 / 80 split of np.random.permutation
+    """run_model (model.py:184-259) with full neighbourhoods: the same 10 / 10 / 80 split of a seeded numpy permutation
     (model.py:229-235), ONE step per epoch over the whole training set, `steps` epochs.
     initializer: "None" -- the frozen table feat_data, ReLU at both layers; "1hot" -- a trainable embedding row per node, ReLU;
     "node_degree" -- a trainable embedding row per degree, SIGMOID at layer 1 (encoders.py:58).  feat_data is not read for the
@@ -278,24 +241,13 @@ def run_full_graph_training(graph, feat_data, labels, num_classes, seed=1, steps
     because its loader hands the one-hot in as the feature table: an accident of the loader, not copied here.
     fused_embed: FullGraphTrainer's flag (it changes something for "node_degree" only: the 1hot index is the identity).
     -> dict(f1_micro, f1_macro, mean_step_time, losses, trainer), as train.run_engine_training."""
-    from sklearn.metrics import f1_score
-    if initializer not in ("None", "1hot", "node_degree"):
-        raise SageError(f"run_full_graph_training: initializer = {initializer!r}, expected 'None', '1hot' or 'node_degree'")
     dev = torch.device("cuda")
-    np.random.seed(seed)
+    embed = embed_arguments("run_full_graph_training", initializer, ("None",), graph, embed_dim, dev)
     rowptr, col = graph.to(dev)
-    n = graph.num_nodes
-    rand_indices = np.random.permutation(n)
-    val = rand_indices[int(0.1 * n):int(0.2 * n)]
-    train = rand_indices[int(0.2 * n):]
-    if initializer == "None":
-        table = torch.as_tensor(feat_data, dtype=torch.float32).to(dev)
-        tr = FullGraphTrainer(rowptr, col, table, num_classes, hidden1, hidden2, gcn=gcn, lr=lr, agg_self_loop=agg_self_loop, head=head)
-    else:
-        index, k = one_hot_index(n, dev) if initializer == "1hot" else degree_index(rowptr)
-        tr = FullGraphTrainer(rowptr, col, None, num_classes, hidden1, hidden2, gcn=gcn, lr=lr, agg_self_loop=agg_self_loop, head=head,
-                              embed_index=index, embed_rows=k, embed_dim=embed_dim,
-                              act1=ACT_SIGMOID if initializer == "node_degree" else ACT_RELU, fused_embed=fused_embed)
+    _, val, train = _split(graph.num_nodes, seed)
+    table = torch.as_tensor(feat_data, dtype=torch.float32).to(dev) if embed is None else None
+    tr = FullGraphTrainer(rowptr, col, table, num_classes, hidden1, hidden2, gcn=gcn, lr=lr, agg_self_loop=agg_self_loop, head=head,
+                          fused_embed=fused_embed, **(embed or {}))
     labels_dev = torch.as_tensor(np.asarray(labels).reshape(-1), dtype=torch.int64).to(dev)
     ids = torch.as_tensor(train.astype(np.int32)).to(dev)
     tgt = labels_dev[ids.long()]
@@ -306,7 +258,5 @@ def run_full_graph_training(graph, feat_data, labels, num_classes, seed=1, steps
         losses.append(tr.step(ids, tgt))
     torch.cuda.synchronize()
     elapsed = time.time() - t0
-    pred = tr.predict(torch.as_tensor(val.astype(np.int32)).to(dev)).cpu().numpy()
-    truth = np.asarray(labels)[val].reshape(-1)
-    return {"f1_micro": float(f1_score(truth, pred, average="micro")), "f1_macro": float(f1_score(truth, pred, average="macro")),
-            "mean_step_time": elapsed / max(int(steps), 1), "losses": [float(x) for x in losses], "trainer": tr}
+    pred = tr.predict(torch.as_tensor(val.astype(np.int32)).to(dev))
+    return _validation_result(labels, val, pred, elapsed, int(steps), losses, tr)

@@ -115,6 +115,28 @@ def _row_edges(rowptr, ids, live=None):
     return deg.sum()
 
 
+def _seed_frontier(rowptr, rp2, c2, seeds, fr, what):
+    """The frontier F of a seed batch into the cleared ops.CsrFrontier `fr`: the distinct ids among `seeds` (int32 on the device, at
+    least one) and all their neighbours in the outer CSR (rp2, c2) -> (e2, size, e1): the seeds' outer edges, |F|, and the edges of
+    F's rows in the inner CSR `rowptr`.  The caller clears fr afterwards, also when this raises (`what` names it in the messages).
+    Two host reads."""
+    n, m = rowptr.shape[0] - 1, seeds.shape[0]
+    # host read 1: the seeds' outer edges, and their range (device-resident seeds were never checked; sage_linear_act does not clamp)
+    e2, lo, hi = torch.stack([_row_edges(rp2, seeds), seeds.min().long(), seeds.max().long()]).tolist()
+    if lo < 0 or hi >= n:
+        raise SageError(f"{what}: seed id {lo if lo < 0 else hi} outside [0, {n})")
+    bound = min(n, m + e2)                                # |F| of a frontier that was empty on entry
+    fr.reserve(bound)
+    ops.csr_frontier(rp2, c2, seeds, fr, max_edges=e2)
+    # host read 2: |F| and the inner edges of F's rows
+    size, e1 = torch.stack([fr.count[0].long(), _row_edges(rowptr, fr.nodes[:bound], live=fr.count[0])]).tolist()
+    if size > bound:
+        if size > fr.max_nodes:                           # overflow: `nodes` no longer names every row of the map
+            fr.refill()
+        raise SageError(f"{what}: the frontier holds {size} ids, {bound} at most are the seeds': it was not cleared before the call")
+    return e2, size, e1
+
+
 def _layer_rows(rowptr, col, table, weight, concat, self_loop, act, flag, ids, index, self_rows, out, rows, block, workspace, max_edges):
     """layer_all_nodes' block loop for the rows `ids` instead of all of them: out[r] = the layer's output for node ids[r].
     self_rows: the concat encoder's own rows of `table`, one per id."""
@@ -172,21 +194,9 @@ def embed_nodes(rowptr, col, table, w1, w2, seeds, concat=False, agg_self_loop=F
         raise SageError(f"embed_nodes: out is {tuple(out.shape)}, expected {(m, h2)}")
     if m == 0:
         return out
-    # host read 1: the seeds' outer edges, and their range (device-resident seeds were not checked above; sage_linear_act does not clamp)
-    e2, lo, hi = torch.stack([_row_edges(rp2, seeds), seeds.min().long(), seeds.max().long()]).tolist()
-    if lo < 0 or hi >= n:
-        raise SageError(f"embed_nodes: seed id {lo if lo < 0 else hi} outside [0, {n})")
     fr = ops.CsrFrontier(n, dev, max_nodes=0) if frontier is None else frontier
-    bound = min(n, m + e2)                                # |F| of a frontier that was empty on entry
-    fr.reserve(bound)
     try:
-        ops.csr_frontier(rp2, c2, seeds, fr, max_edges=e2)
-        # host read 2: |F| and the inner edges of F's rows
-        size, e1 = torch.stack([fr.count[0].long(), _row_edges(rowptr, fr.nodes[:bound], live=fr.count[0])]).tolist()
-        if size > bound:
-            if size > fr.max_nodes:                       # overflow: `nodes` no longer names every row of the map
-                fr.refill()
-            raise SageError(f"embed_nodes: the frontier holds {size} ids, {bound} at most are the seeds': it was not cleared before the call")
+        e2, size, e1 = _seed_frontier(rowptr, rp2, c2, seeds, fr, "embed_nodes")
         f_nodes = fr.nodes[:size]
         rows = max(1, min(int(rows_per_call), max(size, m)))
         block = torch.empty(rows * max(d0, h1), dtype=torch.float32, device=dev)

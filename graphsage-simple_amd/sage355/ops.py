@@ -195,6 +195,50 @@ def linear_act(agg, weight, act=ACT_RELU, self_tab=None, self_index=None, n_dev=
     return out
 
 
+def linear_act_backward_workspace_bytes(n, dim, has_self, out_dim):
+    """Bytes of the workspace sage_linear_act_backward_ws needs for its weight gradient (host arithmetic)."""
+    return int(native.lib().sage_linear_act_backward_workspace_bytes(int(n), int(dim), int(bool(has_self)), int(out_dim)))
+
+
+def linear_act_backward(agg, weight, act, out, grad_out, self_tab=None, self_index=None, n_dev=None, need_w=True, need_x=True,
+                        workspace=None):
+    """The backward of linear_act over its n rows (the first n_dev[0] of them when given) -> (grad_w, grad_x), either None when not
+    asked for.  out is what the forward returned, grad_out = d loss / d out; grad_w has weight's shape, grad_x [n, kw] is
+    d loss / d [self | agg].  The reproducible entry point (sage_linear_act_backward_ws): the partial tiles of grad_w go through a
+    workspace and are added in a fixed order, no float atomics.  workspace: a uint8 device tensor to use when it is large enough."""
+    _need_gpu()
+    n, dim = agg.shape
+    out_dim, kw = weight.shape
+    grad_w = torch.zeros_like(weight) if need_w else None
+    grad_x = torch.empty((n, kw), dtype=torch.float32, device=agg.device) if need_x else None
+    ws = None
+    if need_w:
+        need = max(256, linear_act_backward_workspace_bytes(n, dim, self_tab is not None, out_dim))
+        ws = workspace if workspace is not None and workspace.numel() >= need else torch.empty(need, dtype=torch.uint8, device=agg.device)
+    P = native.ptr
+    rc = native.lib().sage_linear_act_backward_ws(
+        P(self_tab), self_tab.stride(0) if self_tab is not None else 0, P(self_index), P(agg), agg.stride(0), dim,
+        P(weight), weight.stride(0), out_dim, int(act), P(out), out.stride(0), P(grad_out), grad_out.stride(0), n, P(n_dev),
+        P(grad_w), grad_w.stride(0) if need_w else 0, P(grad_x), kw if need_x else 0, None,
+        P(ws), ws.numel() if need_w else 0, native.stream_handle())
+    native.check(rc, "linear_act_backward")
+    return grad_w, grad_x
+
+
+class Scratch:
+    """Named uint8 buffers of one device that only ever grow: get(name, nbytes) -> a buffer of at least nbytes (256 at the least),
+    the same one as long as it is large enough."""
+
+    def __init__(self, device):
+        self.device, self._buffers = device, {}
+
+    def get(self, name, nbytes):
+        t = self._buffers.get(name)
+        if t is None or t.numel() < nbytes:
+            t = self._buffers[name] = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=self.device)
+        return t
+
+
 def layer_forward_supported(dim, out_dim, concat):
     return bool(native.lib().sage_layer_forward_supported(int(dim), int(out_dim), 1 if concat else 0))
 

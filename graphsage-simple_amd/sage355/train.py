@@ -2,7 +2,7 @@
 (SupervisedGraphSage) and model.py:184-259 (run_model) -- SURVEY.md section 8 row f-1.
 
 Kept from the reference: the classifier (weight [C, embed_dim], xavier, scores = (W . embeds)^T,
-CrossEntropyLoss), the 10 / 10 / 80 test / val / train split of np.random.permutation
+CrossEntropyLoss), the 10 / 10 / 80 test / val / train split of a seeded numpy permutation
 (model.py:229-234), SGD lr = 0.7 (model.py:237), random.shuffle of the train list per epoch,
 micro/macro F1 on the validation split (model.py:256-258), mean batch time (model.py:259).
 Single process: the per-epoch shuffle is `random.shuffle(train)` on Python's GLOBAL stream, the one the strict
@@ -28,6 +28,7 @@ from torch.nn import init
 from . import dist
 from .aggregators import MeanAggregator
 from .encoders import Encoder
+from .head import _sum_over_batch, head_grads, head_predict  # noqa: F401  (_sum_over_batch: its old home, still imported from here)
 from .native import ACT_RELU, ACT_SIGMOID
 
 
@@ -72,8 +73,6 @@ def run_training(feat_data, labels, adj_lists, num_classes, seed=1, epochs=1, ba
     `seed` seeds numpy (the split) and Python's random (shuffles + neighbour sampling) as model.py:192-193
     does; `sample_seed` reseeds only Python's random, to vary the sampling stream on a fixed split.  With
     world_size > 1 the shuffles come from a private `random.Random(seed)` instead (module docstring)."""
-    from sklearn.metrics import f1_score
-    np.random.seed(seed)
     random.seed(seed if sample_seed is None else sample_seed)
     rank, world = (torch.distributed.get_rank(), dist.world_size()) if dist.world_size() > 1 else (0, 1)
     num_nodes = feat_data.shape[0]
@@ -81,10 +80,8 @@ def run_training(feat_data, labels, adj_lists, num_classes, seed=1, epochs=1, ba
         model = build_model(feat_data, adj_lists, num_classes, **model_kwargs)
     params = [p for p in model.parameters() if p.requires_grad]
     dist.broadcast_params(params)
-    rand_indices = np.random.permutation(num_nodes)
-    test = rand_indices[:int(0.1 * num_nodes)]
-    val = rand_indices[int(0.1 * num_nodes):int(0.2 * num_nodes)]
-    train = list(rand_indices[int(0.2 * num_nodes):])
+    test, val, train = _split(num_nodes, seed)
+    train = list(train)
     optimizer = torch.optim.SGD(params, lr=lr)
     # world 1: the global stream, as model.py:243; world > 1: a generator identical on every rank, untouched by neighbour sampling
     shuffler = random if world == 1 else random.Random(seed)
@@ -114,9 +111,8 @@ def run_training(feat_data, labels, adj_lists, num_classes, seed=1, epochs=1, ba
             times.append(time.time() - start)
     with torch.no_grad():
         val_output = model(val)
-    pred = val_output.detach().cpu().numpy().argmax(axis=1)
-    truth = np.asarray(labels)[val].reshape(-1)
-    res = {"f1_micro": float(f1_score(truth, pred, average="micro")), "f1_macro": float(f1_score(truth, pred, average="macro")),
+    micro, macro = _f1(labels, val, val_output.detach().cpu().numpy().argmax(axis=1))
+    res = {"f1_micro": micro, "f1_macro": macro,
            "mean_batch_time": float(np.mean(times)) if times else 0.0, "losses": losses, "test_nodes": test}
     if return_model:
         res["model"] = model
@@ -127,18 +123,85 @@ def run_training(feat_data, labels, adj_lists, num_classes, seed=1, epochs=1, ba
     return res
 
 
-def _sum_over_batch(g_scores, emb, piece=256):
-    """g_scores^T . emb = [C, B] x [B, H] with the reduction over B in a FIXED order: 256-row pieces as one batched product, their
-    sum over the piece index by torch.sum (one thread per output element adds them in index order), a ragged tail last."""
-    b = g_scores.shape[0]
-    whole = (b // piece) * piece
-    if whole <= piece:
-        return g_scores.t() @ emb
-    n = whole // piece
-    acc = torch.bmm(g_scores[:whole].view(n, piece, -1).transpose(1, 2), emb[:whole].view(n, piece, -1)).sum(0)
-    if whole < b:
-        acc = acc + g_scores[whole:].t() @ emb[whole:]
-    return acc
+def _split(n, seed):
+    """(test, val, train): numpy's global generator seeded with `seed`, the 10 / 10 / 80 split of its permutation of n (model.py:192, 229-234)."""
+    np.random.seed(seed)
+    rand_indices = np.random.permutation(n)
+    return rand_indices[:int(0.1 * n)], rand_indices[int(0.1 * n):int(0.2 * n)], rand_indices[int(0.2 * n):]
+
+
+def _f1(labels, val, pred):
+    """(micro, macro) F1 of the predictions `pred` for the nodes `val` (model.py:256-258)."""
+    from sklearn.metrics import f1_score
+    truth = np.asarray(labels)[val].reshape(-1)
+    return float(f1_score(truth, pred, average="micro")), float(f1_score(truth, pred, average="macro"))
+
+
+def _batches(train, shuffler, epochs, batch_size, ref_batching, dev):
+    """The mini-batches of `epochs` epochs as contiguous int32 device tensors of node ids: `train` (a list, shuffled in place by
+    shuffler.shuffle at the start of every epoch and uploaded once per epoch) in batch_size slices, or with ref_batching in the
+    reference's descending `train[batch:max(train_num, batch + batch_size)]` (module docstring)."""
+    for _ in range(epochs):
+        shuffler.shuffle(train)
+        order = torch.as_tensor(np.asarray(train), dtype=torch.int32).to(dev)
+        for lo in range(0, len(train), batch_size):
+            hi = max(len(train), lo + batch_size) if ref_batching else min(len(train), lo + batch_size)
+            yield order[lo:hi].contiguous()
+
+
+def _validation_result(labels, val, pred, elapsed, steps, losses, trainer):
+    """What the run drivers of the three trainers return: dict(f1_micro, f1_macro, mean_step_time, losses, trainer); pred: the
+    trainer's classes of the validation nodes `val`, on the device."""
+    micro, macro = _f1(labels, val, pred.cpu().numpy())
+    return {"f1_micro": micro, "f1_macro": macro, "mean_step_time": elapsed / max(steps, 1), "losses": [float(x) for x in losses],
+            "trainer": trainer}
+
+
+def check_trainer_args(who, head, act1, hidden2, num_classes, table=None, embed_index=None, embed_rows=None, embed_dim=None):
+    """The refusals the three trainers share, in the name of the class `who`: the head, layer 1's activation, a table AND an index, an
+    index without the embedding's shape, a native head without a kernel for the shape.  A trainer passes what it has."""
+    from . import native, ops
+    if head not in ("torch", "native"):
+        raise native.SageError(f"{who}: head = {head!r}, expected 'torch' or 'native'")
+    if act1 not in (ACT_RELU, ACT_SIGMOID):
+        raise native.SageError(f"{who}: act1 = {act1!r}, expected ACT_RELU or ACT_SIGMOID")
+    if embed_index is not None and table is not None:
+        raise native.SageError(f"{who}: table and embed_index are alternatives: layer 1 reads one of them")
+    if embed_index is not None and (embed_rows is None or embed_dim is None or int(embed_rows) < 1 or int(embed_dim) < 1):
+        raise native.SageError(f"{who}: embed_rows = {embed_rows!r}, embed_dim = {embed_dim!r}")
+    if head == "native" and not ops.xent_head_supported(hidden2, num_classes):
+        raise native.SageError(f"{who}: head='native' has no kernel for hidden2 = {hidden2}, num_classes = {num_classes}")
+
+
+def init_parameters(dev, d0, hidden1, hidden2, num_classes, gcn, embed_rows=None):
+    """(w1, w2, w_cls, embed | None) on `dev`, drawn in this order from torch's generator -- one torch seed gives every trainer the same
+    start: the three weights xavier_uniform_ (encoders.py:36-38, model.py:61-62), then, with embed_rows, the embedding
+    [embed_rows, d0] N(0, 1) as nn.Embedding's weight is (aggregators.py:31) -- AFTER the three weights, which therefore start as a
+    frozen-table trainer's do.  The caller broadcasts them (dist.broadcast_params)."""
+    m = 1 if gcn else 2
+    w1 = torch.empty(hidden1, m * d0, device=dev)
+    w2 = torch.empty(hidden2, m * hidden1, device=dev)
+    w_cls = torch.empty(num_classes, hidden2, device=dev)
+    for w in (w1, w2, w_cls):
+        init.xavier_uniform_(w)
+    embed = None
+    if embed_rows is not None:
+        embed = torch.empty(int(embed_rows), d0, device=dev)
+        init.normal_(embed)
+    return w1, w2, w_cls, embed
+
+
+def csr_pair(rowptr, col, rowptr_outer=None, col_outer=None):
+    """The layer-1 CSR checked and the layer-2 CSR (default: the same) -> (rowptr_outer, col_outer), as FullGraphTrainer and
+    ExactBatchTrainer take them."""
+    from . import native, ops
+    ops._chk(rowptr, torch.int64, "rowptr", 1)
+    ops._chk(col, torch.int32, "col", 1)
+    rowptr2 = rowptr if rowptr_outer is None else ops._chk(rowptr_outer, torch.int64, "rowptr_outer", 1)
+    col2 = col if col_outer is None else ops._chk(col_outer, torch.int32, "col_outer", 1)
+    if rowptr2.shape[0] != rowptr.shape[0]:
+        raise native.SageError("inner and outer CSR must cover the same node ids")
+    return rowptr2, col2
 
 
 class EngineTrainer:
@@ -178,35 +241,17 @@ class EngineTrainer:
         w_cls trajectories); "native" -- one sage_xent_head call, its sums in an order fixed by the shape.  With the
         native head the loss and the classifier gradient that grads() returns live in buffers of the trainer, rewritten by its next call."""
         from . import native, ops
-        if head not in ("torch", "native"):
-            raise native.SageError(f"EngineTrainer: head = {head!r}, expected 'torch' or 'native'")
-        if act1 not in (ACT_RELU, ACT_SIGMOID):
-            raise native.SageError(f"EngineTrainer: act1 = {act1!r}, expected ACT_RELU or ACT_SIGMOID")
-        if embed_index is not None and table is not None:
-            raise native.SageError("EngineTrainer: table and embed_index are alternatives: layer 1 reads one of them")
+        check_trainer_args("EngineTrainer", head, act1, hidden2, num_classes, table, embed_index, embed_rows, embed_dim)
         if sparse_embed and embed_index is None:
             raise native.SageError("EngineTrainer: sparse_embed needs embed_index: a frozen table has no update to make sparse")
-        if embed_index is not None:
-            if embed_rows is None or embed_dim is None or int(embed_rows) < 1 or int(embed_dim) < 1:
-                raise native.SageError(f"EngineTrainer: embed_rows = {embed_rows!r}, embed_dim = {embed_dim!r}")
-            if dist.world_size() > 1:
-                raise native.SageError("EngineTrainer: a trainable embedding is single-process in this build (its gradient is not all-reduced)")
-        if head == "native" and not ops.xent_head_supported(hidden2, num_classes):
-            raise native.SageError(f"EngineTrainer: head='native' has no kernel for hidden2 = {hidden2}, num_classes = {num_classes}")
+        if embed_index is not None and dist.world_size() > 1:
+            raise native.SageError("EngineTrainer: a trainable embedding is single-process in this build (its gradient is not all-reduced)")
         self.head = head
         from .engine import TwoHopEngine
         dev = table.device if embed_index is None else embed_index.device
         d0 = table.shape[1] if embed_index is None else int(embed_dim)
-        m = 1 if gcn else 2
-        self.w1 = torch.empty(hidden1, m * d0, device=dev)
-        self.w2 = torch.empty(hidden2, m * hidden1, device=dev)
-        self.w_cls = torch.empty(num_classes, hidden2, device=dev)
-        for w in (self.w1, self.w2, self.w_cls):
-            init.xavier_uniform_(w)
-        self.embed_weight = None
-        if embed_index is not None:          # after the three weights: they start as the frozen trainer's do for the same torch seed
-            self.embed_weight = torch.empty(int(embed_rows), d0, device=dev)
-            init.normal_(self.embed_weight)
+        self.w1, self.w2, self.w_cls, self.embed_weight = init_parameters(dev, d0, hidden1, hidden2, num_classes, gcn,
+                                                                          None if embed_index is None else embed_rows)
         self.lr = float(lr)
         self.sparse_embed = bool(sparse_embed)
         self.concat = not gcn
@@ -254,20 +299,17 @@ class EngineTrainer:
         return self.embed(seeds, key) @ self.w_cls.t()
 
     def predict(self, seeds, key=0):
-        """int32 [B]: the class of the highest score (model.py:256, `val_output.data.numpy().argmax(axis=1)`).  The native head computes
-        it from the embeddings in one launch (the inference form of sage_xent_head); the torch head takes scores().argmax(1)."""
-        if self.head != "native":
-            return self.scores(seeds, key).argmax(1).to(torch.int32)
+        """int32 [B]: the class of the highest score of one sampled forward (head.head_predict: model.py:256)."""
         return self._predict_of(self.embed(seeds, key))
 
     def _predict_of(self, emb):
-        """predict()'s rule on given embeddings."""
+        """predict()'s rule on given embeddings; the native head works in the trainer's reserved buffers."""
         if self.head != "native":
-            return (emb @ self.w_cls.t()).argmax(1).to(torch.int32)
+            return head_predict(emb, self.w_cls, self.head)
         if emb.shape[0] > self._head["rows"]:
             self._head_reserve(emb.shape[0])
         hd = self._head
-        return self._ops.xent_head(emb, self.w_cls, grads=False, pred=True, workspace=hd["workspace"], out={"pred": hd["pred"]})["pred"].clone()
+        return head_predict(emb, self.w_cls, self.head, workspace=hd["workspace"], out={"pred": hd["pred"]}).clone()
 
     def embed_exact(self, seeds):
         """[B, hidden2] embeddings over the FULL neighbourhoods at both hops (aggregators.py:47-48, num_sample=None): no sampler key, the
@@ -303,36 +345,20 @@ class EngineTrainer:
         else:
             b = seeds.shape[0]
             out = e.forward(seeds, seed=key)                               # sample, frontier, sample, layer 1, layer 2
-        if self.head == "native":
-            # classifier + loss + their gradients in one call (model.py:59-69): no autograd, and the sum over the batch runs in 64-row
-            # ranges added in range order, so w_cls keeps its run-to-run bit identity at any batch size
+        hd = {}
+        if self.head == "native":                                          # the head works in the trainer's buffers: no allocation in a step
             if b > self._head["rows"]:
                 self._head_reserve(b)                                      # never while capturing: capture_step's batch is <= max_batch
-            hd = self._head
-            r = self._ops.xent_head(out, self.w_cls, labels, scale=1.0 / float(b if global_batch is None else global_batch),
-                                    workspace=hd["workspace"], out=hd)
-            g_w1, g_w2, *g_e = self._backward(out, r["grad_emb"], _embed_lr)
-            # eager: the caller may keep the loss of every step (run_engine_training does); queued: the captured step copies it at once
-            loss = r["loss"][0]
-            return (loss if seeds is None else loss.clone()), (g_w1, g_w2, r["grad_w"], *g_e)
-        # classifier + loss + their gradients: stock torch on the same stream (model.py:59-69)
-        # The classifier's weight gradient is a [C, B] x [B, H2] product whose reduction runs over the BATCH: for B >= 1024 the BLAS behind
-        # torch.mm may split it and add the pieces with atomics, and two runs of one schedule then differ in the last bits of w_cls (seen
-        # once in four runs of the GPU suite, 1024-seed case only).  So autograd stops at the scores and the two small products are
-        # spelled out; the one over the batch is cut into 256-row pieces (one batched product) that are added in a fixed order.
-        # (Accumulating it in fp64 instead costs 0.2 ms per step: 0.31 -> 0.53 ms captured at config-3 size.)
-        emb = out.detach()
-        scores = (emb @ self.w_cls.detach().t()).requires_grad_(True)
-        if global_batch is None:
-            loss = nn.functional.cross_entropy(scores, labels)
-        else:
-            loss = nn.functional.cross_entropy(scores, labels, reduction="sum") / float(global_batch)
-        (g_scores,) = torch.autograd.grad(loss, (scores,))
-        g_out = g_scores @ self.w_cls.detach()                              # [B, C] x [C, H2]: reduction over the classes
-        g_cls = _sum_over_batch(g_scores, emb)                               # [C, B] x [B, H2]: reduction over the batch
+            hd = dict(workspace=self._head["workspace"], out=self._head)
+        # classifier + loss + their gradients on the same stream (model.py:59-69)
+        loss, g_out, g_cls = head_grads(out, self.w_cls, labels, self.head, b, global_batch, **hd)
         # both layers' weight gradients from the intermediates this forward left in the engine's workspace
         g_w1, g_w2, *g_e = self._backward(out, g_out, _embed_lr)
-        return loss.detach(), (g_w1, g_w2, g_cls, *g_e)
+        if self.head == "native" and seeds is not None:
+            # the loss lives in the trainer's buffer.  Eager: the caller may keep the loss of every step (run_engine_training does);
+            # queued: the captured step copies it at once
+            loss = loss.clone()
+        return loss, (g_w1, g_w2, g_cls, *g_e)
 
     def step(self, seeds, labels, key, global_batch=None):
         """forward + backward + SGD; -> loss as a device scalar (reading it is the caller's only synchronisation).
@@ -414,51 +440,26 @@ def run_engine_training(graph, feat_data, labels, num_classes, seed=1, epochs=1,
     the embedding's width (the reference's --feature_dim default), a multiple of 4.  sparse_embed: EngineTrainer's (an initializer
     only): update the touched embedding rows alone.  exact_eval: the validation predictions come from predict_exact (full
     neighbourhoods, no sampler key) instead of one sampled forward; training is the same either way."""
-    from sklearn.metrics import f1_score
-    from . import native
-    from .fullgraph import degree_index, one_hot_index
-    if initializer not in (None, "None", "1hot", "node_degree"):
-        raise native.SageError(f"run_engine_training: initializer = {initializer!r}, expected None, '1hot' or 'node_degree'")
+    from .fullgraph import embed_arguments
     dev = torch.device("cuda")
-    np.random.seed(seed)
+    embed = embed_arguments("run_engine_training", initializer, (None, "None"), graph, embed_dim, dev)
     rowptr, col = graph.to(dev)
-    n = graph.num_nodes
-    if initializer in (None, "None"):
-        table, embed_kwargs = torch.as_tensor(feat_data, dtype=torch.float32).to(dev), dict(sparse_embed=sparse_embed)
-    else:
-        index, rows = one_hot_index(n, dev) if initializer == "1hot" else degree_index(rowptr)
-        table = None
-        embed_kwargs = dict(embed_index=index, embed_rows=rows, embed_dim=embed_dim,
-                            act1=ACT_SIGMOID if initializer == "node_degree" else ACT_RELU, sparse_embed=sparse_embed)
-    rand_indices = np.random.permutation(n)
-    val = rand_indices[int(0.1 * n):int(0.2 * n)]
-    train = list(rand_indices[int(0.2 * n):])
+    table = torch.as_tensor(feat_data, dtype=torch.float32).to(dev) if embed is None else None
+    _, val, train = _split(graph.num_nodes, seed)
+    train = list(train)
     top = len(train) if ref_batching else batch_size
     tr = EngineTrainer(rowptr, col, table, num_classes, hidden1, hidden2, num_sample1, num_sample2, gcn=gcn, lr=lr, max_batch=max(top, len(val)),
-                       head=head, **embed_kwargs)
+                       head=head, sparse_embed=sparse_embed, **(embed or {}))
     labels_dev = torch.as_tensor(np.asarray(labels).reshape(-1), dtype=torch.int64).to(dev)
-    shuffler = random.Random(seed)
     losses, key = [], int(sample_seed) << 20
     torch.cuda.synchronize()
     t0 = time.time()
-    steps = 0
-    for _ in range(epochs):
-        shuffler.shuffle(train)
-        order = torch.as_tensor(np.asarray(train), dtype=torch.int32).to(dev)
-        for lo in range(0, len(train), batch_size):
-            hi = max(len(train), lo + batch_size) if ref_batching else min(len(train), lo + batch_size)
-            ids = order[lo:hi].contiguous()
-            losses.append(tr.step(ids, labels_dev[ids.long()], key))
-            key += 1
-            steps += 1
+    for ids in _batches(train, random.Random(seed), epochs, batch_size, ref_batching, dev):
+        losses.append(tr.step(ids, labels_dev[ids.long()], key))
+        key += 1
     torch.cuda.synchronize()
     elapsed = time.time() - t0
     with torch.no_grad():
         val_ids = torch.as_tensor(val.astype(np.int32)).to(dev)
-        if exact_eval:
-            pred = tr.predict_exact(val_ids).cpu().numpy()
-        else:
-            pred = (tr.predict(val_ids, key=key) if head == "native" else tr.scores(val_ids, key=key).argmax(1)).cpu().numpy()
-    truth = np.asarray(labels)[val].reshape(-1)
-    return {"f1_micro": float(f1_score(truth, pred, average="micro")), "f1_macro": float(f1_score(truth, pred, average="macro")),
-            "mean_step_time": elapsed / max(steps, 1), "losses": [float(x) for x in losses], "trainer": tr}
+        pred = tr.predict_exact(val_ids) if exact_eval else tr.predict(val_ids, key=key)
+    return _validation_result(labels, val, pred, elapsed, len(losses), losses, tr)
