@@ -291,6 +291,7 @@ struct ChunkWs {
 
 // Item entries a workspace sized for max_edges holds: the chunks of all long rows are at most floor(E_sel / E) + (number of long
 // rows), and a long row has more than E edges.  false: more than an int32 item index reaches.  rows, max_edges >= 0.
+// tests/test_gpu_csr_plan.py reads the first two pieces back, in this order: off[rows], then carry[nblocks + 1] (sage_csr_mean's workspace).
 inline bool chunk_ws(int64_t rows, int64_t max_edges, int32_t dim, WsCursor& cur, ChunkWs* C) {
     C->cap = max_edges / kChunk + std::min<int64_t>(rows, max_edges / (kChunk + 1));
     if (C->cap >= (1ll << 31)) return false;

@@ -607,3 +607,281 @@ def linear_bar(c, nn=None):
         smallest = np.minimum(smallest, ax[:, k, None] * aw[None, :, k])
     share = float((smallest / (2.0 ** -23 * (ax @ aw.T))).min())
     return 2.0 * max(figs.values()), figs, share
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# The CSR chunk planner (csrc/sage_csr_common.h: csr_count_kernel -> csr_carry_kernel -> csr_expand_kernel, then chunk_item and
+# chunked_row_sum): cases whose long rows sit where the count scan changes thread, wave, block and carry pass, a numpy emulation of the
+# three launches (faithful and deliberately broken), fp64 references with derived per-element bars, and an fp32 emulation of what a
+# row comes out as under a given plan -- shared by tests/test_gpu_csr_plan.py (the kernels) and tests/test_csr_plan_host.py (the
+# emulations on the very same data).
+# The geometry, as sage_csr_common.h has it (kCountIpt, kWave, kCountThreads, kCountTile, kCarryThreads, kChunk):
+PLAN_IPT, PLAN_WAVE, PLAN_THREADS = 8, 64, 256
+PLAN_TILE = PLAN_IPT * PLAN_THREADS                    # 2048 rows per count block
+PLAN_CARRY = 1024                                      # block sums per pass of the carry kernel
+PLAN_CHUNK = 512
+PLAN_DEGREES = (513, 1024, 1025, 1537)                 # 2, 2, 3, 4 chunks: the offsets are a multiple of nothing
+PLAN_N_SMALL = 3 * PLAN_TILE + 5
+# last row of thread 0 | first of thread 1; wave 0 | 1; into wave 3; block 0 | 1; block 1 | 2; the last row, in a block that is not full
+PLAN_LONG_SMALL = (7, 8, 511, 512, 1535, 1536, 2047, 2048, 4095, 4096, PLAN_N_SMALL - 1)
+PLAN_N_BIG = (PLAN_CARRY + 1) * PLAN_TILE + 3          # 1026 count blocks: the carry kernel takes a second pass
+# block 0; the last row the first carry pass covers; the first row of the second pass; the last row
+PLAN_LONG_BIG = (5, (PLAN_CARRY - 1) * PLAN_TILE + PLAN_TILE - 1, PLAN_CARRY * PLAN_TILE, PLAN_N_BIG - 1)
+PLAN_BROKEN = ("no_cross_wave", "no_block_carry", "no_pass_base", "shifted")
+PLAN_U = 2.0 ** -24
+PLAN_STALE = np.frombuffer(b"\xa5\xa5\xa5\xa5", dtype=np.float32)[0]    # what a partial that nobody wrote holds in a 0xA5-filled workspace
+
+
+def csr_plan_reference(deg, broken=None):
+    """The planner's three launches in numpy on the clamped degrees of the n rows -> (chunks [n], off [n], total).
+    chunks[r] = ceil(deg / 512) where deg > 512, else 0; off = the exclusive prefix sum of chunks; total = their sum (carry[nb]).
+    Computed the way the kernels do -- 8 rows per thread, a shuffle scan over the 64 lanes, the sums of the waves before, the
+    block's carry, the carry kernel's passes of 1024 block sums with a running base -- so that one step can be left out:
+    broken = "no_cross_wave" (before += wave_sum[i] missing), "no_block_carry" (carry[r / kCountTile] not added),
+    "no_pass_base" (base_sh += tile missing: every pass starts at 0 and carry[nb] is 0), "shifted" (every offset + total)."""
+    assert broken is None or broken in PLAN_BROKEN
+    deg = np.asarray(deg, dtype=np.int64)
+    n = len(deg)
+    chunks = np.where(deg > PLAN_CHUNK, -(-deg // PLAN_CHUNK), 0)
+    nb = -(-n // PLAN_TILE)
+    c = np.zeros(nb * PLAN_TILE, dtype=np.int64)
+    c[:n] = chunks
+    c = c.reshape(nb, PLAN_THREADS // PLAN_WAVE, PLAN_WAVE, PLAN_IPT)
+    s = c.sum(3)                                                   # a thread's 8 rows
+    lane_excl = np.cumsum(s, 2) - s                                # incl - s after the shuffles
+    wave_sum = s.sum(2)
+    before = np.cumsum(wave_sum, 1) - wave_sum
+    if broken == "no_cross_wave":
+        before[:] = 0
+    local = before[:, :, None, None] + lane_excl[:, :, :, None] + (np.cumsum(c, 3) - c)
+    block = wave_sum.sum(1)
+    carry = np.zeros(nb + 1, dtype=np.int64)
+    base = 0
+    for t0 in range(0, nb, PLAN_CARRY):
+        x = block[t0:t0 + PLAN_CARRY]
+        carry[t0:t0 + len(x)] = base + np.cumsum(x) - x
+        if broken != "no_pass_base":
+            base += int(x.sum())
+    carry[nb] = base
+    off = local.reshape(-1)[:n].copy()
+    if broken != "no_block_carry":
+        off += carry[np.arange(n) // PLAN_TILE]
+    total = int(carry[nb])
+    if broken == "shifted":
+        off += total
+    return chunks, off, total
+
+
+def csr_plan_case(n, long_rows, seed, filler=6):
+    """A rectangular CSR of n rows over ids in [0, n) -> (rowptr int64 [n + 1], col int32, deg int64 [n]).  Row long_rows[i] has
+    PLAN_DEGREES[i % 4] entries; the rows beside a long row that are not long themselves are empty; every other row has 0..filler.
+    Ids are random; every second long row holds its own id -- as the last entry, or as the first entry of its last chunk."""
+    rs = np.random.default_rng(seed)
+    long_rows = np.asarray(long_rows, dtype=np.int64)
+    deg = rs.integers(0, filler + 1, n).astype(np.int64)
+    beside = np.concatenate([long_rows - 1, long_rows + 1])
+    deg[beside[(beside >= 0) & (beside < n)]] = 0
+    deg[long_rows] = np.asarray(PLAN_DEGREES)[np.arange(len(long_rows)) % len(PLAN_DEGREES)]
+    rowptr = np.zeros(n + 1, dtype=np.int64)
+    np.cumsum(deg, out=rowptr[1:])
+    col = rs.integers(0, n, int(rowptr[-1])).astype(np.int32)
+    for i, p in enumerate(long_rows):
+        own = col[rowptr[p]:rowptr[p + 1]] == p
+        col[rowptr[p]:rowptr[p + 1]][own] = (p + 2) % n               # no accidental self entry
+        if i % 2 == 0:
+            last_chunk = rowptr[p] + (deg[p] - 1) // PLAN_CHUNK * PLAN_CHUNK
+            col[rowptr[p + 1] - 1 if i % 4 == 0 else last_chunk] = p
+    return rowptr, col, deg
+
+
+def csr_plan_perm(n, long_rows, seed):
+    """A permutation of [0, n) without a fixed point among the long rows that maps long rows to long rows (rotated by one) and the
+    others among themselves: as a node list it keeps the long rows at their positions while row != node id."""
+    rs = np.random.default_rng(seed)
+    long_rows = np.asarray(long_rows, dtype=np.int64)
+    perm = np.empty(n, dtype=np.int64)
+    rest = np.setdiff1d(np.arange(n), long_rows)
+    perm[rest] = rs.permutation(rest)
+    perm[long_rows] = np.roll(long_rows, 1)
+    return perm
+
+
+def plan_gamma(length, extra=0):
+    """Higham's gamma_m (Accuracy and Stability of Numerical Algorithms, section 4.2) for a sum of `length` terms in 512-term chunks:
+    m = min(length, 512) + ceil(length / 512) + extra -- the longest chain of additions is one chunk plus the chunk adds
+    (tests/test_gpu_csr_sum.py's gamma_bound); extra = 2 for a mean (the self term, the multiplication by fl(1 / c)) and for a
+    weighted term (the weight's rounding and the product's)."""
+    length = np.asarray(length, dtype=np.float64)
+    m = np.minimum(length, PLAN_CHUNK) + np.ceil(length / PLAN_CHUNK) + extra
+    return m * PLAN_U / (1 - m * PLAN_U)
+
+
+def csr_row_sums(rowptr, col, table):
+    """fp64 (sums, sums of magnitudes) [n, dim] of the rows of a CSR whose ids are inside the table, by np.add.reduceat"""
+    t = np.asarray(table)
+    n = len(rowptr) - 1
+    deg = np.diff(rowptr)
+    ids = col[:int(rowptr[-1])]
+    tot, mass = np.zeros((n, t.shape[1])), np.zeros((n, t.shape[1]))
+    has = deg > 0
+    starts = rowptr[:-1][has]                                         # strictly increasing: the empty rows own no entries
+    for c0 in range(0, t.shape[1] if has.any() else 0, 128):          # 128 columns at a time: [E, dim] in fp64 is large at dim 1433
+        rows = t[:, c0:c0 + 128].astype(np.float64)[ids]
+        tot[has, c0:c0 + 128] = np.add.reduceat(rows, starts, axis=0)
+        mass[has, c0:c0 + 128] = np.add.reduceat(np.abs(rows), starts, axis=0)
+    return tot, mass
+
+
+def csr_rows_reference(rowptr, col, table, nodes=None, self_loop=False, flag=False, mean=True, sums=None):
+    """fp64 row sums (mean=False: sage_csr_sum) or means (sage_csr_mean) of the rows `nodes` (None: every row) of a CSR whose ids
+    are inside the table, by np.add.reduceat -> (ref [rows, dim], bar [rows, dim], ceff [rows]).  The mean adds the node's own row
+    where self_loop and the row does not hold it, and divides by the count; a set without a term is zeros (NaN with `flag`).
+    bar = gamma_m * sum|terms| (/ count), m = plan_gamma's with 2 more for a mean.  Derived, not measured.
+    sums: csr_row_sums of the same arguments, to share among calls (left unchanged)."""
+    t = np.asarray(table)
+    n = len(rowptr) - 1
+    deg = np.diff(rowptr)
+    tot, mass = (x.copy() for x in (csr_row_sums(rowptr, col, table) if sums is None else sums))
+    extra = np.zeros(n, dtype=bool)
+    if mean and self_loop:
+        src = np.repeat(np.arange(n), deg)
+        own = np.zeros(n, dtype=bool)
+        own[src[col[:len(src)] == src]] = True
+        extra = ~own
+        tot[extra] += t[:n][extra].astype(np.float64)
+        mass[extra] += np.abs(t[:n][extra].astype(np.float64))
+    ceff = deg + extra
+    if nodes is not None:
+        nodes = np.asarray(nodes, dtype=np.int64)
+        tot, mass, ceff, deg = tot[nodes], mass[nodes], ceff[nodes], deg[nodes]
+    if not mean:
+        return tot, plan_gamma(deg)[:, None] * mass, ceff
+    d = np.maximum(ceff, 1)[:, None]
+    ref = tot / d
+    ref[ceff == 0] = np.nan if flag else 0.0
+    return ref, plan_gamma(deg, 2)[:, None] * mass / d, ceff
+
+
+def plan_miss(got, ref, bar, what=""):
+    """How `got` misses a planner test's bar: None when it meets it, else a message.  NaNs must coincide, elements without a term
+    (bar 0) are exact, every other element is within its bar.  Prints the largest err / bar (information only)."""
+    got = np.asarray(got, dtype=np.float64)
+    if got.shape != ref.shape:
+        return f"{what}: shape {got.shape} vs {ref.shape}"
+    if not np.array_equal(np.isnan(got), np.isnan(ref)):
+        return f"{what}: NaN pattern differs in rows {np.nonzero((np.isnan(got) != np.isnan(ref)).any(1))[0][:8].tolist()}"
+    fin = ~np.isnan(ref)
+    err = np.where(fin, np.abs(np.where(fin, got - ref, 0.0)), 0.0)
+    ratio = np.where(bar > 0, err / np.maximum(bar, 1e-300), np.where(err > 0, np.inf, 0.0))
+    worst = float(ratio.max()) if ratio.size else 0.0
+    print(f"{what}: max err / bound = {worst:.3f}")
+    if worst > 1.0:
+        r, c = np.unravel_index(np.argmax(ratio), ratio.shape)
+        return f"{what}: row {r} column {c}: |got - ref| = {err[r, c]:.3e} > bar {bar[r, c]:.3e} ({int((ratio > 1).sum())} elements over)"
+    return None
+
+
+def csr_mean_under_plan(rowptr, col, table, rows, off, total, cap, self_loop, last_wins=True):
+    """What sage_csr_mean's chunk and row kernels make of rows `rows` (row r = node r) given the plan (off, total = carry[nb]) and a
+    workspace of `cap` items filled with 0xA5 bytes, in numpy fp32 with the kernels' order of additions -> {row: [dim] fp32}.
+    csr_expand_kernel: a long row whose chunks fit writes its id into item_row[off .. off + k) (two rows that claim one item race:
+    the later row wins, or the earlier one with last_wins=False); csr_chunk_kernel: item i < min(total, cap) is summed for the row
+    item_row[i] names if that row's range holds i (chunk_item), every other partial stays stale; csr_row_kernel: a row that fits adds
+    partials[off .. off + k) -- whoever wrote them -- and takes has_self from there, any other long row sums its chunks in place."""
+    t = np.asarray(table, dtype=np.float32)
+    deg = np.diff(rowptr)
+    k_of = {int(r): int(-(-deg[r] // PLAN_CHUNK)) if deg[r] > PLAN_CHUNK else 0 for r in rows}
+    fits = {r: k_of[r] > 0 and off[r] + k_of[r] <= cap for r in k_of}
+    item_row = {}
+    for r in (sorted(k_of) if last_wins else sorted(k_of, reverse=True)):
+        if fits[r]:
+            for i in range(int(off[r]), int(off[r]) + k_of[r]):
+                item_row[i] = r
+
+    def chunk(r, c):
+        b = int(rowptr[r]) + c * PLAN_CHUNK
+        e = min(b + PLAN_CHUNK, int(rowptr[r + 1]))
+        ids = col[b:e]
+        return np.cumsum(t[ids], axis=0, dtype=np.float32)[-1], bool((ids == r).any())      # sequential fp32, in stored order
+
+    items = min(int(total), int(cap))
+    partial, has_self = {}, {}
+    for i, r in item_row.items():
+        if i < items:
+            partial[i], has_self[i] = chunk(r, i - int(off[r]))
+    stale = np.full(t.shape[1], PLAN_STALE, dtype=np.float32)
+    out = {}
+    for r in k_of:
+        s = np.zeros(t.shape[1], dtype=np.float32)
+        found = False
+        if fits[r]:
+            for i in range(int(off[r]), int(off[r]) + k_of[r]):
+                s = s + partial.get(i, stale)
+                found |= has_self.get(i, True)                       # 0xA5A5A5A5 != 0
+        elif k_of[r] > 0:
+            for c in range(k_of[r]):
+                p, f = chunk(r, c)
+                s = s + p
+                found |= f
+        else:
+            ids = col[rowptr[r]:rowptr[r + 1]]
+            if len(ids):
+                s = np.cumsum(t[ids], axis=0, dtype=np.float32)[-1]
+            found = bool((ids == r).any())
+        extra = bool(self_loop) and not found
+        if extra:
+            s = s + t[r]
+        ceff = int(deg[r]) + int(extra)
+        out[r] = (s * (np.float32(1.0) / np.float32(ceff))).astype(np.float32) if ceff else np.zeros_like(s)
+    return out
+
+
+def plan_item_cap(rows, max_edges):
+    """chunk_ws's item capacity: max_edges / 512 + min(rows, max_edges / 513)"""
+    return max_edges // PLAN_CHUNK + min(rows, max_edges // (PLAN_CHUNK + 1))
+
+
+def plan_tight_max_edges(rows, total):
+    """The smallest max_edges whose item list holds `total` items.  The list is then (almost always exactly) as long as the plan:
+    a long row whose offset is too large by anything no longer fits and is summed by its row wave."""
+    me = 0
+    while plan_item_cap(rows, me) < total:
+        me += 1
+    return me
+
+
+def embed_plan_case(embed_rows, long_rows, seed, n_sets=312, k=64):
+    """Sampled sets (nbr int32 [n_sets, k], cnt int32 [n_sets]) whose terms give embedding row long_rows[i] exactly
+    PLAN_DEGREES[i % 4] terms; the other terms name random other rows (runs of about one).  cnt cycles through k, k, k - 4, k, 0, k,
+    33, k; padding is -1."""
+    rs = np.random.default_rng(seed)
+    long_rows = np.asarray(long_rows, dtype=np.int64)
+    lens = np.asarray(PLAN_DEGREES)[np.arange(len(long_rows)) % len(PLAN_DEGREES)]
+    cnt = np.asarray([k, k, k - 4, k, 0, k, 33, k])[np.arange(n_sets) % 8].astype(np.int32)
+    terms = int(cnt.sum())
+    assert terms > lens.sum()
+    rest = np.setdiff1d(np.arange(min(embed_rows, 1 << 22)), long_rows)
+    keys = np.concatenate([np.repeat(long_rows, lens), rs.choice(rest, terms - int(lens.sum()))])
+    keys = keys[rs.permutation(terms)]
+    nbr = np.full((n_sets, k), -1, dtype=np.int32)
+    nbr[np.arange(k)[None, :] < cnt[:, None]] = keys                 # row-major: set t holds the next cnt[t] keys
+    return nbr, cnt
+
+
+def embed_plan_reference(grad, nbr, cnt, embed_rows, rows=None):
+    """fp64 sums of grad[t] / c_t per embedding row by np.add.at -> (ref, bar) [embed_rows, dim] (rows given: the compact arrays
+    over those ascending ids).  bar = gamma_m * sum|terms|, m = plan_gamma's of the row's term count with 2 more for the weight."""
+    g = np.asarray(grad, dtype=np.float64)
+    k = nbr.shape[1]
+    c = np.minimum(cnt, k).astype(np.int64)
+    held = np.arange(k)[None, :] < c[:, None]
+    keys = nbr[held].astype(np.int64)
+    sets = np.repeat(np.arange(len(c)), c)
+    term = g[sets] / c[sets, None]
+    if rows is not None:
+        keys = np.searchsorted(rows, keys)
+        embed_rows = len(rows)
+    ref, mass = np.zeros((embed_rows, g.shape[1])), np.zeros((embed_rows, g.shape[1]))
+    np.add.at(ref, keys, term)
+    np.add.at(mass, keys, np.abs(term))
+    return ref, plan_gamma(np.bincount(keys, minlength=embed_rows), 2)[:, None] * mass
