@@ -1,5 +1,5 @@
 // The weighted term sum of the csr_mean adjoints: sage_csr_mean_backward.hip (whole graph, caller-built transpose, and its GROUPED
-// form) and sage_csr_mean_backward_rows.hip (one seed batch, transpose sorted per call).  sum_weighted is the only place that forms a
+// form) and sage_csr_mean_backward_rows.hip (one seed batch, transpose sorted per call; every table row, or the touched rows only).  sum_weighted is the only place that forms a
 // term -- ONE fma(w[x], grad_out[x], acc) -- and bwd_chunk_kernel / bwd_row_kernel hand it to sage_csr_common.h's chunked_row_sum, so
 // every member of the family adds a row's terms in the same way and a row's bits depend on its term sequence alone.
 // Internal linkage, as sage_csr_common.h: each translation unit that includes this holds its own copy of the kernels.
@@ -115,6 +115,52 @@ __global__ __launch_bounds__(256) void bwd_row_kernel(const int64_t* __restrict_
     }
 }
 
+// 5'. one wave per RUN u < U of a run list (sage_sorted_terms.h; U read on the device), GROUPED: the run's sum -- bwd_row_kernel's, the
+// same chunked_row_sum over the same sum_weighted -- stored as row u of the compact gradient (u < max_rows) and / or applied to row
+// run_row[u] of the table: table = fma(-lr, sum, table), one rounding.  Rows without a run are neither read nor written.
+template <int VEC>
+__global__ __launch_bounds__(256) void bwd_runs_row_kernel(const int64_t* __restrict__ runptr, const int32_t* __restrict__ col_t, int runs_cap,
+                                                           const int64_t* __restrict__ num_runs, const float* __restrict__ w,
+                                                           const float* __restrict__ g, int64_t ldg, int dim, const int64_t* __restrict__ off,
+                                                           int64_t cap, const float* __restrict__ partials, int64_t num_src,
+                                                           const int32_t* __restrict__ run_row, int32_t* __restrict__ rows_out,
+                                                           float* __restrict__ grad_rows, int64_t max_rows, int64_t ldr,
+                                                           float* __restrict__ table, int64_t ldt, int num_rows, float lr) {
+    using V = typename VecT<VEC>::type;
+    const int lane = sage_lane();
+    const int wave = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const int nwaves = (int)((gridDim.x * blockDim.x) >> 6);
+    const int last_row = (int)num_src - 1;
+    const int64_t total = runptr[runs_cap];
+    const int nruns = (int)min(uniform64(*num_runs), (int64_t)runs_cap);
+    for (int u = wave; u < nruns; u += nwaves) {
+        int32_t v;
+        int64_t b, e;
+        row_span<true>(runptr, runs_cap, nullptr, u, total, v, b, e);
+        const int64_t k = long_chunks(e - b);
+        const int64_t o = first_item<true>(off, u, k);
+        const int row = min(max(__builtin_amdgcn_readfirstlane(run_row[u]), 0), num_rows - 1);   // a key of the layout: inside the table already
+        const bool keep = grad_rows != nullptr && u < max_rows;
+        if (keep && lane == 0) rows_out[u] = row;
+        for (int cb = 0; cb < dim; cb += kWave * VEC) {
+            const int c0 = cb + lane * VEC;
+            const bool ok = c0 < dim;
+            const V s = chunked_row_sum<V>(k, o, cap, partials, dim, c0, ok, b, e, [&](int64_t tb, int64_t te, V& acc) {
+                sum_weighted<VEC>(col_t, tb, te, w, g, ldg, last_row, c0, ok, acc);
+            });
+            if (ok) {
+                if (keep) *reinterpret_cast<V*>(grad_rows + (int64_t)u * ldr + c0) = s;
+                if (table) {
+                    V* p = reinterpret_cast<V*>(table + (int64_t)row * ldt + c0);
+                    V x = *p;
+                    vfma(x, -lr, s);
+                    *p = x;
+                }
+            }
+        }
+    }
+}
+
 // What the two passes sum: the n rows (`nodes`, or row r itself) of the CSR (rowptr_t, col_t) over num_rows rows, whose entries name
 // rows of w and grad_out.  grouped: w and grad_out have num_src rows and the list holds the self entries (flag is not read).
 struct BwdSum {
@@ -125,12 +171,10 @@ struct BwdSum {
     float* grad_table; int64_t ldgt;
 };
 
-// Launches 1-5 of the family: the chunk plan over the rows, the chunk pass, the row pass.
-inline int bwd_sum_launch(const BwdSum& s, void* workspace, const ChunkWs& C, hipStream_t st) {
-    ChunkPlan P;
-    if (const int rc = csr_chunk_plan(s.rowptr_t, s.num_rows, s.nodes, s.n, workspace, C, st, &P)) return rc;
-
-    const bool vec4 = (s.dim % 4 == 0) && (s.ldg % 4 == 0) && (s.ldgt % 4 == 0) && sage_aligned(s.grad_out, 16) && sage_aligned(s.grad_table, 16);
+// Launches 1-4 of the family: the chunk plan over the rows and the chunk pass.  vec4: 16-byte accesses (the caller's outputs included).
+inline int bwd_chunk_launch(const BwdSum& s, bool vec4, void* workspace, const ChunkWs& C, hipStream_t st, ChunkPlan* plan) {
+    if (const int rc = csr_chunk_plan(s.rowptr_t, s.num_rows, s.nodes, s.n, workspace, C, st, plan)) return rc;
+    const ChunkPlan& P = *plan;
     if (P.cap > 0) {
         const int blocks = (int)std::min<int64_t>((P.cap + 3) / 4, kNumCU * 8);
 #define SAGE_BWD_CHUNK(VEC, GROUPED)                                                                                                    \
@@ -141,6 +185,14 @@ inline int bwd_sum_launch(const BwdSum& s, void* workspace, const ChunkWs& C, hi
 #undef SAGE_BWD_CHUNK
         SAGE_CHECK_LAUNCH("bwd_chunk_kernel");
     }
+    return SAGE_OK;
+}
+
+// Launches 1-5 of the family: the chunk plan over the rows, the chunk pass, the row pass.
+inline int bwd_sum_launch(const BwdSum& s, void* workspace, const ChunkWs& C, hipStream_t st) {
+    const bool vec4 = (s.dim % 4 == 0) && (s.ldg % 4 == 0) && (s.ldgt % 4 == 0) && sage_aligned(s.grad_out, 16) && sage_aligned(s.grad_table, 16);
+    ChunkPlan P;
+    if (const int rc = bwd_chunk_launch(s, vec4, workspace, C, st, &P)) return rc;
     const int blocks = std::min(sage_cdiv(s.n, 4), kNumCU * 8);
 #define SAGE_BWD_ROW(VEC, GROUPED)                                                                                                        \
     hipLaunchKernelGGL((bwd_row_kernel<VEC, GROUPED>), dim3(blocks), dim3(256), 0, st, s.rowptr_t, s.col_t, s.num_rows, s.nodes, s.n, s.w, s.flag, \

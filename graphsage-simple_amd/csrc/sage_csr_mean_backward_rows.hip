@@ -19,38 +19,74 @@
 //   i. sort    hipcub::DeviceRadixSort::SortPairs on the bits of num_rows (stable)
 //   j. rowptr  rowptr_f[f] = first sorted position whose key is >= f (sorted_rowptr_kernel)
 //   1-5.       the family's chunk plan, chunk pass and row pass over (rowptr_f, vals), GROUPED: w and grad_out are indexed by seed row
+// sage_csr_mean_backward_touched (below) is the same sum for the table rows that have a term only, with the SGD update of those rows
+// fused in: steps a-i are one function behind both entries (rows_sort_terms), step j is sage_sorted_terms.h's run list of the sorted
+// keys instead of a row pointer over the table, the chunk plan and chunk pass walk the runs, and bwd_runs_row_kernel strides over the
+// runs u < U, U read on the device.  Nothing there is sized by num_rows.
 #include "sage_csr_bwd_body.h"
 #include "sage_sorted_terms.h"
 
 namespace {
 
-struct RowsBwdLayout {
-    size_t w, found, local, carry, estart, tstart, keys_in, keys_out, vals_in, vals_out, cub, cub_bytes, rowptr_f, total;
-    ChunkWs c;
+// What steps a-i of both entries need of a workspace.  It serves either self_loop, so it holds max_edges + n term positions.
+struct TermsWs {
+    size_t w, found, local, carry, estart, tstart, keys_in, keys_out, vals_in, vals_out, cub, cub_bytes;
     int64_t slots;       // term positions the workspace holds (at least 1)
     int64_t nblocks;     // count-kernel blocks over the seed rows
 };
 
-// The workspace serves either self_loop, so it holds max_edges + n term positions.
-bool rows_bwd_layout(int32_t n, int64_t max_edges, int64_t num_rows, int32_t dim, RowsBwdLayout* L) {
+bool terms_ws(int32_t n, int64_t max_edges, int64_t num_rows, int32_t dim, WsCursor& cur, TermsWs* T) {
     if (n < 0 || max_edges < 0 || num_rows < 0 || num_rows >= (1ll << 31) - 1 || dim < 1 || max_edges + (int64_t)n >= (1ll << 31)) return false;
-    L->slots = std::max<int64_t>(max_edges + n, 1);
-    L->nblocks = std::max<int64_t>(((int64_t)n + kCountTile - 1) / kCountTile, 1);
+    T->slots = std::max<int64_t>(max_edges + n, 1);
+    T->nblocks = std::max<int64_t>(((int64_t)n + kCountTile - 1) / kCountTile, 1);
+    T->w = cur.take((size_t)n * 4);
+    T->found = cur.take((size_t)n * 4);
+    T->local = cur.take((size_t)n * 8);
+    T->carry = cur.take((size_t)(T->nblocks + 1) * 8);
+    T->estart = cur.take((size_t)(n + 1) * 8);
+    T->tstart = cur.take((size_t)(n + 1) * 8);
+    T->keys_in = cur.take((size_t)T->slots * 4);
+    T->keys_out = cur.take((size_t)T->slots * 4);
+    T->vals_in = cur.take((size_t)T->slots * 4);
+    T->vals_out = cur.take((size_t)T->slots * 4);
+    T->cub_bytes = sort_temp_reserve(T->slots);
+    T->cub = cur.take(T->cub_bytes);
+    return true;
+}
+
+struct RowsBwdLayout {
+    TermsWs t;
+    size_t rowptr_f, total;
+    ChunkWs c;
+};
+
+bool rows_bwd_layout(int32_t n, int64_t max_edges, int64_t num_rows, int32_t dim, RowsBwdLayout* L) {
     WsCursor cur;
-    L->w = cur.take((size_t)n * 4);
-    L->found = cur.take((size_t)n * 4);
-    L->local = cur.take((size_t)n * 8);
-    L->carry = cur.take((size_t)(L->nblocks + 1) * 8);
-    L->estart = cur.take((size_t)(n + 1) * 8);
-    L->tstart = cur.take((size_t)(n + 1) * 8);
-    L->keys_in = cur.take((size_t)L->slots * 4);
-    L->keys_out = cur.take((size_t)L->slots * 4);
-    L->vals_in = cur.take((size_t)L->slots * 4);
-    L->vals_out = cur.take((size_t)L->slots * 4);
-    L->cub_bytes = sort_temp_reserve(L->slots);
-    L->cub = cur.take(L->cub_bytes);
+    if (!terms_ws(n, max_edges, num_rows, dim, cur, &L->t)) return false;
     L->rowptr_f = cur.take((size_t)(num_rows + 1) * 8);
-    if (!chunk_ws(num_rows, L->slots, dim, cur, &L->c)) return false;      // every long run's chunks fit: at most slots terms in all
+    if (!chunk_ws(num_rows, L->t.slots, dim, cur, &L->c)) return false;      // every long run's chunks fit: at most slots terms in all
+    L->total = cur.off;
+    return true;
+}
+
+// sage_csr_mean_backward_touched: a run list of at most runs_cap = min(max_edges + n, num_rows) runs instead of rowptr_f; for
+// num_rows >= max_edges + n nothing here depends on num_rows.
+struct TouchedLayout {
+    TermsWs t;
+    size_t run_row, runptr, heads, end_pos, total;
+    ChunkWs c;
+    int64_t runs_cap;
+};
+
+bool touched_layout(int32_t n, int64_t max_edges, int64_t num_rows, int32_t dim, TouchedLayout* L) {
+    WsCursor cur;
+    if (!terms_ws(n, max_edges, num_rows, dim, cur, &L->t)) return false;
+    L->runs_cap = std::min<int64_t>(max_edges + n, num_rows);      // distinct rows with a term: what every array below is sized by
+    L->run_row = cur.take((size_t)L->runs_cap * 4);
+    L->runptr = cur.take((size_t)(L->runs_cap + 1) * 8);
+    L->heads = cur.take((size_t)(run_head_blocks(L->t.slots) + 1) * 8);
+    L->end_pos = cur.take(8);
+    if (!chunk_ws(L->runs_cap, L->t.slots, dim, cur, &L->c)) return false;
     L->total = cur.off;
     return true;
 }
@@ -160,6 +196,86 @@ __global__ __launch_bounds__(256) void rows_layout_kernel(const int64_t* __restr
     }
 }
 
+// The sorted terms: keys ascending (table rows, then the sentinels num_rows), vals the seed row of each term, w the weight of each
+// seed row; `slots` positions in all.
+struct SortedTerms {
+    const int32_t* keys;
+    const int32_t* vals;
+    const float* w;
+    int64_t slots;
+};
+
+// What both entries pass on to steps a-i.
+struct TermsArgs {
+    const int64_t* rowptr; const int32_t* col; int64_t num_nodes;
+    const int32_t* nodes; int32_t n; int64_t max_edges;
+    const int32_t* index; int64_t num_rows; int32_t self_loop;
+    int64_t* total_terms;
+};
+
+// Steps a-i of both entries (n >= 1, num_rows >= 1), errors under the entry's `name`: the sort's temporary is checked before anything
+// is launched.
+int rows_sort_terms(const char* name, const TermsArgs& a, void* workspace, const TermsWs& L, hipStream_t st, SortedTerms* T) {
+    char* ws = (char*)workspace;
+    float* w = (float*)(ws + L.w);
+    int32_t* found = (int32_t*)(ws + L.found);
+    int64_t* local = (int64_t*)(ws + L.local);
+    int64_t* carry = (int64_t*)(ws + L.carry);
+    int64_t* estart = (int64_t*)(ws + L.estart);
+    int64_t* tstart = (int64_t*)(ws + L.tstart);
+    int32_t* keys_in = (int32_t*)(ws + L.keys_in);
+    int32_t* keys_out = (int32_t*)(ws + L.keys_out);
+    int32_t* vals_in = (int32_t*)(ws + L.vals_in);
+    int32_t* vals_out = (int32_t*)(ws + L.vals_out);
+    const int n = a.n, R = (int)a.num_rows;
+    const int64_t capacity = a.max_edges + (a.self_loop ? n : 0);
+    const int64_t slots = std::max<int64_t>(capacity, 1);         // <= L.slots
+    const int bits = sort_key_bits(a.num_rows);
+    size_t sort_bytes = 0;
+    if (sort_temp_bytes((int)slots, bits, &sort_bytes) != hipSuccess || sort_bytes > L.cub_bytes) {
+        sage_set_error("%s: the radix sort asks for %zu bytes of temporary, %zu reserved", name, sort_bytes, L.cub_bytes);
+        return SAGE_ELAUNCH;
+    }
+
+    const int nb = (int)L.nblocks;
+    const int entry_blocks = (int)std::min<int64_t>(std::max<int64_t>((a.max_edges / kChunk + 4) / 4, 1), kNumCU * 8);
+    if (a.self_loop) {
+        hipLaunchKernelGGL(rows_count_kernel<false>, dim3(nb), dim3(kCountThreads), 0, st, a.rowptr, a.num_nodes, a.nodes, n, 0,
+                           (const int32_t*)nullptr, (float*)nullptr, local, carry);
+        SAGE_CHECK_LAUNCH("rows_count_kernel (entries)");
+        hipLaunchKernelGGL(csr_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, carry, nb);
+        SAGE_CHECK_LAUNCH("csr_carry_kernel (entries)");
+        hipLaunchKernelGGL(rows_start_kernel, dim3(sage_cdiv((int64_t)n + 1, 256)), dim3(256), 0, st, (const int64_t*)local, (const int64_t*)carry, nb,
+                           n, estart, (int64_t*)nullptr);
+        SAGE_CHECK_LAUNCH("rows_start_kernel (entries)");
+        if (const int rc = sage_fill_u32(found, 0u, (size_t)n, st)) return rc;
+        hipLaunchKernelGGL(rows_self_scan_kernel, dim3(entry_blocks), dim3(256), 0, st, a.rowptr, a.col, a.num_nodes, a.nodes, n,
+                           (const int64_t*)estart, found);
+        SAGE_CHECK_LAUNCH("rows_self_scan_kernel");
+    }
+    hipLaunchKernelGGL(rows_count_kernel<true>, dim3(nb), dim3(kCountThreads), 0, st, a.rowptr, a.num_nodes, a.nodes, n, (int)a.self_loop,
+                       (const int32_t*)found, w, local, carry);
+    SAGE_CHECK_LAUNCH("rows_count_kernel (terms)");
+    hipLaunchKernelGGL(csr_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, carry, nb);
+    SAGE_CHECK_LAUNCH("csr_carry_kernel (terms)");
+    hipLaunchKernelGGL(rows_start_kernel, dim3(sage_cdiv((int64_t)n + 1, 256)), dim3(256), 0, st, (const int64_t*)local, (const int64_t*)carry, nb, n,
+                       tstart, a.total_terms);
+    SAGE_CHECK_LAUNCH("rows_start_kernel (terms)");
+
+    const int term_blocks = (int)std::min<int64_t>(std::max<int64_t>((slots / kChunk + 4) / 4, 1), kNumCU * 8);
+    hipLaunchKernelGGL(rows_layout_kernel, dim3(term_blocks), dim3(256), 0, st, a.rowptr, a.col, a.num_nodes, a.nodes, n, (const int64_t*)tstart,
+                       a.index, R, slots, capacity, keys_in, vals_in);
+    SAGE_CHECK_LAUNCH("rows_layout_kernel");
+    size_t cub_bytes = L.cub_bytes;
+    if (hipcub::DeviceRadixSort::SortPairs(ws + L.cub, cub_bytes, (const int32_t*)keys_in, keys_out, (const int32_t*)vals_in, vals_out, (int)slots, 0,
+                                           bits, st) != hipSuccess) {
+        sage_set_error("%s: radix sort failed", name);
+        return SAGE_ELAUNCH;
+    }
+    *T = SortedTerms{keys_out, vals_out, w, slots};
+    return SAGE_OK;
+}
+
 }  // namespace
 
 extern "C" size_t sage_csr_mean_backward_rows_workspace_bytes(int32_t n, int64_t max_edges, int64_t num_rows, int32_t dim) {
@@ -189,73 +305,86 @@ extern "C" int sage_csr_mean_backward_rows(const int64_t* rowptr, const int32_t*
     if (num_rows == 0) return SAGE_OK;
 
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    float* w = (float*)(ws + L.w);
-    int32_t* found = (int32_t*)(ws + L.found);
-    int64_t* local = (int64_t*)(ws + L.local);
-    int64_t* carry = (int64_t*)(ws + L.carry);
-    int64_t* estart = (int64_t*)(ws + L.estart);
-    int64_t* tstart = (int64_t*)(ws + L.tstart);
-    int32_t* keys_in = (int32_t*)(ws + L.keys_in);
-    int32_t* keys_out = (int32_t*)(ws + L.keys_out);
-    int32_t* vals_in = (int32_t*)(ws + L.vals_in);
-    int32_t* vals_out = (int32_t*)(ws + L.vals_out);
-    int64_t* rowptr_f = (int64_t*)(ws + L.rowptr_f);
+    int64_t* rowptr_f = (int64_t*)((char*)workspace + L.rowptr_f);
     const int R = (int)num_rows;
-    const BwdSum sum{rowptr_f, vals_out, num_rows, true, nullptr, R, w, nullptr, n, grad_out, ldg, dim, grad_table, ldgt};
 
     if (n == 0) {                                        // no term: every row of grad_table is stored as zeros
+        char* ws = (char*)workspace;
+        const BwdSum sum{rowptr_f, (const int32_t*)(ws + L.t.vals_out), num_rows, true, nullptr, R, (const float*)(ws + L.t.w), nullptr, n, grad_out, ldg, dim,
+                         grad_table, ldgt};
         if (const int rc = sage_fill_u32(rowptr_f, 0u, (size_t)(num_rows + 1) * 2, st)) return rc;
         if (total_terms)
             if (const int rc = sage_fill_u32(total_terms, 0u, 2, st)) return rc;
         return bwd_sum_launch(sum, workspace, L.c, st);
     }
 
-    const int64_t capacity = max_edges + (self_loop ? n : 0);
-    const int64_t slots = std::max<int64_t>(capacity, 1);         // <= L.slots
-    const int bits = sort_key_bits(num_rows);
-    size_t sort_bytes = 0;
-    if (sort_temp_bytes((int)slots, bits, &sort_bytes) != hipSuccess || sort_bytes > L.cub_bytes) {
-        sage_set_error("csr_mean_backward_rows: the radix sort asks for %zu bytes of temporary, %zu reserved", sort_bytes, L.cub_bytes);
-        return SAGE_ELAUNCH;
-    }
-
-    const int nb = (int)L.nblocks;
-    const int entry_blocks = (int)std::min<int64_t>(std::max<int64_t>((max_edges / kChunk + 4) / 4, 1), kNumCU * 8);
-    if (self_loop) {
-        hipLaunchKernelGGL(rows_count_kernel<false>, dim3(nb), dim3(kCountThreads), 0, st, rowptr, num_nodes, nodes, n, 0, (const int32_t*)nullptr,
-                           (float*)nullptr, local, carry);
-        SAGE_CHECK_LAUNCH("rows_count_kernel (entries)");
-        hipLaunchKernelGGL(csr_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, carry, nb);
-        SAGE_CHECK_LAUNCH("csr_carry_kernel (entries)");
-        hipLaunchKernelGGL(rows_start_kernel, dim3(sage_cdiv((int64_t)n + 1, 256)), dim3(256), 0, st, (const int64_t*)local, (const int64_t*)carry, nb,
-                           n, estart, (int64_t*)nullptr);
-        SAGE_CHECK_LAUNCH("rows_start_kernel (entries)");
-        if (const int rc = sage_fill_u32(found, 0u, (size_t)n, st)) return rc;
-        hipLaunchKernelGGL(rows_self_scan_kernel, dim3(entry_blocks), dim3(256), 0, st, rowptr, col, num_nodes, nodes, n, (const int64_t*)estart,
-                           found);
-        SAGE_CHECK_LAUNCH("rows_self_scan_kernel");
-    }
-    hipLaunchKernelGGL(rows_count_kernel<true>, dim3(nb), dim3(kCountThreads), 0, st, rowptr, num_nodes, nodes, n, (int)self_loop,
-                       (const int32_t*)found, w, local, carry);
-    SAGE_CHECK_LAUNCH("rows_count_kernel (terms)");
-    hipLaunchKernelGGL(csr_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, carry, nb);
-    SAGE_CHECK_LAUNCH("csr_carry_kernel (terms)");
-    hipLaunchKernelGGL(rows_start_kernel, dim3(sage_cdiv((int64_t)n + 1, 256)), dim3(256), 0, st, (const int64_t*)local, (const int64_t*)carry, nb, n,
-                       tstart, total_terms);
-    SAGE_CHECK_LAUNCH("rows_start_kernel (terms)");
-
-    const int term_blocks = (int)std::min<int64_t>(std::max<int64_t>((slots / kChunk + 4) / 4, 1), kNumCU * 8);
-    hipLaunchKernelGGL(rows_layout_kernel, dim3(term_blocks), dim3(256), 0, st, rowptr, col, num_nodes, nodes, n, (const int64_t*)tstart, index, R,
-                       slots, capacity, keys_in, vals_in);
-    SAGE_CHECK_LAUNCH("rows_layout_kernel");
-    size_t cub_bytes = L.cub_bytes;
-    if (hipcub::DeviceRadixSort::SortPairs(ws + L.cub, cub_bytes, (const int32_t*)keys_in, keys_out, (const int32_t*)vals_in, vals_out, (int)slots, 0,
-                                           bits, st) != hipSuccess) {
-        sage_set_error("csr_mean_backward_rows: radix sort failed");
-        return SAGE_ELAUNCH;
-    }
-    hipLaunchKernelGGL(sorted_rowptr_kernel, dim3(sage_cdiv(num_rows + 1, 256)), dim3(256), 0, st, (const int32_t*)keys_out, (int)slots, R, rowptr_f);
+    SortedTerms T;
+    const TermsArgs args{rowptr, col, num_nodes, nodes, n, max_edges, index, num_rows, self_loop, total_terms};
+    if (const int rc = rows_sort_terms("csr_mean_backward_rows", args, workspace, L.t, st, &T)) return rc;
+    hipLaunchKernelGGL(sorted_rowptr_kernel, dim3(sage_cdiv(num_rows + 1, 256)), dim3(256), 0, st, T.keys, (int)T.slots, R, rowptr_f);
     SAGE_CHECK_LAUNCH("sorted_rowptr_kernel");
+    const BwdSum sum{rowptr_f, T.vals, num_rows, true, nullptr, R, T.w, nullptr, n, grad_out, ldg, dim, grad_table, ldgt};
     return bwd_sum_launch(sum, workspace, L.c, st);
+}
+
+extern "C" size_t sage_csr_mean_backward_touched_workspace_bytes(int32_t n, int64_t max_edges, int64_t num_rows, int32_t dim) {
+    TouchedLayout L;
+    return touched_layout(n, max_edges, num_rows, dim, &L) ? L.total : 0;
+}
+
+extern "C" int sage_csr_mean_backward_touched(const int64_t* rowptr, const int32_t* col, int64_t num_nodes, const int32_t* nodes, int32_t n,
+                                              int64_t max_edges, const int32_t* index, int64_t num_rows, const float* grad_out, int64_t ldg,
+                                              int32_t dim, int32_t self_loop, int32_t* num_rows_out, int32_t* rows_out, float* grad_rows,
+                                              int64_t max_rows, int64_t ldr, float* table, int64_t ldt, float lr, int64_t* total_terms,
+                                              void* workspace, size_t workspace_bytes, sage_stream_t stream) {
+    // sage_csr_mean_backward_rows' rules and order: shapes first, then pointers, then the workspace
+    SAGE_REQUIRE(num_nodes >= 0 && num_nodes < (1ll << 31), "csr_mean_backward_touched: num_nodes = %lld", (long long)num_nodes);
+    SAGE_REQUIRE(n >= 0, "csr_mean_backward_touched: n = %d", n);
+    SAGE_REQUIRE(max_edges >= 0, "csr_mean_backward_touched: max_edges = %lld", (long long)max_edges);
+    SAGE_REQUIRE(num_rows >= 0 && num_rows < (1ll << 31) - 1, "csr_mean_backward_touched: num_rows = %lld", (long long)num_rows);
+    SAGE_REQUIRE(num_rows > 0 || n == 0, "csr_mean_backward_touched: num_rows = 0 with n = %d seed rows", n);
+    SAGE_REQUIRE(dim >= 1 && ldg >= dim, "csr_mean_backward_touched: dim = %d, ldg = %lld", dim, (long long)ldg);
+    SAGE_REQUIRE(!grad_rows || ldr >= dim, "csr_mean_backward_touched: dim = %d, ldr = %lld", dim, (long long)ldr);
+    SAGE_REQUIRE(!table || ldt >= dim, "csr_mean_backward_touched: dim = %d, ldt = %lld", dim, (long long)ldt);
+    SAGE_REQUIRE(!grad_rows || max_rows >= 1, "csr_mean_backward_touched: max_rows = %lld with grad_rows", (long long)max_rows);
+    SAGE_REQUIRE(self_loop == 0 || self_loop == 1, "csr_mean_backward_touched: self_loop = %d", self_loop);
+    SAGE_REQUIRE(rowptr && col && nodes && grad_out && num_rows_out, "csr_mean_backward_touched: NULL array");
+    SAGE_REQUIRE(grad_rows || table, "csr_mean_backward_touched: neither grad_rows nor table is given");
+    SAGE_REQUIRE(!grad_rows || rows_out, "csr_mean_backward_touched: grad_rows without rows_out");
+    TouchedLayout L;
+    SAGE_REQUIRE(touched_layout(n, max_edges, num_rows, dim, &L),
+                 "csr_mean_backward_touched: n = %d, max_edges = %lld, num_rows = %lld, dim = %d out of range (max_edges + n < 2^31)", n,
+                 (long long)max_edges, (long long)num_rows, dim);
+    if (const int rc = csr_workspace_check("csr_mean_backward_touched", workspace, workspace_bytes, L.total)) return rc;
+    if (n == 0) return SAGE_OK;                          // no term, no launch: num_rows_out and *total_terms are left as they were
+
+    hipStream_t st = (hipStream_t)stream;
+    char* ws = (char*)workspace;
+    int32_t* run_row = (int32_t*)(ws + L.run_row);
+    int64_t* runptr = (int64_t*)(ws + L.runptr);
+    int64_t* heads = (int64_t*)(ws + L.heads);
+    int64_t* end_pos = (int64_t*)(ws + L.end_pos);
+    const int R = (int)num_rows, C = (int)L.runs_cap;
+    SortedTerms T;
+    const TermsArgs args{rowptr, col, num_nodes, nodes, n, max_edges, index, num_rows, self_loop, total_terms};
+    if (const int rc = rows_sort_terms("csr_mean_backward_touched", args, workspace, L.t, st, &T)) return rc;
+    // j'. the run list of the sorted keys: at most C runs, heads[hb] = U
+    const int hb = (int)run_head_blocks(T.slots);
+    if (const int rc = sorted_run_list(T.keys, (int)T.slots, R, L.runs_cap, heads, run_row, runptr, end_pos, num_rows_out, st)) return rc;
+    // 1-4. the family's chunk plan and chunk pass with the run list as the row pointer; 5'. the row pass over the runs
+    const bool vec4 = (dim % 4 == 0) && (ldg % 4 == 0) && sage_aligned(grad_out, 16) && (!grad_rows || (ldr % 4 == 0 && sage_aligned(grad_rows, 16))) &&
+                      (!table || (ldt % 4 == 0 && sage_aligned(table, 16)));
+    const BwdSum sum{runptr, T.vals, L.runs_cap, true, nullptr, C, T.w, nullptr, n, grad_out, ldg, dim, nullptr, 0};
+    ChunkPlan P;
+    if (const int rc = bwd_chunk_launch(sum, vec4, workspace, L.c, st, &P)) return rc;
+    const int blocks = (int)std::min<int64_t>(sage_cdiv(L.runs_cap, 4), kNumCU * 8);
+#define SAGE_BWD_RUNS(VEC)                                                                                                                  \
+    hipLaunchKernelGGL((bwd_runs_row_kernel<VEC>), dim3(blocks), dim3(256), 0, st, (const int64_t*)runptr, T.vals, C, (const int64_t*)(heads + hb), \
+                       T.w, grad_out, ldg, dim, (const int64_t*)P.off, P.cap, (const float*)P.partials, (int64_t)n, (const int32_t*)run_row,       \
+                       rows_out, grad_rows, max_rows, ldr, table, ldt, R, lr)
+    if (vec4) SAGE_BWD_RUNS(4);
+    else SAGE_BWD_RUNS(1);
+#undef SAGE_BWD_RUNS
+    SAGE_CHECK_LAUNCH("bwd_runs_row_kernel");
+    return SAGE_OK;
 }

@@ -173,10 +173,8 @@ __global__ __launch_bounds__(256) void embed_row_kernel(const float* __restrict_
 }
 
 // ---- sage_embed_grad_rows: the same sums over the RUNS of the sorted list, nothing sized by embed_rows -----------------------------
-// The sorted keys are the embedding rows with a term, ascending, each a run of equal keys, then the sentinels.  A run list takes the
-// place of the row pointer over the embedding rows: run u = (run_row[u], [runptr[u], runptr[u + 1])), u < U; entries [U, runs_cap] of
-// runptr hold the end of the terms (empty spans), so the count / carry / expand / chunk kernels above walk it as they walk a CSR of
-// runs_cap rows.  runs_cap = min(slots, embed_rows) bounds U on the host.
+// sage_sorted_terms.h's run list of the sorted keys takes the place of the row pointer over the embedding rows; the count / carry /
+// expand / chunk kernels above walk it as they walk a CSR of runs_cap = min(slots, embed_rows) rows.
 struct RowsLayout {
     SortWs s;
     size_t run_row, runptr, heads, end_pos, total;
@@ -184,13 +182,11 @@ struct RowsLayout {
     int64_t head_blocks, runs_cap;
 };
 
-constexpr int kHeadThreads = 256, kHeadIpt = 8, kHeadTile = kHeadThreads * kHeadIpt;
-
 bool rows_layout(int32_t n, int32_t k, int64_t embed_rows, int32_t dim, RowsLayout* L) {
     WsCursor cur;
     if (!sort_ws(n, k, embed_rows, dim, cur, &L->s)) return false;
     L->runs_cap = std::min<int64_t>(L->s.slots, embed_rows);       // distinct rows with a term: what every array below is sized by
-    L->head_blocks = ((int64_t)L->s.slots + kHeadTile - 1) / kHeadTile;
+    L->head_blocks = run_head_blocks(L->s.slots);
     L->run_row = cur.take((size_t)L->runs_cap * 4);
     L->runptr = cur.take((size_t)(L->runs_cap + 1) * 8);
     L->heads = cur.take((size_t)(L->head_blocks + 1) * 8);
@@ -198,75 +194,6 @@ bool rows_layout(int32_t n, int32_t k, int64_t embed_rows, int32_t dim, RowsLayo
     if (!chunk_ws(L->runs_cap, L->s.slots, dim, cur, &L->c)) return false;
     L->total = cur.off;
     return true;
-}
-
-// Is position i of the sorted keys the first of a run of a row (the sentinel's run is none)?
-__device__ inline bool run_head(const int32_t* __restrict__ keys, int64_t i, int sentinel) {
-    const int key = keys[i];
-    return key != sentinel && (i == 0 || keys[i - 1] != key);
-}
-
-// 3a / 3c. kHeadIpt consecutive positions per thread.  SCATTER false: heads[block] := the run heads in the block's tile (then
-// csr_carry_kernel: heads[block] := the runs before the tile, heads[head_blocks] := U).  SCATTER true: run u = heads[block] + (the
-// heads before it in the tile) gets its row and its start, and the one position where the terms end (the first sentinel, or
-// slots) is written to end_pos
-template <bool SCATTER>
-__global__ __launch_bounds__(kHeadThreads) void embed_heads_kernel(const int32_t* __restrict__ keys, int slots, int sentinel, int64_t runs_cap,
-                                                                    int64_t* __restrict__ heads, int32_t* __restrict__ run_row,
-                                                                    int64_t* __restrict__ runptr, int64_t* __restrict__ end_pos) {
-    __shared__ int wave_sum[kHeadThreads / kWave];
-    const int64_t i0 = (int64_t)blockIdx.x * kHeadTile + (int64_t)threadIdx.x * kHeadIpt;
-    bool h[kHeadIpt];
-    int s = 0;
-#pragma unroll
-    for (int u = 0; u < kHeadIpt; ++u) {
-        h[u] = i0 + u < slots && run_head(keys, i0 + u, sentinel);
-        s += h[u] ? 1 : 0;
-    }
-    const int lane = sage_lane(), w = threadIdx.x / kWave;
-    int incl = s;
-#pragma unroll
-    for (int d = 1; d < kWave; d <<= 1) {
-        const int y = __shfl_up(incl, d, kWave);
-        if (lane >= d) incl += y;
-    }
-    if (lane == kWave - 1) wave_sum[w] = incl;
-    __syncthreads();
-    int before = 0, block = 0;
-#pragma unroll
-    for (int i = 0; i < kHeadThreads / kWave; ++i) {
-        if (i < w) before += wave_sum[i];
-        block += wave_sum[i];
-    }
-    if (!SCATTER) {
-        if (threadIdx.x == 0) heads[blockIdx.x] = block;
-        return;
-    }
-    int64_t u_run = heads[blockIdx.x] + before + incl - s;
-#pragma unroll
-    for (int u = 0; u < kHeadIpt; ++u) {
-        const int64_t i = i0 + u;
-        if (i >= slots) break;
-        if (h[u]) {
-            if (u_run < runs_cap) {                                  // always: distinct keys below the sentinel are at most runs_cap
-                run_row[u_run] = keys[i];
-                runptr[u_run] = i;
-            }
-            ++u_run;
-        }
-        const int key = keys[i];
-        if (key == sentinel && (i == 0 || keys[i - 1] != sentinel)) *end_pos = i;          // sorted: exactly one such position, or none
-        if (i == slots - 1 && key != sentinel) *end_pos = slots;
-    }
-}
-
-// 3d. runptr[u] := the end of the terms for u in [U, runs_cap]; num_rows_out[0] := U
-__global__ __launch_bounds__(256) void embed_runs_fill_kernel(const int64_t* __restrict__ heads, int head_blocks, const int64_t* __restrict__ end_pos,
-                                                              int64_t runs_cap, int64_t* __restrict__ runptr, int32_t* __restrict__ num_rows_out) {
-    const int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t nruns = min(heads[head_blocks], runs_cap);
-    if (u == 0) num_rows_out[0] = (int32_t)nruns;
-    if (u >= nruns && u <= runs_cap) runptr[u] = *end_pos;
 }
 
 // 8'. LG lanes per run u < U (U read on the device): the run's sum, run_sum above, stored as row u of the compact gradient (u <
@@ -442,18 +369,8 @@ extern "C" int sage_embed_grad_rows(const float* grad_agg, int64_t ldg, int32_t 
     const int R = (int)embed_rows, C = (int)L.runs_cap, hb = (int)L.head_blocks;
     SortedTerms T;
     if (const int rc = sort_terms("embed_grad_rows", nbr, cnt, k, n, n_dev, row_order, R, workspace, L.s, st, &T)) return rc;
-    // the run list: count the heads per tile, scan the tiles, write the runs, close the list
-    hipLaunchKernelGGL(embed_heads_kernel<false>, dim3(hb), dim3(kHeadThreads), 0, st, T.keys, L.s.slots, R, L.runs_cap, heads, run_row, runptr,
-                       end_pos);
-    SAGE_CHECK_LAUNCH("embed_heads_kernel (count)");
-    hipLaunchKernelGGL(csr_carry_kernel, dim3(1), dim3(kCarryThreads), 0, st, heads, hb);
-    SAGE_CHECK_LAUNCH("csr_carry_kernel (runs)");
-    hipLaunchKernelGGL(embed_heads_kernel<true>, dim3(hb), dim3(kHeadThreads), 0, st, T.keys, L.s.slots, R, L.runs_cap, heads, run_row, runptr,
-                       end_pos);
-    SAGE_CHECK_LAUNCH("embed_heads_kernel (scatter)");
-    hipLaunchKernelGGL(embed_runs_fill_kernel, dim3(sage_cdiv(L.runs_cap + 1, 256)), dim3(256), 0, st, (const int64_t*)heads, hb,
-                       (const int64_t*)end_pos, L.runs_cap, runptr, num_rows_out);
-    SAGE_CHECK_LAUNCH("embed_runs_fill_kernel");
+    // the run list (sage_sorted_terms.h): count the heads per tile, scan the tiles, write the runs, close the list
+    if (const int rc = sorted_run_list(T.keys, L.s.slots, R, L.runs_cap, heads, run_row, runptr, end_pos, num_rows_out, st)) return rc;
     // the chunk split over the runs: sage_embed_grad's launches with the run list as the row pointer
     ChunkPlan P;
     if (const int rc = chunk_pass(grad_agg, ldg, dim, T, runptr, C, workspace, L.c, st, &P)) return rc;

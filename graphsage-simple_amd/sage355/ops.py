@@ -708,6 +708,104 @@ def csr_mean_backward_rows(rowptr, col, nodes, grad_out, index=None, num_rows=No
     return out
 
 
+def csr_mean_backward_touched_workspace_bytes(n, max_edges, num_rows, dim):
+    """Bytes of the workspace sage_csr_mean_backward_touched needs (host arithmetic; 0 = shape out of range; one value for every
+    num_rows >= max_edges + n)."""
+    return int(native.lib().sage_csr_mean_backward_touched_workspace_bytes(int(n), int(max_edges), int(num_rows), int(dim)))
+
+
+def csr_mean_backward_touched(rowptr, col, nodes, grad_out, index=None, num_rows=None, self_loop=False, max_edges=None, max_rows=None,
+                              table=None, lr=None, want_grad=True, out=None, workspace=None, total_terms=None):
+    """csr_mean_backward_rows for the touched table rows only, and / or their SGD update in place (sage_csr_mean_backward_touched:
+    nothing sized by num_rows or the graph).  The first arguments, max_edges and total_terms are csr_mean_backward_rows'.
+    -> (rows, num_rows, grad_rows): num_rows int32 [1] on the device, the number U of distinct table rows with a term; rows int32
+    [max_rows], grad_rows [max_rows, dim]: the first min(U, max_rows) of them ascending and their sums, bit for bit the rows
+    csr_mean_backward_rows stores (entries past that are left as they were); both None with want_grad=False.  max_rows: default
+    min(max_edges + n, num_rows), which always holds every row.  table [num_rows, dim] with lr: table[e] = fma(-lr, sum, table[e])
+    for ALL U rows, in place, other rows untouched (torch's version counter of `table` does not move: the caller's business).
+    out: (rows, num_rows, grad_rows) to write into (rows / grad_rows may be None there with want_grad=False); workspace: a uint8
+    device tensor to reuse."""
+    _need_gpu()
+    _chk(rowptr, torch.int64, "rowptr", 1)
+    _chk(col, torch.int32, "col", 1)
+    _chk(nodes, torch.int32, "nodes", 1)
+    grad_out, ldg = _row_major(grad_out, "grad_out")
+    num_nodes = rowptr.shape[0] - 1
+    if num_nodes < 0:
+        raise native.SageError("csr_mean_backward_touched: rowptr is empty")
+    n, dim = nodes.shape[0], grad_out.shape[1]
+    if grad_out.shape[0] < n:
+        raise native.SageError(f"csr_mean_backward_touched: grad_out has {grad_out.shape[0]} rows for {n} seed rows")
+    if index is not None:
+        _chk(index, torch.int32, "index", 1)
+        if index.shape[0] != num_nodes:
+            raise native.SageError(f"csr_mean_backward_touched: index has {index.shape[0]} entries for {num_nodes} nodes")
+        if num_rows is None:
+            raise native.SageError("csr_mean_backward_touched: num_rows is required with an index")
+    rows = num_nodes if num_rows is None else int(num_rows)
+    if rows < 0 or (rows == 0 and n > 0):
+        raise native.SageError(f"csr_mean_backward_touched: num_rows = {rows} with {n} seed rows")
+    if not want_grad and table is None:
+        raise native.SageError("csr_mean_backward_touched: nothing to do: want_grad=False and no table to update")
+    if (table is None) != (lr is None):
+        raise native.SageError("csr_mean_backward_touched: table and lr go together")
+    dev = grad_out.device
+    ldt = 0
+    if table is not None:
+        table, ldt = _row_major(table, "table")
+        if table.shape[0] < rows or table.shape[1] != dim:
+            raise native.SageError(f"csr_mean_backward_touched: table is {tuple(table.shape)}, expected ({rows}, {dim})")
+    if total_terms is not None:
+        _chk(total_terms, torch.int64, "total_terms", 1)
+    if max_edges is None:                                 # the host read: the entries of the seeds' rows (ids clamped into the graph)
+        v = nodes.long().clamp_(0, max(num_nodes - 1, 0))
+        max_edges = int((rowptr[v + 1] - rowptr[v]).clamp_(min=0).sum()) if n > 0 and num_nodes > 0 else 0
+    max_edges = int(max_edges)
+    cap = min(max_edges + n, rows) if max_rows is None else int(max_rows)
+    if want_grad and cap < 1 and n > 0:
+        raise native.SageError(f"csr_mean_backward_touched: max_rows = {cap}")
+    cap = max(cap, 1)
+    rows_t, num_t, grad_t = out if out is not None else (None, None, None)
+    if num_t is None:
+        num_t = torch.empty(1, dtype=torch.int32, device=dev)
+    _chk(num_t, torch.int32, "num_rows", 1)
+    ldr = 0
+    if want_grad:
+        if rows_t is None:
+            rows_t = torch.empty(cap, dtype=torch.int32, device=dev)
+        if grad_t is None:
+            grad_t = torch.empty((cap, dim), dtype=torch.float32, device=dev)
+        _chk(rows_t, torch.int32, "rows", 1)
+        grad_t, ldr = _row_major(grad_t, "grad_rows")
+        if rows_t.shape[0] < cap or grad_t.shape[0] < cap or grad_t.shape[1] != dim:
+            raise native.SageError(f"csr_mean_backward_touched: out is rows {tuple(rows_t.shape)}, grad_rows {tuple(grad_t.shape)}, "
+                                   f"expected ({cap},) and ({cap}, {dim})")
+    else:
+        rows_t = grad_t = None
+    if n == 0:                                             # the library launches nothing then: the counts are written here
+        num_t.zero_()
+        if total_terms is not None:
+            total_terms.zero_()
+        return rows_t, num_t, grad_t
+    # an empty tensor may have no storage address: the kernels read none of it
+    if col.numel() == 0:
+        col = torch.zeros(1, dtype=torch.int32, device=dev)
+    if index is not None and index.numel() == 0:
+        index = torch.zeros(1, dtype=torch.int32, device=dev)
+    need = csr_mean_backward_touched_workspace_bytes(n, max_edges, rows, dim)
+    if need == 0:
+        raise native.SageError(f"csr_mean_backward_touched: n = {n}, max_edges = {max_edges}, num_rows = {rows}, dim = {dim} out of range")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    rc = native.lib().sage_csr_mean_backward_touched(native.ptr(rowptr), native.ptr(col), num_nodes, native.ptr(nodes), n, max_edges,
+                                                     native.ptr(index), rows, native.ptr(grad_out), ldg, dim, 1 if self_loop else 0,
+                                                     native.ptr(num_t), native.ptr(rows_t), native.ptr(grad_t), cap, ldr, native.ptr(table),
+                                                     ldt, 0.0 if lr is None else float(lr), native.ptr(total_terms), native.ptr(workspace),
+                                                     workspace.numel(), native.stream_handle())
+    native.check(rc, "csr_mean_backward_touched")
+    return rows_t, num_t, grad_t
+
+
 def group_rows(index, num_groups):
     """(rowptr_g int64 [K + 1], col_g int32 [N]) of an index [N] with values in [0, K = num_groups): row k of this rectangular
     CSR holds the positions v with index[v] == k, ascending -- what csr_sum adds up for row k of a shared embedding

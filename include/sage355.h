@@ -395,6 +395,62 @@ int sage_csr_mean_backward_rows(const int64_t* rowptr, const int32_t* col, int64
                                 void* workspace, size_t workspace_bytes, sage_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * sage_csr_mean_backward_touched (additive, ABI 9) --
+ * sage_csr_mean_backward_rows for the TOUCHED table rows only, and the SGD
+ * update of those rows in place: what exact mini-batches over a 1hot embedding
+ * of millions of rows need, where a batch's neighbourhood names a few thousand.
+ * It is to sage_csr_mean_backward_rows what sage_embed_grad_rows is to
+ * sage_embed_grad.  The first twelve arguments are that entry's, with its
+ * terms, clamps, weights w_r, term ORDER and its rule for a max_edges that is
+ * too small (terms past max_edges + (self_loop ? n : 0) positions are DROPPED;
+ * *total_terms receives the true count).  Let e_0 < e_1 < ... < e_{U-1} be the
+ * distinct table rows that receive at least one term and s_u row e_u's sum, bit
+ * for bit the row sage_csr_mean_backward_rows stores there for the same
+ * arguments (one copy of that arithmetic serves both entry points).
+ *   num_rows_out[0] = U on every call that launches (0 without a term), also
+ *                     when U > max_rows: the caller sees a short buffer.
+ *   rows_out / grad_rows (a nullable pair; rows_out is required with grad_rows):
+ *                     for u < min(U, max_rows): rows_out[u] = e_u and
+ *                     grad_rows[u, 0:dim] = s_u.  Not written: rows at or past
+ *                     max_rows or U, columns [dim, ldr).
+ *   table (nullable): table[e_u, c] = fma(-lr, s_u[c], table[e_u, c]) for EVERY
+ *                     u < U, whatever max_rows is: one rounding (fmaf).  Rows
+ *                     without a term are neither read nor written; columns
+ *                     [dim, ldt) are not written.
+ * At least one of grad_rows and table; with both, the gradient returned is the
+ * one that was applied.
+ * NOTHING costs time or memory in proportion to num_rows or num_nodes: no grid,
+ * loop, fill or workspace array is sized by them; num_rows enters through the
+ * sort's key bits and the clamp only.  After sage_csr_mean_backward_rows' term
+ * layout and stable sort the run heads of the sorted keys are counted and
+ * scanned into a run list (row, start; at most min(max_edges + n, num_rows)
+ * runs, a host-known capacity), which takes the place of the row pointer over
+ * the table in the chunk split; the row kernel strides over u < U, read on the
+ * device.  No float atomics, no host synchronisation, no allocation.
+ * Any dim >= 1, ldg >= dim, ldr / ldt >= dim where their array is given,
+ * max_rows >= 1 with grad_rows; 16-byte accesses when dim and the leading
+ * dimensions are multiples of 4 and the arrays are 16-byte aligned.
+ * Validation, before any launch, in sage_csr_mean_backward_rows' order: shapes,
+ * then NULL arrays (rowptr, col, nodes, grad_out, num_rows_out; neither
+ * grad_rows nor table; grad_rows without rows_out: SAGE_EINVAL), then the
+ * workspace (short or missing: SAGE_ENOSPACE; 256-byte aligned).  n == 0
+ * returns SAGE_OK without a launch (num_rows_out and *total_terms are then left
+ * as they were).  The size query is host arithmetic, returns 0 for a shape out
+ * of range and one value for every num_rows >= max_edges + n.
+ * ------------------------------------------------------------------------- */
+size_t sage_csr_mean_backward_touched_workspace_bytes(int32_t n, int64_t max_edges, int64_t num_rows, int32_t dim);
+int sage_csr_mean_backward_touched(const int64_t* rowptr, const int32_t* col, int64_t num_nodes,
+                                   const int32_t* nodes, int32_t n, int64_t max_edges,
+                                   const int32_t* index /* nullable */, int64_t num_rows,
+                                   const float* grad_out, int64_t ldg, int32_t dim, int32_t self_loop,
+                                   int32_t* num_rows_out,                         /* [1] device, required                       */
+                                   int32_t* rows_out, float* grad_rows,           /* [max_rows], [max_rows, dim]: nullable pair */
+                                   int64_t max_rows, int64_t ldr,
+                                   float* table, int64_t ldt, float lr,           /* [num_rows, dim] updated in place; nullable */
+                                   int64_t* total_terms /* nullable, device */,
+                                   void* workspace, size_t workspace_bytes, sage_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * sage_csr_sum (additive, ABI 9) -- the gradient of a shared embedding row.
  * aggregators.py:68-71 looks features up in a trainable nn.Embedding: node v
  * reads row index[v] (its own row for 1hot, its degree's row for node_degree),
