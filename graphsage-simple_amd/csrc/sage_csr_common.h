@@ -13,6 +13,7 @@
 #include "sage_internal.h"
 
 #include <algorithm>
+#include <type_traits>
 
 namespace {
 
@@ -22,7 +23,11 @@ constexpr int kCarryThreads = 1024;
 
 size_t align256(size_t x) { return (x + 255) / 256 * 256; }
 
+// Eight columns of a lane: two float4, stored and loaded as such (the bf16 table's 16-byte form, see load_cols).
+struct alignas(16) float8 { float4 lo, hi; };
+
 template <int VEC> struct VecT;
+template <> struct VecT<8> { using type = float8; };
 template <> struct VecT<4> { using type = float4; };
 template <> struct VecT<1> { using type = float; };
 
@@ -36,6 +41,9 @@ __device__ inline void vfma(float4& a, float s, const float4& b) {
     a.x = __builtin_fmaf(s, b.x, a.x); a.y = __builtin_fmaf(s, b.y, a.y); a.z = __builtin_fmaf(s, b.z, a.z); a.w = __builtin_fmaf(s, b.w, a.w);
 }
 __device__ inline void vfma(float& a, float s, const float& b) { a = __builtin_fmaf(s, b, a); }
+__device__ inline void vadd(float8& a, const float8& b) { vadd(a.lo, b.lo); vadd(a.hi, b.hi); }
+__device__ inline float8 vscale(const float8& a, float s) { return float8{vscale(a.lo, s), vscale(a.hi, s)}; }
+__device__ inline void vfill(float8& a, float s) { vfill(a.lo, s); vfill(a.hi, s); }
 
 __device__ inline int64_t uniform64(int64_t x) {
     const uint32_t lo = (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)x);
@@ -234,14 +242,58 @@ __device__ inline V chunked_row_sum(int64_t k, int64_t o, int64_t cap, const flo
     return s;
 }
 
+// The table's element type TT: float, or uint16_t = a bf16 value as its raw 16 bits (sage_csr_mean_bf16).  A bf16 value widens to
+// fp32 EXACTLY (bits << 16), so everything after the load is the fp32 arithmetic on the widened table, bit for bit.  On the vector path
+// a lane keeps its four columns [c0, c0 + 4): a float table gives them as one 16-byte load, a bf16 table as one 8-byte load whose two
+// words each hold two columns, the lower column in the low half (little endian).
+// A load and its widening are two steps, so that a trip's loads are all issued before the first of them is waited for: what is
+// in flight is the RAW value (the 8 bytes), widened only where it is added.
+template <typename V, typename TT> struct RawT { using type = V; };                       // a float table: the columns themselves
+template <> struct RawT<float8, uint16_t> { using type = uint4; };
+template <> struct RawT<float4, uint16_t> { using type = uint2; };
+template <> struct RawT<float, uint16_t> { using type = uint32_t; };
+
+template <typename V, typename TT> __device__ inline typename RawT<V, TT>::type load_raw(const TT* __restrict__ p) {
+    if constexpr (std::is_same_v<TT, float>) return *reinterpret_cast<const V*>(p);
+    else if constexpr (std::is_same_v<V, float>) return (uint32_t)*p;
+    else return *reinterpret_cast<const typename RawT<V, TT>::type*>(p);
+}
+__device__ inline void zero_raw(float8& a) { vfill(a, 0.f); }
+__device__ inline void zero_raw(float4& a) { vfill(a, 0.f); }
+__device__ inline void zero_raw(float& a) { vfill(a, 0.f); }
+__device__ inline void zero_raw(uint4& a) { a = make_uint4(0, 0, 0, 0); }
+__device__ inline void zero_raw(uint2& a) { a = make_uint2(0, 0); }
+__device__ inline void zero_raw(uint32_t& a) { a = 0; }
+
+__device__ inline float4 widen2(uint32_t x, uint32_t y) {
+    return make_float4(__uint_as_float(x << 16), __uint_as_float(x & 0xffff0000u), __uint_as_float(y << 16), __uint_as_float(y & 0xffff0000u));
+}
+template <typename V> __device__ inline V widen(const V& raw) { return raw; }
+template <typename V> __device__ inline V widen(const uint4& w) { return float8{widen2(w.x, w.y), widen2(w.z, w.w)}; }
+template <typename V> __device__ inline V widen(const uint2& w) { return widen2(w.x, w.y); }
+template <typename V> __device__ inline V widen(const uint32_t& w) { return __uint_as_float(w << 16); }
+
+template <typename V, typename TT> __device__ inline V load_cols(const TT* __restrict__ p) { return widen<V>(load_raw<V>(p)); }
+
+// Rows of a trip whose loads are in flight together before the first add.  A bf16 row is half the bytes; measured (DESIGN.md section
+// 9a, configs[2]'s graph, width 256): 8 rows 6.00 ms, 16 rows 5.53, 32 rows 5.34, against 9.76 for the float table's 8 x 16 bytes.
+// The depth never changes the order of a column's additions.
+#ifndef SAGE_CSR_BF16_IN_FLIGHT
+#define SAGE_CSR_BF16_IN_FLIGHT 32
+#endif
+template <typename TT> struct InFlight { static constexpr int rows = 8; };
+template <> struct InFlight<uint16_t> { static constexpr int rows = SAGE_CSR_BF16_IN_FLIGHT; };
+static_assert(kWave % InFlight<uint16_t>::rows == 0, "a wave trip is a whole number of in-flight groups");
+
 // acc += table rows of col[b..e) in stored order (the sage_gather.hip inner loop: ids broadcast by readlane, 8 rows in flight).
 // b, e wave-uniform.  SELF: found |= some entry of the range is node v (compiled out otherwise: v and found are not touched).
 // IDX: the id is a node id, clamped into [0, last_node]; the row read is index[id], clamped into [0, last_row].
-template <int VEC, bool IDX, bool SELF>
-__device__ inline void sum_edges(const int32_t* __restrict__ col, int64_t b, int64_t e, const float* __restrict__ table, int64_t ld,
+template <int VEC, bool IDX, bool SELF, typename TT>
+__device__ inline void sum_edges(const int32_t* __restrict__ col, int64_t b, int64_t e, const TT* __restrict__ table, int64_t ld,
                                  int last_row, int c0, bool ok, int32_t v, typename VecT<VEC>::type& acc, bool& found,
                                  const int32_t* __restrict__ index, int last_node) {
     using V = typename VecT<VEC>::type;
+    constexpr int kRows = InFlight<TT>::rows;
     const int lane = sage_lane();
     for (int64_t base = b; base < e; base += kWave) {
         const int m = (int)min((int64_t)kWave, e - base);
@@ -255,17 +307,17 @@ __device__ inline void sum_edges(const int32_t* __restrict__ col, int64_t b, int
         } else {
             myid = min(max(raw, 0), last_row);           // never read outside the table
         }
-        for (int j0 = 0; j0 < m; j0 += 8) {
-            V t[8];
+        for (int j0 = 0; j0 < m; j0 += kRows) {
+            typename RawT<V, TT>::type t[kRows];
 #pragma unroll
-            for (int u = 0; u < 8; ++u) {
+            for (int u = 0; u < kRows; ++u) {
                 const int id = __builtin_amdgcn_readlane(myid, min(j0 + u, m - 1));
-                if (ok) t[u] = *reinterpret_cast<const V*>(table + (int64_t)id * ld + c0);
-                else vfill(t[u], 0.f);
+                if (ok) t[u] = load_raw<V>(table + (int64_t)id * ld + c0);
+                else zero_raw(t[u]);
             }
 #pragma unroll
-            for (int u = 0; u < 8; ++u)
-                if (j0 + u < m) vadd(acc, t[u]);
+            for (int u = 0; u < kRows; ++u)
+                if (j0 + u < m) vadd(acc, widen<V>(t[u]));
         }
     }
 }

@@ -25,7 +25,15 @@
 // IDX instantiations (sage_csr_mean_indexed): the table is virtual, T[v] = embed[index[v]] (aggregators.py:68-71), and only the
 // ADDRESS of a row changes: the lane that loads col[base + lane] also loads index[] of the clamped id, the self row is read
 // through index[v].  "Row v holds v" is still decided on node ids.  Same chunks, launches, fall-back and order of additions.
+//
+// TT = uint16_t instantiations (sage_csr_mean_bf16): the frozen table is STORED as bf16.  Only the LOAD of a table element changes
+// (load_cols: 8 bytes for a lane's four columns, widened exactly by `<< 16` / `& 0xffff0000`); accumulators, partials and out stay
+// fp32 with the layout above, so the result is the fp32 kernel's on the widened table bit for bit.  No IDX form.
 #include "sage_csr_common.h"
+
+#ifndef SAGE_CSR_BF16_COLS
+#define SAGE_CSR_BF16_COLS 4
+#endif
 
 namespace {
 
@@ -44,9 +52,9 @@ bool csr_layout(int32_t n, int64_t max_edges, int32_t dim, CsrLayout* L) {
 }
 
 // 4. one wave per item (row, chunk): partials[item] := the chunk's sum, has_self[item] := the chunk holds node v
-template <int VEC, bool IDX>
+template <int VEC, bool IDX, typename TT>
 __global__ __launch_bounds__(256) void csr_chunk_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int64_t num_nodes,
-                                                        const int32_t* __restrict__ nodes, int n, const float* __restrict__ table,
+                                                        const int32_t* __restrict__ nodes, int n, const TT* __restrict__ table,
                                                         int table_rows, int64_t ld, int dim, const int64_t* __restrict__ off,
                                                         const int64_t* __restrict__ carry, int nb, int64_t cap,
                                                         const int32_t* __restrict__ item_row, int32_t* __restrict__ has_self,
@@ -75,9 +83,9 @@ __global__ __launch_bounds__(256) void csr_chunk_kernel(const int64_t* __restric
 }
 
 // 5. one wave per row
-template <int VEC, bool IDX>
+template <int VEC, bool IDX, typename TT>
 __global__ __launch_bounds__(256) void csr_row_kernel(const int64_t* __restrict__ rowptr, const int32_t* __restrict__ col, int64_t num_nodes,
-                                                      const int32_t* __restrict__ nodes, int n, const float* __restrict__ table,
+                                                      const int32_t* __restrict__ nodes, int n, const TT* __restrict__ table,
                                                       int table_rows, int64_t ld, int dim, int self_loop,
                                                       const int32_t* __restrict__ any_nonempty, const int64_t* __restrict__ off,
                                                       int64_t cap, const int32_t* __restrict__ has_self,
@@ -115,7 +123,7 @@ __global__ __launch_bounds__(256) void csr_row_kernel(const int64_t* __restrict_
                 int self;                                       // v is in [0, num_nodes) here
                 if constexpr (IDX) self = min(max(__builtin_amdgcn_readfirstlane(index[v]), 0), last_row);
                 else self = min(v, last_row);
-                vadd(s, *reinterpret_cast<const V*>(table + (int64_t)self * ld + c0));
+                vadd(s, load_cols<V>(table + (int64_t)self * ld + c0));
             }
             const int64_t ceff = deg + (extra ? 1 : 0);
             if (ok) {
@@ -135,11 +143,13 @@ extern "C" size_t sage_csr_mean_workspace_bytes(int32_t n, int64_t max_edges, in
     return csr_layout(n, max_edges, dim, &L) ? L.total : 0;
 }
 
-// Both entries: the refusals (shapes first, then pointers, then the workspace: a bad shape is reported as such whatever the pointers
+// All three entries: the refusals (shapes first, then pointers, then the workspace: a bad shape is reported as such whatever the pointers
 // are) under the entry's `name` and its word for the table's rows, then the five launches, for the plain table (index == nullptr,
-// indexed false) and for the virtual one.
+// indexed false) and for the virtual one.  TT = uint16_t: the plain table stored as bf16 (no indexed form: the embedding it would
+// read is trained, and stays fp32); ld counts elements, and the vector path's one load per lane is 8 bytes.
+template <typename TT>
 static int csr_mean_run(const char* name, const char* rows_name, bool indexed, const int64_t* rowptr, const int32_t* col, int64_t num_nodes,
-                        const int32_t* nodes, int32_t n, int64_t max_edges, const int32_t* index, const float* table, int64_t table_rows,
+                        const int32_t* nodes, int32_t n, int64_t max_edges, const int32_t* index, const TT* table, int64_t table_rows,
                         int64_t ld, int32_t dim, int32_t self_loop, const int32_t* any_nonempty, float* out, int64_t ldo, void* workspace,
                         size_t workspace_bytes, sage_stream_t stream) {
     SAGE_REQUIRE(num_nodes >= 0 && num_nodes < (1ll << 31), "%s: num_nodes = %lld", name, (long long)num_nodes);
@@ -158,23 +168,36 @@ static int csr_mean_run(const char* name, const char* rows_name, bool indexed, c
     ChunkPlan P;
     if (const int rc = csr_chunk_plan(rowptr, num_nodes, nodes, n, workspace, L.c, st, &P)) return rc;
     int32_t* has_self = (int32_t*)((char*)workspace + L.has_self);
-    const bool vec4 = (dim % 4 == 0) && (ld % 4 == 0) && (ldo % 4 == 0) && sage_aligned(table, 16) && sage_aligned(out, 16);
+    constexpr bool kIsFloat = std::is_same_v<TT, float>;
+    const bool vec4 = (dim % 4 == 0) && (ld % 4 == 0) && (ldo % 4 == 0) && sage_aligned(table, 4 * sizeof(TT)) && sage_aligned(out, 16);
+    // the bf16 table's 16-byte form, eight columns per lane: built with -DSAGE_CSR_BF16_COLS=8 only (experiments/mb_csr_mean_bf16.py);
+    // it lost to the 8-byte form, so the library holds no such kernel
+    constexpr bool kCols8 = !kIsFloat && SAGE_CSR_BF16_COLS == 8;
+    const bool vec8 = kCols8 && vec4 && (dim % 8 == 0) && (ld % 8 == 0) && sage_aligned(table, 16);
     if (P.cap > 0) {
         const int blocks = (int)std::min<int64_t>((P.cap + 3) / 4, kNumCU * 8);
 #define SAGE_CSR_CHUNK(VEC, IDX)                                                                                                       \
-    hipLaunchKernelGGL((csr_chunk_kernel<VEC, IDX>), dim3(blocks), dim3(256), 0, st, rowptr, col, num_nodes, nodes, n, table, (int)table_rows, \
+    hipLaunchKernelGGL((csr_chunk_kernel<VEC, IDX, TT>), dim3(blocks), dim3(256), 0, st, rowptr, col, num_nodes, nodes, n, table, (int)table_rows, \
                        ld, dim, P.off, P.carry, P.nb, P.cap, P.item_row, has_self, P.partials, index)
-        if (index) { if (vec4) SAGE_CSR_CHUNK(4, true); else SAGE_CSR_CHUNK(1, true); }
-        else { if (vec4) SAGE_CSR_CHUNK(4, false); else SAGE_CSR_CHUNK(1, false); }
+        bool launched = false;
+        if constexpr (kIsFloat)
+            if (index) { if (vec4) SAGE_CSR_CHUNK(4, true); else SAGE_CSR_CHUNK(1, true); launched = true; }
+        if constexpr (kCols8)
+            if (vec8) { SAGE_CSR_CHUNK(8, false); launched = true; }
+        if (!launched) { if (vec4) SAGE_CSR_CHUNK(4, false); else SAGE_CSR_CHUNK(1, false); }
 #undef SAGE_CSR_CHUNK
         SAGE_CHECK_LAUNCH("csr_chunk_kernel");
     }
     const int blocks = std::min(sage_cdiv(n, 4), kNumCU * 8);
 #define SAGE_CSR_ROW(VEC, IDX)                                                                                                            \
-    hipLaunchKernelGGL((csr_row_kernel<VEC, IDX>), dim3(blocks), dim3(256), 0, st, rowptr, col, num_nodes, nodes, n, table, (int)table_rows, ld, \
+    hipLaunchKernelGGL((csr_row_kernel<VEC, IDX, TT>), dim3(blocks), dim3(256), 0, st, rowptr, col, num_nodes, nodes, n, table, (int)table_rows, ld, \
                        dim, self_loop, any_nonempty, P.off, P.cap, has_self, P.partials, out, ldo, index)
-    if (index) { if (vec4) SAGE_CSR_ROW(4, true); else SAGE_CSR_ROW(1, true); }
-    else { if (vec4) SAGE_CSR_ROW(4, false); else SAGE_CSR_ROW(1, false); }
+    bool launched = false;
+    if constexpr (kIsFloat)
+        if (index) { if (vec4) SAGE_CSR_ROW(4, true); else SAGE_CSR_ROW(1, true); launched = true; }
+    if constexpr (kCols8)
+        if (vec8) { SAGE_CSR_ROW(8, false); launched = true; }
+    if (!launched) { if (vec4) SAGE_CSR_ROW(4, false); else SAGE_CSR_ROW(1, false); }
 #undef SAGE_CSR_ROW
     SAGE_CHECK_LAUNCH("csr_row_kernel");
     return SAGE_OK;
@@ -193,5 +216,13 @@ extern "C" int sage_csr_mean_indexed(const int64_t* rowptr, const int32_t* col, 
                                      int32_t self_loop, const int32_t* any_nonempty, float* out, int64_t ldo, void* workspace,
                                      size_t workspace_bytes, sage_stream_t stream) {
     return csr_mean_run("csr_mean_indexed", "embed_rows", true, rowptr, col, num_nodes, nodes, n, max_edges, index, embed, embed_rows, ld, dim,
+                        self_loop, any_nonempty, out, ldo, workspace, workspace_bytes, stream);
+}
+
+extern "C" int sage_csr_mean_bf16(const int64_t* rowptr, const int32_t* col, int64_t num_nodes, const int32_t* nodes, int32_t n,
+                                  int64_t max_edges, const uint16_t* table, int64_t table_rows, int64_t ld, int32_t dim, int32_t self_loop,
+                                  const int32_t* any_nonempty, float* out, int64_t ldo, void* workspace, size_t workspace_bytes,
+                                  sage_stream_t stream) {
+    return csr_mean_run("csr_mean_bf16", "table_rows", false, rowptr, col, num_nodes, nodes, n, max_edges, nullptr, table, table_rows, ld, dim,
                         self_loop, any_nonempty, out, ldo, workspace, workspace_bytes, stream);
 }

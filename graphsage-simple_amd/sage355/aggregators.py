@@ -30,7 +30,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from . import autograd, native
+from . import autograd, native, ops
 
 
 EMBED_INITIALIZERS = ("1hot", "node_degree")     # aggregators.py:30, 68: the feature rows index a trainable embedding
@@ -104,6 +104,7 @@ class MeanAggregator(nn.Module):
         if initializer in EMBED_INITIALIZERS:
             embed_matrix = self._embed_lookup(embed_matrix)
         dev = torch.device("cuda")
+        ops.refuse_bf16(embed_matrix, "sage355.MeanAggregator")
         embed_dev = embed_matrix.to(dev, torch.float32)
         if embed_dev.dim() != 2 or embed_dev.shape[0] != unique_nodes.shape[0]:
             raise native.SageError(f"features returned {tuple(embed_matrix.shape)} for {unique_nodes.shape[0]} ids")

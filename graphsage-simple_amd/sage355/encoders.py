@@ -330,6 +330,9 @@ class Encoder(nn.Module):
         if not torch.cuda.is_available():
             raise native.SageError("sage355.Encoder needs an MI355X; there is no CPU path")
         native.lib()
+        for enc in self._pair():                              # the sampled paths have no bf16 form, and would widen the whole table
+            if enc._is_table():
+                ops.refuse_bf16(enc.features.weight, "sage355.Encoder")
         if not self.cuda:
             _cap_host_threads_once()
         grad = torch.is_grad_enabled()

@@ -13,7 +13,7 @@ from operator import attrgetter
 import torch
 
 from . import native
-from .ops import ACT_RELU, _chk, _need_gpu, _row_major, as_ids
+from .ops import ACT_RELU, _chk, _need_gpu, _row_major, as_ids, refuse_bf16
 
 
 def pretransform_table(table, w1, rows_per_call=1 << 18):
@@ -169,6 +169,7 @@ class TwoHopEngine:
         (col1 = embed_index[col]) and hands that to the library, so the sampled layer-1 sets hold embedding rows and every layer-1
         kernel runs unchanged on the R-row table; frontier, hash and outer hop keep node ids.  gcn encoder without the aggregator's
         self loop only, no relabel, d0 % 4 == 0, never a slice-major copy."""
+        refuse_bf16(table, "TwoHopEngine")          # the sampled engine keeps private fp32 / bf16x3 copies: no bf16 table
         if embed_index is not None:          # before anything touches the device: every refusal is reachable without one
             slice_major = self._check_indexed(rowptr, table, embed_index, concat, agg_self_loop, relabel, slice_major, _parent)
         _need_gpu()
@@ -683,6 +684,7 @@ class RolePipeline:
     def __init__(self, rowptr, col, table, w1, w2, k1, k2, batch, depth=4, roles="SGDL", priorities=None, streams=None, threads=None,
                  window=None, **engine_kwargs):
         self._broken, self._cap_stream = False, None
+        refuse_bf16(table, "RolePipeline")
         if depth < 1 or depth > native.PIPE_MAX_DEPTH:
             raise native.SageError(f"RolePipeline: depth must be in [1, {native.PIPE_MAX_DEPTH}]")
         if len(roles) != 4:

@@ -19,7 +19,7 @@ import torch
 
 from . import dist, ops
 from .head import head_grads, head_predict
-from .fullgraph import embed_arguments
+from .fullgraph import check_table_dtype, embed_arguments
 from .inference import _check_index, _seed_frontier
 from .native import ACT_RELU, SageError
 from .train import _batches, _split, _validation_result, check_trainer_args, csr_pair, init_parameters
@@ -37,7 +37,11 @@ class ExactBatchTrainer:
     gradient is placed with index_copy_, never with an atomic scatter).  An id outside the graph raises.
     Host reads per step: embed_nodes' two (the seeds' outer edge count with their range; |F| with F's inner edge count).
     The trainer owns one persistent ops.CsrFrontier; its map is cleared after the backward has read it, also when a step raises.
-    The frontier's rows are put in ascending id order before layer 1 runs, so two runs of a step give the same bits."""
+    The frontier's rows are put in ascending id order before layer 1 runs, so two runs of a step give the same bits.
+
+    table may be torch.bfloat16, a storage format: the caller rounded it once, layer 1's mean widens it exactly (sage_csr_mean_bf16),
+    and everything a step computes is what it computes on table.float().  The concat encoder widens the frontier's own rows once per
+    step ([|F|, d0] fp32) and hands them to the contraction and its backward as they are, without an index."""
 
     def __init__(self, rowptr, col, table, num_classes, hidden1=50, hidden2=128, gcn=True, lr=0.7, agg_self_loop=False, head="native",
                  rowptr_outer=None, col_outer=None, act1=ACT_RELU):
@@ -45,7 +49,7 @@ class ExactBatchTrainer:
         ops._need_gpu()
         self.rowptr, self.col = rowptr, col
         self.rowptr2, self.col2 = csr_pair(rowptr, col, rowptr_outer, col_outer)
-        table, _ = ops._row_major(table, "table")
+        table, _ = ops._feature_table(table, "table")
         self.n = rowptr.shape[0] - 1
         if self.n < 1 or table.shape[0] < self.n:
             raise SageError(f"ExactBatchTrainer: table has {table.shape[0]} rows for {self.n} nodes")
@@ -72,8 +76,8 @@ class ExactBatchTrainer:
 
     def _forward(self, seeds):
         """The forward of one batch; the frontier's map stays FILLED for the backward (the callers clear it in a finally).
-        -> dict of what the backward reads: the frontier's nodes, the seeds' rows, layer 1's own rows, agg1, h1_F, agg2, out and the two
-        edge counts."""
+        -> dict of what the backward reads: the frontier's nodes, the seeds' rows, layer 1's own rows (self1: their rows of the table;
+        own1, own1_index: what the contraction reads them through), agg1, h1_F, agg2, out and the two edge counts."""
         ops._chk(seeds, torch.int32, "seeds", 1)
         m, fr, who = seeds.shape[0], self.frontier, type(self).__name__
         if m < 1:
@@ -89,11 +93,14 @@ class ExactBatchTrainer:
         tab, index = self._layer1()
         self1 = (f_nodes if index is None else index[f_nodes.long()]) if self.concat else None     # the concat encoder's own rows of tab
         agg1 = ops.csr_mean(self.rowptr, self.col, tab, nodes=f_nodes, self_loop=self.self_loop, max_edges=e1, workspace=ws, index=index)
-        h1_f = ops.linear_act(agg1, self.w1, self.act1, self_tab=tab if self.concat else None, self_index=self1)
+        own1, own1_index = (tab, self1) if self.concat else (None, None)
+        if self.concat and tab.dtype == torch.bfloat16:                # the frontier's own rows, widened once for the forward and the backward
+            own1, own1_index = tab.index_select(0, f_nodes).float(), None
+        h1_f = ops.linear_act(agg1, self.w1, self.act1, self_tab=own1, self_index=own1_index)
         agg2 = ops.csr_mean(self.rowptr2, self.col2, h1_f, nodes=seeds, self_loop=self.self_loop, max_edges=e2, workspace=ws, index=fr.pos)
         rows = fr.pos[seeds.long()] if self.concat else None           # the seeds' rows of h1_F
         out = ops.linear_act(agg2, self.w2, ACT_RELU, self_tab=h1_f if self.concat else None, self_index=rows)
-        return dict(f_nodes=f_nodes, rows=rows, self1=self1, agg1=agg1, h1_f=h1_f, agg2=agg2, out=out, e2=e2, e1=e1)
+        return dict(f_nodes=f_nodes, rows=rows, self1=self1, own1=own1, own1_index=own1_index, agg1=agg1, h1_f=h1_f, agg2=agg2, out=out, e2=e2, e1=e1)
 
     def forward(self, seeds):
         """[len(seeds), h2] embeddings of the nodes `seeds` (int32 on the device; here they may repeat)."""
@@ -110,8 +117,8 @@ class ExactBatchTrainer:
     def _layer1_grads(self, f, g_h1, dw, update):
         """Layer 1's backward over the frontier's rows -> (g_w1, the gradients of further parameters): only dW1 here, the table is
         frozen."""
-        g_w1, _ = ops.linear_act_backward(f["agg1"], self.w1, self.act1, f["h1_f"], g_h1, self_tab=self.table if self.concat else None,
-                                          self_index=f["self1"], need_x=False, workspace=dw)
+        g_w1, _ = ops.linear_act_backward(f["agg1"], self.w1, self.act1, f["h1_f"], g_h1, self_tab=f["own1"], self_index=f["own1_index"],
+                                          need_x=False, workspace=dw)
         return g_w1, ()
 
     def _grads(self, seeds, labels, update=False):
@@ -239,22 +246,25 @@ class ExactBatchEmbedTrainer(ExactBatchTrainer):
 
 
 def run_exact_batch_training(graph, feat_data, labels, num_classes, seed=1, epochs=1, batch_size=128, ref_batching=False, lr=0.7,
-                             hidden1=50, hidden2=128, gcn=True, agg_self_loop=False, head="native", initializer="None", embed_dim=100,
-                             sparse_embed=False):
+                             hidden1=50, hidden2=128, gcn=True, agg_self_loop=False, head="native", table_dtype=torch.float32, initializer="None",
+                             embed_dim=100, sparse_embed=False):
     """run_model (model.py:184-259) with num_sample=None batches: the same split, shuffles, batching and SGD as
     train.run_engine_training, every step through ExactBatchTrainer, validation by its predict (full neighbourhoods as well).
     initializer, embed_dim: run_full_graph_training's -- "None": the frozen table feat_data; "1hot" / "node_degree": a trainable
     embedding through ExactBatchEmbedTrainer (feat_data is not read and may be None), with its sparse_embed.
+    table_dtype: torch.float32, or torch.bfloat16 = the frozen table is rounded to bf16 once and stored so (half its bytes; exact for
+    0/1 features); refused with a trainable embedding, which stays fp32.
     -> dict(f1_micro, f1_macro, mean_step_time, losses, trainer), as train.run_engine_training."""
     dev = torch.device("cuda")
     embed = embed_arguments("run_exact_batch_training", initializer, ("None",), graph, embed_dim, dev)
+    table_dtype = check_table_dtype("run_exact_batch_training", table_dtype, embed is not None)
     if sparse_embed and embed is None:
         raise SageError("run_exact_batch_training: sparse_embed needs initializer '1hot' or 'node_degree': a frozen table has no update")
     rowptr, col = graph.to(dev)
     _, val, train = _split(graph.num_nodes, seed)
     common = dict(hidden1=hidden1, hidden2=hidden2, gcn=gcn, lr=lr, agg_self_loop=agg_self_loop, head=head)
     if embed is None:
-        tr = ExactBatchTrainer(rowptr, col, torch.as_tensor(feat_data, dtype=torch.float32).to(dev), num_classes, **common)
+        tr = ExactBatchTrainer(rowptr, col, torch.as_tensor(feat_data, dtype=torch.float32).to(dev).to(table_dtype), num_classes, **common)
     else:
         tr = ExactBatchEmbedTrainer(rowptr, col, num_classes, sparse_embed=sparse_embed, **embed, **common)
     labels_dev = torch.as_tensor(np.asarray(labels).reshape(-1), dtype=torch.int64).to(dev)

@@ -41,6 +41,10 @@ class FullGraphTrainer:
 
     head: "native" -- one sage_xent_head call; "torch" -- the same expressions as stock torch ops (train.EngineTrainer).
 
+    table may be torch.bfloat16 with gcn=True, a storage format: refresh_table's mean widens it exactly (sage_csr_mean_bf16), the
+    backward never reads the table, and every result is that of table.float() bit for bit.  The concat encoder is refused: its own
+    rows would need the [N, d0] fp32 copy that a bf16 table exists to avoid (ExactBatchTrainer widens a batch's own rows instead).
+
     Trainable embedding: embed_index int32 [N] on the device with values in [0, embed_rows), and table=None.  Layer 1 reads
     X = embed[embed_index] ([N, embed_dim]); self.embed [embed_rows, embed_dim] is drawn N(0, 1) as nn.Embedding's weight is
     (aggregators.py:31), AFTER w1, w2, w_cls -- one torch seed still gives those three the start the frozen-table trainer gives them --
@@ -64,7 +68,10 @@ class FullGraphTrainer:
         self.rowptr2, self.col2 = csr_pair(rowptr, col, rowptr_outer, col_outer)
         self.n = rowptr.shape[0] - 1
         if embed_index is None:
-            table, _ = ops._row_major(table, "table")
+            table, _ = ops._feature_table(table, "table")
+            if table.dtype == torch.bfloat16 and not gcn:
+                raise SageError("FullGraphTrainer: a torch.bfloat16 table with the concat encoder (gcn=False) is not supported: its own rows "
+                                "would need an [N, d0] fp32 copy of the table; use gcn=True, ExactBatchTrainer, or table.float()")
             if self.n < 1 or table.shape[0] < self.n:
                 raise SageError(f"FullGraphTrainer: table has {table.shape[0]} rows for {self.n} nodes")
             dev, d0 = table.device, table.shape[1]
@@ -215,6 +222,15 @@ def degree_index(rowptr):
     return deg.contiguous(), (int(deg.max()) + 1 if deg.numel() else 1)
 
 
+def check_table_dtype(who, table_dtype, trainable_embedding):
+    """The table_dtype argument of a run driver `who`: torch.float32, or torch.bfloat16 for a frozen table only."""
+    if table_dtype not in (torch.float32, torch.bfloat16):
+        raise SageError(f"{who}: table_dtype = {table_dtype!r}, expected torch.float32 or torch.bfloat16")
+    if table_dtype == torch.bfloat16 and trainable_embedding:
+        raise SageError(f"{who}: table_dtype torch.bfloat16 with a trainable embedding: bf16 stores a frozen table, the embedding stays fp32")
+    return table_dtype
+
+
 def embed_arguments(who, initializer, frozen, graph, embed_dim, dev):
     """What a run driver `who` hands its trainer for --initializer (model.py:153-157, 209-212): None for a spelling in `frozen` (the
     frozen feature table), else dict(embed_index, embed_rows, embed_dim, act1) -- "1hot": a row per node, ReLU; "node_degree": a row
@@ -231,7 +247,8 @@ def embed_arguments(who, initializer, frozen, graph, embed_dim, dev):
 
 
 def run_full_graph_training(graph, feat_data, labels, num_classes, seed=1, steps=100, lr=0.7, hidden1=50, hidden2=128, gcn=True,
-                            agg_self_loop=False, head="native", initializer="None", embed_dim=100, fused_embed=False):
+                            agg_self_loop=False, head="native", initializer="None", embed_dim=100, fused_embed=False,
+                            table_dtype=torch.float32):
     """run_model (model.py:184-259) with full neighbourhoods: the same 10 / 10 / 80 split of a seeded numpy permutation
     (model.py:229-235), ONE step per epoch over the whole training set, `steps` epochs.
     initializer: "None" -- the frozen table feat_data, ReLU at both layers; "1hot" -- a trainable embedding row per node, ReLU;
@@ -240,12 +257,15 @@ def run_full_graph_training(graph, feat_data, labels, num_classes, seed=1, steps
     reference itself overrides that width for these two initializers with the one-hot's (N and max degree + 1, model.py:209-212)
     because its loader hands the one-hot in as the feature table: an accident of the loader, not copied here.
     fused_embed: FullGraphTrainer's flag (it changes something for "node_degree" only: the 1hot index is the identity).
+    table_dtype: torch.float32, or torch.bfloat16 = the frozen table is rounded to bf16 once and stored so (gcn=True only; refused
+    with a trainable embedding).
     -> dict(f1_micro, f1_macro, mean_step_time, losses, trainer), as train.run_engine_training."""
     dev = torch.device("cuda")
     embed = embed_arguments("run_full_graph_training", initializer, ("None",), graph, embed_dim, dev)
+    table_dtype = check_table_dtype("run_full_graph_training", table_dtype, embed is not None)
     rowptr, col = graph.to(dev)
     _, val, train = _split(graph.num_nodes, seed)
-    table = torch.as_tensor(feat_data, dtype=torch.float32).to(dev) if embed is None else None
+    table = torch.as_tensor(feat_data, dtype=torch.float32).to(dev).to(table_dtype) if embed is None else None
     tr = FullGraphTrainer(rowptr, col, table, num_classes, hidden1, hidden2, gcn=gcn, lr=lr, agg_self_loop=agg_self_loop, head=head,
                           fused_embed=fused_embed, **(embed or {}))
     labels_dev = torch.as_tensor(np.asarray(labels).reshape(-1), dtype=torch.int64).to(dev)

@@ -6,6 +6,10 @@ then the output layer for all N nodes from h1.  Row r of every result is node r:
 
 Memory: h1 [N, h1] + out [N, h2] + one [rows_per_call, max(d0, h1)] block of means + the csr_mean workspace.
 
+The feature table may be stored as torch.bfloat16 (index=None): layer 1's mean reads it through sage_csr_mean_bf16, which widens each
+element exactly, so every result is that of table.float() bit for bit at half the table's bytes.  The contraction is not touched:
+the concat encoder's own rows are widened in torch, one [rows_per_call, d0] fp32 block at a time.  h1 and every output stay fp32.
+
 embed_nodes is the same computation for a chosen batch of nodes: the frontier of the batch's full neighbourhoods (ops.csr_frontier),
 layer 1 for the frontier only, layer 2 for the batch -- the bits of embed_all_nodes(...)[seeds] in memory proportional to the frontier.
 """
@@ -41,11 +45,15 @@ def layer_all_nodes(rowptr, col, table, weight, concat, self_loop, act, nan_empt
     table [>= N, dim]; weight [out_dim, dim] (gcn) or [out_dim, 2 * dim] (concat: [self | mean]).
     index: int32 [N] on the device, values in [0, K) (checked once per call) -- table is then a [K, dim] embedding and node v's
     row is table[index[v]] (aggregators.py:68-71), read through the index by the mean and by the concat encoder's own row:
-    nothing [N, dim] is allocated, the bits are those of layer_all_nodes(table[index])."""
+    nothing [N, dim] is allocated, the bits are those of layer_all_nodes(table[index]).
+    table may be torch.bfloat16 when index is None: the bits of layer_all_nodes(table.float())."""
     ops._need_gpu()
     ops._chk(rowptr, torch.int64, "rowptr", 1)
     ops._chk(col, torch.int32, "col", 1)
-    table, _ = ops._row_major(table, "table")
+    if index is not None:
+        ops.refuse_bf16(table, "layer_all_nodes(index=)")
+    table, _ = ops._feature_table(table, "table")
+    bf16 = table.dtype == torch.bfloat16
     weight, _ = ops._row_major(weight, "weight")
     n = rowptr.shape[0] - 1
     dim = table.shape[1]
@@ -71,7 +79,8 @@ def layer_all_nodes(rowptr, col, table, weight, concat, self_loop, act, nan_empt
         agg = block[: (r1 - r0) * dim].view(r1 - r0, dim)
         ops.csr_mean(rowptr, col, table, nodes=ids[r0:r1], self_loop=self_loop, any_nonempty=flag, out=agg, workspace=_workspace, index=index)
         if index is None:
-            ops.linear_act(agg, weight, act, self_tab=table[r0:r1] if concat else None, out=out[r0:r1])
+            own = (table[r0:r1].float() if bf16 else table[r0:r1]) if concat else None     # bf16: the block's own rows, widened
+            ops.linear_act(agg, weight, act, self_tab=own, out=out[r0:r1])
         else:
             ops.linear_act(agg, weight, act, self_tab=table if concat else None, self_index=index[r0:r1] if concat else None, out=out[r0:r1])
     return out
@@ -139,14 +148,19 @@ def _seed_frontier(rowptr, rp2, c2, seeds, fr, what):
 
 def _layer_rows(rowptr, col, table, weight, concat, self_loop, act, flag, ids, index, self_rows, out, rows, block, workspace, max_edges):
     """layer_all_nodes' block loop for the rows `ids` instead of all of them: out[r] = the layer's output for node ids[r].
-    self_rows: the concat encoder's own rows of `table`, one per id."""
+    self_rows: the concat encoder's own rows of `table`, one per id.  A bf16 table (index None, so self_rows is ids): the block's own
+    rows are gathered and widened in torch and handed over without an index."""
     dim = table.shape[1]
+    bf16 = table.dtype == torch.bfloat16
     for r0 in range(0, ids.shape[0], rows):
         r1 = min(r0 + rows, ids.shape[0])
         agg = block[: (r1 - r0) * dim].view(r1 - r0, dim)
         ops.csr_mean(rowptr, col, table, nodes=ids[r0:r1], self_loop=self_loop, any_nonempty=flag, out=agg, max_edges=max_edges,
                      workspace=workspace, index=index)
-        ops.linear_act(agg, weight, act, self_tab=table if concat else None, self_index=self_rows[r0:r1] if concat else None, out=out[r0:r1])
+        if concat and bf16:
+            ops.linear_act(agg, weight, act, self_tab=table.index_select(0, ids[r0:r1]).float(), out=out[r0:r1])
+        else:
+            ops.linear_act(agg, weight, act, self_tab=table if concat else None, self_index=self_rows[r0:r1] if concat else None, out=out[r0:r1])
 
 
 def embed_nodes(rowptr, col, table, w1, w2, seeds, concat=False, agg_self_loop=False, act1=ACT_RELU, act2=ACT_RELU, nan_empty=True,
@@ -163,7 +177,9 @@ def embed_nodes(rowptr, col, table, w1, w2, seeds, concat=False, agg_self_loop=F
     again before returning, also when an error follows the kernel.
     Host reads: two per call -- the edge count of the seeds' rows (with the seeds' range), then |F| with F's inner edge count; they
     size the frontier, h1_F and the csr_mean workspaces (never len(col): that would be a workspace for the whole graph).
-    Memory: the map (4 N bytes, or the caller's), h1_F, out, one [rows_per_call, max(d0, h1)] block of means."""
+    Memory: the map (4 N bytes, or the caller's), h1_F, out, one [rows_per_call, max(d0, h1)] block of means.
+    table may be torch.bfloat16 when index is None: the bits of embed_nodes(table.float()); the concat encoder then adds one
+    [rows_per_call, d0] fp32 block of own rows, never an [N, d0] array."""
     ops._need_gpu()
     rp2 = rowptr if rowptr_outer is None else rowptr_outer
     c2 = col if col_outer is None else col_outer
@@ -173,7 +189,9 @@ def embed_nodes(rowptr, col, table, w1, w2, seeds, concat=False, agg_self_loop=F
         raise SageError("inner and outer CSR must cover the same node ids")
     n = rowptr.shape[0] - 1
     mult = 2 if concat else 1
-    table, _ = ops._row_major(table, "table")
+    if index is not None:
+        ops.refuse_bf16(table, "embed_nodes(index=)")
+    table, _ = ops._feature_table(table, "table")
     d0, h1, h2 = table.shape[1], w1.shape[0], w2.shape[0]
     if w1.dim() != 2 or w2.dim() != 2 or w1.shape[1] != mult * d0 or w2.shape[1] != mult * h1:
         raise SageError(f"weight shapes {tuple(w1.shape)}, {tuple(w2.shape)} do not fit d0={d0}, concat={bool(concat)}")
@@ -239,9 +257,12 @@ def _first_one_index(weight, embed_rows, block_elems=1 << 24):
     return index
 
 
-def _stack_arguments(enc2, what):
+def _stack_arguments(enc2, what, table_dtype=torch.float32):
     """What embed_all_from_modules and embed_nodes_from_modules read from a two-layer stack, with their refusals (`what` names the
-    caller in the messages): -> ((rowptr, col, table, w1, w2), keyword arguments) of embed_all_nodes / embed_nodes."""
+    caller in the messages): -> ((rowptr, col, table, w1, w2), keyword arguments) of embed_all_nodes / embed_nodes.
+    table_dtype: torch.float32, or torch.bfloat16 = the feature table is rounded once, here, and read as bf16."""
+    if table_dtype not in (torch.float32, torch.bfloat16):
+        raise SageError(f"{what}: table_dtype {table_dtype}, expected torch.float32 or torch.bfloat16")
     from .aggregators import EMBED_INITIALIZERS, MeanAggregator
     from .encoders import SIGMOID_INITIALIZERS
     from .graph import csr_from_adj_lists
@@ -264,6 +285,8 @@ def _stack_arguments(enc2, what):
             raise SageError(f"{what}: initializer {enc1.initializer!r}, but enc1's aggregator was built without it: no `embed`")
         if not enc1.gcn:
             raise SageError(f"{what}: the concat encoder with the {enc1.initializer!r} initializer is not supported")
+        if table_dtype == torch.bfloat16:
+            raise SageError(f"{what}: table_dtype torch.bfloat16 with the {enc1.initializer!r} initializer: the trained embedding stays fp32")
     if bool(enc1.gcn) != bool(enc2.gcn):
         raise SageError(f"{what}: the two encoders differ in `gcn`")
     agg_gcn = bool(getattr(enc1.aggregator, "gcn", False))
@@ -280,7 +303,10 @@ def _stack_arguments(enc2, what):
             index = _first_one_index(enc1.features.weight, table.shape[0])
             n = index.shape[0]
         else:
-            table = _module_tensor(enc1.features.weight, "enc1.features.weight")
+            if table_dtype == torch.bfloat16:
+                table = enc1.features.weight.detach().to("cuda").to(torch.bfloat16).contiguous()
+            else:
+                table = _module_tensor(enc1.features.weight, "enc1.features.weight")
             n = table.shape[0]
         w1, w2 = _module_tensor(enc1.weight, "enc1.weight"), _module_tensor(enc2.weight, "enc2.weight")
         g1 = csr_from_adj_lists(enc1.adj_lists, num_nodes=n)
@@ -290,7 +316,7 @@ def _stack_arguments(enc2, what):
                                               rowptr_outer=rp2, col_outer=c2, index=index)
 
 
-def embed_all_from_modules(enc2, rows_per_call=ROWS_PER_CALL):
+def embed_all_from_modules(enc2, rows_per_call=ROWS_PER_CALL, table_dtype=torch.float32):
     """embed_all_nodes on a trained two-layer stack as model.py:214-222 wires it (this package's Encoder / MeanAggregator, or
     the reference's classes of the same shape): enc1 = enc2.base_model over an nn.Embedding feature table.  Reads the table,
     both `weight` Parameters, the encoders' `gcn` flag, the aggregators' `gcn` flag, the activations (the initializer rule)
@@ -300,13 +326,15 @@ def embed_all_from_modules(enc2, rows_per_call=ROWS_PER_CALL):
     is read through it (embed_all_nodes(index=...)), and nothing [N, embed_dim] is built.  Refused: a row without a 1, an index
     past the embedding's rows, an aggregator without `embed`, the concat encoder with such an initializer (the reference feeds
     the raw one-hot as the own row there, fullgraph.py), and such an initializer on enc2.
+    table_dtype=torch.bfloat16: enc1.features.weight is rounded to bf16 once per call and layer 1 reads that (embed_all_nodes);
+    refused with the embedding initializers.
     Anything else raises SageError."""
-    args, kwargs = _stack_arguments(enc2, "embed_all_from_modules")
+    args, kwargs = _stack_arguments(enc2, "embed_all_from_modules", table_dtype)
     return embed_all_nodes(*args, rows_per_call=rows_per_call, **kwargs)
 
 
-def embed_nodes_from_modules(enc2, nodes, rows_per_call=ROWS_PER_CALL):
+def embed_nodes_from_modules(enc2, nodes, rows_per_call=ROWS_PER_CALL, table_dtype=torch.float32):
     """embed_nodes on the stack embed_all_from_modules takes, with its argument extraction and its refusals:
     -> device tensor [len(nodes), h2], row r = node nodes[r], the bits of embed_all_from_modules(enc2)[nodes]."""
-    args, kwargs = _stack_arguments(enc2, "embed_nodes_from_modules")
+    args, kwargs = _stack_arguments(enc2, "embed_nodes_from_modules", table_dtype)
     return embed_nodes(*args, nodes, rows_per_call=rows_per_call, **kwargs)

@@ -44,6 +44,7 @@ SYMBOLS = [
     "sage_csr_frontier_workspace_bytes", "sage_csr_frontier", "sage_csr_frontier_clear",
     "sage_csr_mean_backward_rows_workspace_bytes", "sage_csr_mean_backward_rows",
     "sage_csr_mean_backward_touched_workspace_bytes", "sage_csr_mean_backward_touched",
+    "sage_csr_mean_bf16",
 ]
 PIPE_MAX_DEPTH = 8
 
@@ -182,6 +183,7 @@ def lib():
     L.sage_csr_mean_backward_touched_workspace_bytes.argtypes = [I32, I64, I64, I32]
     L.sage_csr_mean_backward_touched.argtypes = [P, P, I64, P, I32, I64, P, I64, P, I64, I32, I32, P, P, P, I64, I64, P, I64, c_float, P,
                                                  P, c_size_t, P]
+    L.sage_csr_mean_bf16.argtypes = L.sage_csr_mean.argtypes
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name == "sage_prepared_weight_bytes" or name.endswith("_workspace_bytes"):

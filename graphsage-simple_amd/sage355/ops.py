@@ -38,6 +38,23 @@ def _row_major(t, name):
     return t, (t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1))
 
 
+def _feature_table(t, name):
+    """The frozen feature table of the full-neighbourhood mean: 2-d fp32 or bf16 (a storage format: sage_csr_mean_bf16), unit inner
+    stride; returns (tensor, leading dimension in elements).  Everything else stays with _row_major: fp32 only."""
+    if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2:
+        if t.stride(1) != 1 and t.shape[1] > 1:
+            raise native.SageError(f"{name}: inner stride must be 1")
+        return t, (t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1))
+    return _row_major(t, name)
+
+
+def refuse_bf16(t, who):
+    """A path that has no bf16 form says so by name, instead of failing on whatever reads the table first."""
+    if isinstance(t, torch.Tensor) and t.dtype == torch.bfloat16:
+        raise native.SageError(f"{who}: a torch.bfloat16 table is not supported here (bf16 is a storage format of the frozen table of the "
+                               "full-neighbourhood mean: ops.csr_mean, inference, ExactBatchTrainer, FullGraphTrainer(gcn=True)); pass table.float()")
+
+
 def check_id_range(ids64, num_nodes, what="node ids"):
     """Host-side range check of ids that arrived from the host (numpy int64 array).  The reference fails safely for a
     bad id (IndexError from the nn.Embedding lookup, encoders.py:50 / aggregators.py:65); a device kernel would read
@@ -330,11 +347,15 @@ def csr_mean(rowptr, col, table, nodes=None, self_loop=False, any_nonempty=None,
     len(col) (exact for distinct rows; a smaller bound only costs speed).  workspace: a uint8 device tensor to reuse.
     index: int32 [num_nodes] on the device -- `table` is then a [K, dim] embedding and node v's row is table[index[v]]
     (aggregators.py:68-71; sage_csr_mean_indexed): the bits of csr_mean(table[index]) without that [num_nodes, dim] array.  An
-    index value outside [0, K) is clamped, not refused: check the index where it is built."""
+    index value outside [0, K) is clamped, not refused: check the index where it is built.
+    table may be torch.bfloat16 (sage_csr_mean_bf16; not with index=): the caller rounded it once, the kernel widens each element
+    exactly and sums in fp32, so the result is csr_mean(table.float()) bit for bit at half the table bytes; out stays fp32."""
     _need_gpu()
     _chk(rowptr, torch.int64, "rowptr", 1)
     _chk(col, torch.int32, "col", 1)
-    table, ld = _row_major(table, "table")
+    if index is not None:
+        refuse_bf16(table, "csr_mean(index=): the embedding is trained and stays fp32")
+    table, ld = _feature_table(table, "table")
     num_nodes = rowptr.shape[0] - 1
     if num_nodes < 0:
         raise native.SageError("csr_mean: rowptr is empty")
@@ -374,10 +395,12 @@ def csr_mean(rowptr, col, table, nodes=None, self_loop=False, any_nonempty=None,
                                                 native.stream_handle())
         native.check(rc, "csr_mean_indexed")
         return out
-    rc = native.lib().sage_csr_mean(native.ptr(rowptr), native.ptr(col), num_nodes, native.ptr(nodes), n, max_edges,
-                                    native.ptr(table), table.shape[0], ld, dim, 1 if self_loop else 0, native.ptr(any_nonempty),
-                                    native.ptr(out), ldo, native.ptr(workspace), workspace.numel(), native.stream_handle())
-    native.check(rc, "csr_mean")
+    bf16 = table.dtype == torch.bfloat16
+    entry = native.lib().sage_csr_mean_bf16 if bf16 else native.lib().sage_csr_mean
+    rc = entry(native.ptr(rowptr), native.ptr(col), num_nodes, native.ptr(nodes), n, max_edges,
+               native.ptr(table), table.shape[0], ld, dim, 1 if self_loop else 0, native.ptr(any_nonempty),
+               native.ptr(out), ldo, native.ptr(workspace), workspace.numel(), native.stream_handle())
+    native.check(rc, "csr_mean_bf16" if bf16 else "csr_mean")
     return out
 
 

@@ -165,6 +165,8 @@ def check_trainer_args(who, head, act1, hidden2, num_classes, table=None, embed_
         raise native.SageError(f"{who}: head = {head!r}, expected 'torch' or 'native'")
     if act1 not in (ACT_RELU, ACT_SIGMOID):
         raise native.SageError(f"{who}: act1 = {act1!r}, expected ACT_RELU or ACT_SIGMOID")
+    if embed_index is not None:
+        ops.refuse_bf16(table, f"{who}(embed_index=)")
     if embed_index is not None and table is not None:
         raise native.SageError(f"{who}: table and embed_index are alternatives: layer 1 reads one of them")
     if embed_index is not None and (embed_rows is None or embed_dim is None or int(embed_rows) < 1 or int(embed_dim) < 1):
@@ -242,6 +244,7 @@ class EngineTrainer:
         native head the loss and the classifier gradient that grads() returns live in buffers of the trainer, rewritten by its next call."""
         from . import native, ops
         check_trainer_args("EngineTrainer", head, act1, hidden2, num_classes, table, embed_index, embed_rows, embed_dim)
+        ops.refuse_bf16(table, "EngineTrainer")
         if sparse_embed and embed_index is None:
             raise native.SageError("EngineTrainer: sparse_embed needs embed_index: a frozen table has no update to make sparse")
         if embed_index is not None and dist.world_size() > 1:

@@ -211,6 +211,33 @@ int sage_csr_mean_indexed(const int64_t* rowptr, const int32_t* col, int64_t num
                           float* out, int64_t ldo, void* workspace, size_t workspace_bytes, sage_stream_t stream);
 
 /* ---------------------------------------------------------------------------
+ * sage_csr_mean_bf16 (additive, ABI 9) -- sage_csr_mean (aggregators.py:47-48
+ * with num_sample=None, then aggregators.py:52-74) over a frozen feature
+ * table STORED as bf16: table holds the raw 16 bits of each value, ld counts
+ * elements.  bf16 is a storage format and nothing else: the caller rounds
+ * once (round to nearest even), the kernel widens every element exactly
+ * (bits << 16) and accumulates in fp32 in sage_csr_mean's order, so with
+ * T32[i, j] = the fp32 value of table[i, j] the result is
+ *     sage_csr_mean(table = T32) BIT FOR BIT, NaN results included (where
+ *     two NaNs of DIFFERENT payloads meet in one addition, which payload the
+ *     NaN result carries is defined by neither entry):
+ * the same chunks of SAGE_CSR_MEAN_CHUNK entries, the same launches, the same
+ * fall-back for a small max_edges, the same self term and any_nonempty rule.
+ * Partials and out are fp32; the workspace is sage_csr_mean_workspace_bytes.
+ * A lane's four columns are one 8-byte load when dim, ld and ldo are
+ * multiples of 4, table is 8-byte and out 16-byte aligned; otherwise one
+ * 2-byte load per column.  Every clamp, every other argument and the order of
+ * validation are sage_csr_mean's, under the name csr_mean_bf16.  There is no
+ * indexed form: the embedding sage_csr_mean_indexed reads is trained and
+ * stays fp32.
+ * ------------------------------------------------------------------------- */
+int sage_csr_mean_bf16(const int64_t* rowptr, const int32_t* col, int64_t num_nodes,
+                       const int32_t* nodes /* nullable: row r is node r */, int32_t n, int64_t max_edges,
+                       const uint16_t* table /* bf16 bits */, int64_t table_rows, int64_t ld, int32_t dim,
+                       int32_t self_loop, const int32_t* any_nonempty /* nullable */,
+                       float* out, int64_t ldo, void* workspace, size_t workspace_bytes, sage_stream_t stream);
+
+/* ---------------------------------------------------------------------------
  * sage_csr_frontier (additive, ABI 9) -- the frontier of a FULL-neighbourhood
  * hop: aggregators.py:47-53 with num_sample=None, `samp_neighs = to_neighs`
  * (+ the node itself), `unique_nodes_list = list(set.union(*samp_neighs))` and
