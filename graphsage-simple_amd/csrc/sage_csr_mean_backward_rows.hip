@@ -30,7 +30,8 @@ namespace {
 
 // What steps a-i of both entries need of a workspace.  It serves either self_loop, so it holds max_edges + n term positions.
 struct TermsWs {
-    size_t w, found, local, carry, estart, tstart, keys_in, keys_out, vals_in, vals_out, cub, cub_bytes;
+    size_t w, found, local, carry, estart, tstart;
+    SortPairsWs pairs;
     int64_t slots;       // term positions the workspace holds (at least 1)
     int64_t nblocks;     // count-kernel blocks over the seed rows
 };
@@ -45,12 +46,7 @@ bool terms_ws(int32_t n, int64_t max_edges, int64_t num_rows, int32_t dim, WsCur
     T->carry = cur.take((size_t)(T->nblocks + 1) * 8);
     T->estart = cur.take((size_t)(n + 1) * 8);
     T->tstart = cur.take((size_t)(n + 1) * 8);
-    T->keys_in = cur.take((size_t)T->slots * 4);
-    T->keys_out = cur.take((size_t)T->slots * 4);
-    T->vals_in = cur.take((size_t)T->slots * 4);
-    T->vals_out = cur.take((size_t)T->slots * 4);
-    T->cub_bytes = sort_temp_reserve(T->slots);
-    T->cub = cur.take(T->cub_bytes);
+    T->pairs.take(T->slots, cur);
     return true;
 }
 
@@ -73,20 +69,16 @@ bool rows_bwd_layout(int32_t n, int64_t max_edges, int64_t num_rows, int32_t dim
 // num_rows >= max_edges + n nothing here depends on num_rows.
 struct TouchedLayout {
     TermsWs t;
-    size_t run_row, runptr, heads, end_pos, total;
+    RunListWs r;
+    size_t total;
     ChunkWs c;
-    int64_t runs_cap;
 };
 
 bool touched_layout(int32_t n, int64_t max_edges, int64_t num_rows, int32_t dim, TouchedLayout* L) {
     WsCursor cur;
     if (!terms_ws(n, max_edges, num_rows, dim, cur, &L->t)) return false;
-    L->runs_cap = std::min<int64_t>(max_edges + n, num_rows);      // distinct rows with a term: what every array below is sized by
-    L->run_row = cur.take((size_t)L->runs_cap * 4);
-    L->runptr = cur.take((size_t)(L->runs_cap + 1) * 8);
-    L->heads = cur.take((size_t)(run_head_blocks(L->t.slots) + 1) * 8);
-    L->end_pos = cur.take(8);
-    if (!chunk_ws(L->runs_cap, L->t.slots, dim, cur, &L->c)) return false;
+    L->r.take(L->t.slots, std::min<int64_t>(max_edges + n, num_rows), cur);   // distinct rows with a term: what every array below is sized by
+    if (!chunk_ws(L->r.runs_cap, L->t.slots, dim, cur, &L->c)) return false;
     L->total = cur.off;
     return true;
 }
@@ -223,19 +215,11 @@ int rows_sort_terms(const char* name, const TermsArgs& a, void* workspace, const
     int64_t* carry = (int64_t*)(ws + L.carry);
     int64_t* estart = (int64_t*)(ws + L.estart);
     int64_t* tstart = (int64_t*)(ws + L.tstart);
-    int32_t* keys_in = (int32_t*)(ws + L.keys_in);
-    int32_t* keys_out = (int32_t*)(ws + L.keys_out);
-    int32_t* vals_in = (int32_t*)(ws + L.vals_in);
-    int32_t* vals_out = (int32_t*)(ws + L.vals_out);
     const int n = a.n, R = (int)a.num_rows;
     const int64_t capacity = a.max_edges + (a.self_loop ? n : 0);
     const int64_t slots = std::max<int64_t>(capacity, 1);         // <= L.slots
     const int bits = sort_key_bits(a.num_rows);
-    size_t sort_bytes = 0;
-    if (sort_temp_bytes((int)slots, bits, &sort_bytes) != hipSuccess || sort_bytes > L.cub_bytes) {
-        sage_set_error("%s: the radix sort asks for %zu bytes of temporary, %zu reserved", name, sort_bytes, L.cub_bytes);
-        return SAGE_ELAUNCH;
-    }
+    if (const int rc = sort_temp_check(name, (int)slots, bits, L.pairs)) return rc;
 
     const int nb = (int)L.nblocks;
     const int entry_blocks = (int)std::min<int64_t>(std::max<int64_t>((a.max_edges / kChunk + 4) / 4, 1), kNumCU * 8);
@@ -264,15 +248,10 @@ int rows_sort_terms(const char* name, const TermsArgs& a, void* workspace, const
 
     const int term_blocks = (int)std::min<int64_t>(std::max<int64_t>((slots / kChunk + 4) / 4, 1), kNumCU * 8);
     hipLaunchKernelGGL(rows_layout_kernel, dim3(term_blocks), dim3(256), 0, st, a.rowptr, a.col, a.num_nodes, a.nodes, n, (const int64_t*)tstart,
-                       a.index, R, slots, capacity, keys_in, vals_in);
+                       a.index, R, slots, capacity, L.pairs.keys(ws), L.pairs.vals(ws));
     SAGE_CHECK_LAUNCH("rows_layout_kernel");
-    size_t cub_bytes = L.cub_bytes;
-    if (hipcub::DeviceRadixSort::SortPairs(ws + L.cub, cub_bytes, (const int32_t*)keys_in, keys_out, (const int32_t*)vals_in, vals_out, (int)slots, 0,
-                                           bits, st) != hipSuccess) {
-        sage_set_error("%s: radix sort failed", name);
-        return SAGE_ELAUNCH;
-    }
-    *T = SortedTerms{keys_out, vals_out, w, slots};
+    if (const int rc = sort_pairs(name, ws, L.pairs, (int)slots, bits, st)) return rc;
+    *T = SortedTerms{L.pairs.sorted_keys(ws), L.pairs.sorted_vals(ws), w, slots};
     return SAGE_OK;
 }
 
@@ -310,7 +289,7 @@ extern "C" int sage_csr_mean_backward_rows(const int64_t* rowptr, const int32_t*
 
     if (n == 0) {                                        // no term: every row of grad_table is stored as zeros
         char* ws = (char*)workspace;
-        const BwdSum sum{rowptr_f, (const int32_t*)(ws + L.t.vals_out), num_rows, true, nullptr, R, (const float*)(ws + L.t.w), nullptr, n, grad_out, ldg, dim,
+        const BwdSum sum{rowptr_f, L.t.pairs.sorted_vals(ws), num_rows, true, nullptr, R, (const float*)(ws + L.t.w), nullptr, n, grad_out, ldg, dim,
                          grad_table, ldgt};
         if (const int rc = sage_fill_u32(rowptr_f, 0u, (size_t)(num_rows + 1) * 2, st)) return rc;
         if (total_terms)
@@ -359,29 +338,24 @@ extern "C" int sage_csr_mean_backward_touched(const int64_t* rowptr, const int32
     if (n == 0) return SAGE_OK;                          // no term, no launch: num_rows_out and *total_terms are left as they were
 
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    int32_t* run_row = (int32_t*)(ws + L.run_row);
-    int64_t* runptr = (int64_t*)(ws + L.runptr);
-    int64_t* heads = (int64_t*)(ws + L.heads);
-    int64_t* end_pos = (int64_t*)(ws + L.end_pos);
-    const int R = (int)num_rows, C = (int)L.runs_cap;
+    const int R = (int)num_rows, C = (int)L.r.runs_cap;
     SortedTerms T;
     const TermsArgs args{rowptr, col, num_nodes, nodes, n, max_edges, index, num_rows, self_loop, total_terms};
     if (const int rc = rows_sort_terms("csr_mean_backward_touched", args, workspace, L.t, st, &T)) return rc;
-    // j'. the run list of the sorted keys: at most C runs, heads[hb] = U
-    const int hb = (int)run_head_blocks(T.slots);
-    if (const int rc = sorted_run_list(T.keys, (int)T.slots, R, L.runs_cap, heads, run_row, runptr, end_pos, num_rows_out, st)) return rc;
+    // j'. the run list of the sorted keys: at most C runs, *U.num_runs of them
+    RunList U;
+    if (const int rc = sorted_run_list(T.keys, (int)T.slots, R, L.r, workspace, num_rows_out, st, &U)) return rc;
     // 1-4. the family's chunk plan and chunk pass with the run list as the row pointer; 5'. the row pass over the runs
     const bool vec4 = (dim % 4 == 0) && (ldg % 4 == 0) && sage_aligned(grad_out, 16) && (!grad_rows || (ldr % 4 == 0 && sage_aligned(grad_rows, 16))) &&
                       (!table || (ldt % 4 == 0 && sage_aligned(table, 16)));
-    const BwdSum sum{runptr, T.vals, L.runs_cap, true, nullptr, C, T.w, nullptr, n, grad_out, ldg, dim, nullptr, 0};
+    const BwdSum sum{U.runptr, T.vals, L.r.runs_cap, true, nullptr, C, T.w, nullptr, n, grad_out, ldg, dim, nullptr, 0};
     ChunkPlan P;
     if (const int rc = bwd_chunk_launch(sum, vec4, workspace, L.c, st, &P)) return rc;
-    const int blocks = (int)std::min<int64_t>(sage_cdiv(L.runs_cap, 4), kNumCU * 8);
+    const int blocks = (int)std::min<int64_t>(sage_cdiv(L.r.runs_cap, 4), kNumCU * 8);
 #define SAGE_BWD_RUNS(VEC)                                                                                                                  \
-    hipLaunchKernelGGL((bwd_runs_row_kernel<VEC>), dim3(blocks), dim3(256), 0, st, (const int64_t*)runptr, T.vals, C, (const int64_t*)(heads + hb), \
-                       T.w, grad_out, ldg, dim, (const int64_t*)P.off, P.cap, (const float*)P.partials, (int64_t)n, (const int32_t*)run_row,       \
-                       rows_out, grad_rows, max_rows, ldr, table, ldt, R, lr)
+    hipLaunchKernelGGL((bwd_runs_row_kernel<VEC>), dim3(blocks), dim3(256), 0, st, U.runptr, T.vals, C, U.num_runs, T.w, grad_out, ldg, dim, \
+                       (const int64_t*)P.off, P.cap, (const float*)P.partials, (int64_t)n, U.run_row, rows_out, grad_rows, max_rows, ldr,   \
+                       table, ldt, R, lr)
     if (vec4) SAGE_BWD_RUNS(4);
     else SAGE_BWD_RUNS(1);
 #undef SAGE_BWD_RUNS

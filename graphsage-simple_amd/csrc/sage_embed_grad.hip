@@ -26,8 +26,8 @@ namespace {
 
 // What both entry points need to lay the terms out and sort them.
 struct SortWs {
-    size_t keys_in, keys_out, vals_in, vals_out, inv_c, cub;
-    size_t cub_bytes;
+    SortPairsWs pairs;
+    size_t inv_c;
     int slots, bits;
 };
 
@@ -35,18 +35,8 @@ bool sort_ws(int32_t n, int32_t k, int64_t embed_rows, int32_t dim, WsCursor& cu
     if (n < 1 || k < 1 || dim < 1 || embed_rows < 1 || embed_rows >= (1ll << 31) || (int64_t)n * k >= (1ll << 31)) return false;
     S->slots = n * k;
     S->bits = sort_key_bits(embed_rows);                           // keys are in [0, embed_rows] (the sentinel included)
-    S->keys_in = cur.take((size_t)S->slots * 4);
-    S->keys_out = cur.take((size_t)S->slots * 4);
-    S->vals_in = cur.take((size_t)S->slots * 4);
-    S->vals_out = cur.take((size_t)S->slots * 4);
+    S->pairs.take(S->slots, cur);
     S->inv_c = cur.take((size_t)n * 4);
-    // The sort's temporary.  The library's own size query asks the runtime for the device's architecture, so it answers only where
-    // there is a device; the layout has to be host arithmetic.  Reserved here is a bound on what the sort partitions its temporary
-    // into: a second key and value array (8 bytes per slot), one look-back word per digit (256) and block of at least 512 slots
-    // (at most 4 bytes per slot at 8 bytes a word), digit histograms of a few KiB.  sort_terms asks the library before it sorts
-    // and refuses (SAGE_ELAUNCH, nothing sorted) if it ever wanted more.
-    S->cub_bytes = sort_temp_reserve(S->slots);
-    S->cub = cur.take(S->cub_bytes);
     return true;
 }
 
@@ -177,21 +167,16 @@ __global__ __launch_bounds__(256) void embed_row_kernel(const float* __restrict_
 // expand / chunk kernels above walk it as they walk a CSR of runs_cap = min(slots, embed_rows) rows.
 struct RowsLayout {
     SortWs s;
-    size_t run_row, runptr, heads, end_pos, total;
+    RunListWs r;
+    size_t total;
     ChunkWs c;
-    int64_t head_blocks, runs_cap;
 };
 
 bool rows_layout(int32_t n, int32_t k, int64_t embed_rows, int32_t dim, RowsLayout* L) {
     WsCursor cur;
     if (!sort_ws(n, k, embed_rows, dim, cur, &L->s)) return false;
-    L->runs_cap = std::min<int64_t>(L->s.slots, embed_rows);       // distinct rows with a term: what every array below is sized by
-    L->head_blocks = run_head_blocks(L->s.slots);
-    L->run_row = cur.take((size_t)L->runs_cap * 4);
-    L->runptr = cur.take((size_t)(L->runs_cap + 1) * 8);
-    L->heads = cur.take((size_t)(L->head_blocks + 1) * 8);
-    L->end_pos = cur.take(8);
-    if (!chunk_ws(L->runs_cap, L->s.slots, dim, cur, &L->c)) return false;
+    L->r.take(L->s.slots, std::min<int64_t>(L->s.slots, embed_rows), cur);     // distinct rows with a term: what every array below is sized by
+    if (!chunk_ws(L->r.runs_cap, L->s.slots, dim, cur, &L->c)) return false;
     L->total = cur.off;
     return true;
 }
@@ -242,27 +227,13 @@ struct SortedTerms {
 // Steps 1-2 of both entry points, errors under the entry's `name`: the sort's temporary is checked before anything is launched.
 int sort_terms(const char* name, const int32_t* nbr, const int32_t* cnt, int32_t k, int32_t n, const int32_t* n_dev, const int32_t* row_order,
                int embed_rows, void* workspace, const SortWs& S, hipStream_t st, SortedTerms* T) {
-    char* ws = (char*)workspace;
-    int32_t* keys_in = (int32_t*)(ws + S.keys_in);
-    int32_t* keys_out = (int32_t*)(ws + S.keys_out);
-    int32_t* vals_in = (int32_t*)(ws + S.vals_in);
-    int32_t* vals_out = (int32_t*)(ws + S.vals_out);
-    float* inv_c = (float*)(ws + S.inv_c);
-    size_t sort_bytes = 0;
-    if (sort_temp_bytes(S.slots, S.bits, &sort_bytes) != hipSuccess || sort_bytes > S.cub_bytes) {
-        sage_set_error("%s: the radix sort asks for %zu bytes of temporary, %zu reserved", name, sort_bytes, S.cub_bytes);
-        return SAGE_ELAUNCH;
-    }
-    hipLaunchKernelGGL(embed_expand_kernel, dim3(sage_cdiv(S.slots, 256)), dim3(256), 0, st, nbr, cnt, k, n, n_dev, row_order, embed_rows, keys_in,
-                       vals_in, inv_c);
+    float* inv_c = (float*)((char*)workspace + S.inv_c);
+    if (const int rc = sort_temp_check(name, S.slots, S.bits, S.pairs)) return rc;
+    hipLaunchKernelGGL(embed_expand_kernel, dim3(sage_cdiv(S.slots, 256)), dim3(256), 0, st, nbr, cnt, k, n, n_dev, row_order, embed_rows,
+                       S.pairs.keys(workspace), S.pairs.vals(workspace), inv_c);
     SAGE_CHECK_LAUNCH("embed_expand_kernel");
-    size_t cub_bytes = S.cub_bytes;
-    if (hipcub::DeviceRadixSort::SortPairs(ws + S.cub, cub_bytes, (const int32_t*)keys_in, keys_out, (const int32_t*)vals_in, vals_out, S.slots, 0,
-                                           S.bits, st) != hipSuccess) {
-        sage_set_error("%s: radix sort failed", name);
-        return SAGE_ELAUNCH;
-    }
-    *T = SortedTerms{keys_out, vals_out, inv_c};
+    if (const int rc = sort_pairs(name, workspace, S.pairs, S.slots, S.bits, st)) return rc;
+    *T = SortedTerms{S.pairs.sorted_keys(workspace), S.pairs.sorted_vals(workspace), inv_c};
     return SAGE_OK;
 }
 
@@ -361,24 +332,19 @@ extern "C" int sage_embed_grad_rows(const float* grad_agg, int64_t ldg, int32_t 
                  (long long)embed_rows, dim);
     if (const int rc = csr_workspace_check("embed_grad_rows", workspace, workspace_bytes, L.total)) return rc;
     hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)workspace;
-    int32_t* run_row = (int32_t*)(ws + L.run_row);
-    int64_t* runptr = (int64_t*)(ws + L.runptr);
-    int64_t* heads = (int64_t*)(ws + L.heads);
-    int64_t* end_pos = (int64_t*)(ws + L.end_pos);
-    const int R = (int)embed_rows, C = (int)L.runs_cap, hb = (int)L.head_blocks;
+    const int R = (int)embed_rows, C = (int)L.r.runs_cap;
     SortedTerms T;
     if (const int rc = sort_terms("embed_grad_rows", nbr, cnt, k, n, n_dev, row_order, R, workspace, L.s, st, &T)) return rc;
     // the run list (sage_sorted_terms.h): count the heads per tile, scan the tiles, write the runs, close the list
-    if (const int rc = sorted_run_list(T.keys, L.s.slots, R, L.runs_cap, heads, run_row, runptr, end_pos, num_rows_out, st)) return rc;
+    RunList U;
+    if (const int rc = sorted_run_list(T.keys, L.s.slots, R, L.r, workspace, num_rows_out, st, &U)) return rc;
     // the chunk split over the runs: sage_embed_grad's launches with the run list as the row pointer
     ChunkPlan P;
-    if (const int rc = chunk_pass(grad_agg, ldg, dim, T, runptr, C, workspace, L.c, st, &P)) return rc;
+    if (const int rc = chunk_pass(grad_agg, ldg, dim, T, U.runptr, C, workspace, L.c, st, &P)) return rc;
     const int lg = lane_group(dim);
-    const int blocks = (int)std::min<int64_t>((L.runs_cap * lg + 255) / 256, kNumCU * 8);
-    SAGE_EMBED_LG(embed_runs_row_kernel, blocks, grad_agg, ldg, dim, T.vals, T.inv_c, (const int64_t*)runptr, C, (const int64_t*)(heads + hb),
-                  (const int64_t*)P.off, P.cap, (const float*)P.partials, (const int32_t*)run_row, rows_out, grad_rows, max_rows, ldr, embed, lde, R,
-                  lr);
+    const int blocks = (int)std::min<int64_t>((L.r.runs_cap * lg + 255) / 256, kNumCU * 8);
+    SAGE_EMBED_LG(embed_runs_row_kernel, blocks, grad_agg, ldg, dim, T.vals, T.inv_c, U.runptr, C, U.num_runs, (const int64_t*)P.off, P.cap,
+                  (const float*)P.partials, U.run_row, rows_out, grad_rows, max_rows, ldr, embed, lde, R, lr);
 #undef SAGE_EMBED_LG
     SAGE_CHECK_LAUNCH("embed_runs_row_kernel");
     return SAGE_OK;

@@ -21,15 +21,7 @@ class _GatherMean(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_out):
         nbr, cnt, slot_rows, self_row = ctx.saved_tensors
-        rows, dim = ctx.table_shape
-        grad_out = grad_out.contiguous()
-        grad_table = torch.zeros((rows, dim), dtype=torch.float32, device=grad_out.device)
-        n, k = nbr.shape
-        rc = native.lib().sage_gather_mean_backward(
-            native.ptr(grad_out), grad_out.stride(0), dim, native.ptr(nbr), native.ptr(cnt), k, n, None,
-            native.ptr(slot_rows), native.ptr(self_row), native.ptr(grad_table), rows, grad_table.stride(0),
-            native.stream_handle())
-        native.check(rc, "gather_mean_backward")
+        grad_table = ops.gather_mean_backward(grad_out.contiguous(), nbr, cnt, ctx.table_shape[0], slot_rows=slot_rows, self_row=self_row)
         return grad_table, None, None, None, None, None
 
 

@@ -504,9 +504,9 @@ class TwoHopEngine:
         no gradient reaches it.  No host synchronisation: the frontier size never leaves the device.
         need_embed (an indexed engine only; a plain one raises): -> (g_w1, g_w2, g_embed), g_embed [R, d0] the dense gradient of the
         embedding, every row stored: g_h1 by the mean's backward over (row2, cnt2) -- (seed, slot) order -- then layer 1's grad_x on the
-        kept means, then sage_embed_grad over (nbr1, cnt1) in sage_row_order's order of s1_nodes: no atomics, the bits do not depend
+        kept means, then ops.embed_grad over (nbr1, cnt1) in ops.row_order's order of s1_nodes: no atomics, the bits do not depend
         on where the frontier's rows sit.  The weight gradients come from the same calls with or without it.
-        need_embed="rows": -> (g_w1, g_w2, (rows, num_rows, grad_rows)), the gradient of the TOUCHED rows only (sage_embed_grad_rows):
+        need_embed="rows": -> (g_w1, g_w2, (rows, num_rows, grad_rows)), the gradient of the TOUCHED rows only (ops.embed_grad_rows):
         num_rows int32 [1] on the device, rows int32 [cap] ascending, grad_rows [cap, d0] the very bits need_embed=True stores in those
         rows, cap = min(max_s1 * k1, R); the buffers are the engine's, allocated on first use and rewritten by the next call.  With
         embed_lr=<float> the same call also applies embed[rows] = fma(-embed_lr, grad_rows, embed[rows]) to the engine's embedding.
@@ -599,13 +599,10 @@ class TwoHopEngine:
         #    the entry point takes no workspace)
         _, g_agg1 = ops.linear_act_backward(agg1, w1p, self.act1, h1, g_h1, n_dev=sc["nlive"], need_w=False)
         # 3. the frontier's rows by ascending node id, 4. the chunked sum over the sampled sets, which hold embedding rows
-        wso = scratch("ws_order", lib.sage_row_order_workspace_bytes(n1))
-        native.check(lib.sage_row_order(P(s1_nodes), n1, P(sc["nlive"]), 0, P(order), P(wso), wso.numel(), st), "row_order")
+        ops.row_order(s1_nodes, n_dev=sc["nlive"], out=order, workspace=scratch("ws_order", ops.row_order_workspace_bytes(n1)))
         if need_embed not in ("rows", "update"):
-            g_embed = torch.empty(rows, d0p, device=dev)
-            wse = scratch("ws_embed", lib.sage_embed_grad_workspace_bytes(n1, k1, rows, d0p))
-            native.check(lib.sage_embed_grad(P(g_agg1), d0p, d0p, P(nbr1), P(cnt1), k1, n1, P(sc["nlive"]), P(order), P(g_embed), rows, d0p,
-                                             P(wse), wse.numel(), st), "embed_grad")
+            g_embed = ops.embed_grad(g_agg1, nbr1, cnt1, rows, n_dev=sc["nlive"], row_order=order, out=torch.empty(rows, d0p, device=dev),
+                                     workspace=scratch("ws_embed", ops.embed_grad_workspace_bytes(n1, k1, rows, d0p)))
             return g_w1, g_w2, g_embed
         # the touched rows only: the compact gradient and / or the update of the embedding in place, nothing sized by R
         cap = min(n1 * k1, rows)
@@ -618,10 +615,9 @@ class TwoHopEngine:
                 sc["grad_rows"] = torch.empty(cap, d0p, device=dev)
             rows_t, grad_t = sc["rows"], sc["grad_rows"]
         embed = self.table if embed_lr is not None else None                # the caller's tensor itself (an indexed engine reads it in place)
-        wsr = scratch("ws_embed_rows", lib.sage_embed_grad_rows_workspace_bytes(n1, k1, rows, d0p))
-        native.check(lib.sage_embed_grad_rows(P(g_agg1), d0p, d0p, P(nbr1), P(cnt1), k1, n1, P(sc["nlive"]), P(order), rows, P(sc["num_rows"]),
-                                              P(rows_t), P(grad_t), cap, d0p, P(embed), self.table_ld, float(embed_lr or 0.0),
-                                              P(wsr), wsr.numel(), st), "embed_grad_rows")
+        ops.embed_grad_rows(g_agg1, nbr1, cnt1, rows, n_dev=sc["nlive"], row_order=order, max_rows=cap, embed=embed, lr=embed_lr,
+                            want_grad=need_embed == "rows", out=(rows_t, sc["num_rows"], grad_t),
+                            workspace=scratch("ws_embed_rows", ops.embed_grad_rows_workspace_bytes(n1, k1, rows, d0p)))
         if embed is not None:
             # the write went past torch: move the version counter as `embed.add_()` would, for everything keyed on it (RolePipeline's
             # _weights_key: join, fork behind this stream).  The engine itself holds no copy of an indexed table to refresh

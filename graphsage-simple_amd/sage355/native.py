@@ -203,8 +203,13 @@ def check(rc, what=""):
 
 
 def ptr(t):
-    """Device pointer of a tensor (None -> NULL)."""
-    return None if t is None else c_void_p(t.data_ptr())
+    """Device pointer of a tensor (None -> NULL).  The only way a tensor becomes a pointer of a library call: host memory is refused
+    here, whatever the wrapper checked -- a kernel that walks a host address can take the whole GPU node down."""
+    if t is None:
+        return None
+    if not t.is_cuda:
+        raise SageError(f"native.ptr: a {tuple(t.shape)} {t.dtype} tensor on {t.device}, not on a GPU")
+    return c_void_p(t.data_ptr())
 
 
 def stream_handle():

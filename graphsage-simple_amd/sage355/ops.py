@@ -29,9 +29,9 @@ def _chk(t, dtype, name, dims=None):
     return t
 
 
-def _row_major(t, name):
-    """2-d fp32, unit inner stride; returns (tensor, leading dimension)."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 2:
+def _row_major(t, name, dtypes=(torch.float32,)):
+    """2-d, unit inner stride, fp32 unless the caller allows more; returns (tensor, leading dimension in elements)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype not in dtypes or t.dim() != 2:
         raise native.SageError(f"{name}: expected a 2-d fp32 device tensor")
     if t.stride(1) != 1 and t.shape[1] > 1:
         raise native.SageError(f"{name}: inner stride must be 1")
@@ -39,13 +39,75 @@ def _row_major(t, name):
 
 
 def _feature_table(t, name):
-    """The frozen feature table of the full-neighbourhood mean: 2-d fp32 or bf16 (a storage format: sage_csr_mean_bf16), unit inner
-    stride; returns (tensor, leading dimension in elements).  Everything else stays with _row_major: fp32 only."""
-    if isinstance(t, torch.Tensor) and t.is_cuda and t.dtype == torch.bfloat16 and t.dim() == 2:
-        if t.stride(1) != 1 and t.shape[1] > 1:
-            raise native.SageError(f"{name}: inner stride must be 1")
-        return t, (t.stride(0) if t.shape[0] > 1 else max(t.shape[1], 1))
-    return _row_major(t, name)
+    """The frozen feature table of the full-neighbourhood mean: fp32 or bf16 (a storage format: sage_csr_mean_bf16).  Everything
+    else stays fp32 only."""
+    return _row_major(t, name, (torch.float32, torch.bfloat16))
+
+
+def _opt_i32(t, name, dims=None, min_len=None):
+    """An optional int32 side array (n_dev, any_nonempty, slot_rows, self_row, self_index, self_nodes): None passes through."""
+    if t is not None:
+        _chk(t, torch.int32, name, dims)
+        if min_len is not None and t.numel() < min_len:
+            raise native.SageError(f"{name}: {t.numel()} entries, expected at least {min_len}")
+    return t
+
+
+def _sets(who, nbr, cnt, n_dev=None, slot_rows=None, self_row=None, any_nonempty=None):
+    """The sampled sets of n rows (nbr int32 [n, k], cnt int32 [n]) and the side arrays that go with them; returns (n, k)."""
+    _chk(nbr, torch.int32, "nbr", 2)
+    _chk(cnt, torch.int32, "cnt", 1)
+    n, k = nbr.shape
+    if cnt.shape[0] < n:
+        raise native.SageError(f"{who}: cnt has {cnt.shape[0]} entries for {n} sets")
+    _opt_i32(n_dev, "n_dev", min_len=1)
+    _opt_i32(slot_rows, "slot_rows", 1)
+    _opt_i32(self_row, "self_row", 1, n)
+    _opt_i32(any_nonempty, "any_nonempty", min_len=1)
+    return n, k
+
+
+def _graph(who, rowptr, col, rowptr_name="rowptr", col_name="col"):
+    """The CSR pair every graph operator takes: rowptr int64 [rows + 1], col int32; returns the number of rows."""
+    _chk(rowptr, torch.int64, rowptr_name, 1)
+    _chk(col, torch.int32, col_name, 1)
+    if rowptr.shape[0] < 1:
+        raise native.SageError(f"{who}: {rowptr_name} is empty")
+    return rowptr.shape[0] - 1
+
+
+def _out_rows(who, out, rows, dim, device):
+    """`out` of an operator that stores [rows, dim] fp32: a fresh one, or the caller's (row-major, at least `rows` rows, `dim`
+    columns); returns (out, leading dimension)."""
+    if out is None:
+        out = torch.empty((rows, dim), dtype=torch.float32, device=device)
+    out, ld = _row_major(out, "out")
+    if out.shape[0] < rows or out.shape[1] != dim:
+        raise native.SageError(f"{who}: out is {tuple(out.shape)}, expected ({rows}, {dim})")
+    return out, ld
+
+
+def _is_workspace(t, device):
+    return isinstance(t, torch.Tensor) and t.dtype == torch.uint8 and t.device == device and t.is_contiguous()
+
+
+def _workspace(who, need, workspace, device, shape):
+    """The workspace of a call that needs `need` bytes (0: `shape`, the caller's words for its sizes, is out of range): the caller's
+    uint8 tensor on `device` when it is large enough, else a fresh one -- trainers hand every call one shared buffer that may be short."""
+    if need == 0:
+        raise native.SageError(f"{who}: {shape} out of range")
+    if workspace is not None and not _is_workspace(workspace, device):
+        raise native.SageError(f"{who}: workspace must be a uint8 tensor on {device}")
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty(need, dtype=torch.uint8, device=device)
+    return workspace
+
+
+def _nonempty(t):
+    """An empty tensor may have no storage address: the kernels read none of it, so zeros with one row (one element) stand in."""
+    if t is None or t.numel() > 0:
+        return t
+    return torch.zeros([max(s, 1) for s in t.shape], dtype=t.dtype, device=t.device)
 
 
 def refuse_bf16(t, who):
@@ -59,11 +121,26 @@ def check_id_range(ids64, num_nodes, what="node ids"):
     """Host-side range check of ids that arrived from the host (numpy int64 array).  The reference fails safely for a
     bad id (IndexError from the nn.Embedding lookup, encoders.py:50 / aggregators.py:65); a device kernel would read
     rowptr[] out of bounds, so the check happens here, BEFORE the int32 cast can wrap a large id into range."""
-    if num_nodes is None or ids64.size == 0:
+    if num_nodes is not None:
+        _in_range(what, "id", ids64, int(num_nodes))
+
+
+def _in_range(who, what, values, k):
+    """Every value (a numpy array or a tensor) inside [0, k), or SageError.  Host reads: for ids that come from the host and for
+    what is built once per graph, never for a per-step wrapper."""
+    if (values.numel() if isinstance(values, torch.Tensor) else values.size) == 0:
         return
-    lo, hi = int(ids64.min()), int(ids64.max())
-    if lo < 0 or hi >= int(num_nodes):
-        raise native.SageError(f"{what}: id {lo if lo < 0 else hi} outside [0, {int(num_nodes)})")
+    lo, hi = int(values.min()), int(values.max())
+    if lo < 0 or hi >= k:
+        raise native.SageError(f"{who}: {what} {lo if lo < 0 else hi} outside [0, {k})")
+
+
+def _group_rowptr(keys, k):
+    """int64 [k + 1]: the row pointer of k groups over entries sorted by their int64 group `keys` (bincount, cumsum)."""
+    rowptr = torch.zeros(k + 1, dtype=torch.int64, device=keys.device)
+    if k > 0 and keys.numel() > 0:
+        rowptr[1:] = torch.cumsum(torch.bincount(keys, minlength=k), 0)
+    return rowptr
 
 
 def as_ids(nodes, device, num_nodes=None):
@@ -115,9 +192,10 @@ class Frontier:
 def _sample(entry, rowptr, col, nodes, k, seed, tag, n_dev, frontier, insert_self, any_nonempty, out_nbr, out_cnt):
     """Body of the two sampler wrappers: `entry` names the C entry point (same argument list)."""
     _need_gpu()
-    _chk(rowptr, torch.int64, "rowptr", 1)
-    _chk(col, torch.int32, "col", 1)
+    num_nodes = _graph(entry, rowptr, col)
     _chk(nodes, torch.int32, "nodes", 1)
+    _opt_i32(n_dev, "n_dev", min_len=1)
+    _opt_i32(any_nonempty, "any_nonempty", min_len=1)
     n = nodes.shape[0]
     dev = nodes.device
     nbr = torch.empty((n, k), dtype=torch.int32, device=dev) if out_nbr is None else _chk(out_nbr, torch.int32, "out_nbr")
@@ -127,7 +205,7 @@ def _sample(entry, rowptr, col, nodes, k, seed, tag, n_dev, frontier, insert_sel
     nbr_slot = torch.empty((n, k), dtype=torch.int32, device=dev) if frontier is not None else None
     self_slot = torch.empty(n, dtype=torch.int32, device=dev) if (frontier is not None and insert_self) else None
     rc = getattr(native.lib(), "sage_" + entry)(
-        native.ptr(rowptr), native.ptr(col), rowptr.shape[0] - 1, native.ptr(nodes), n, native.ptr(n_dev), int(k),
+        native.ptr(rowptr), native.ptr(col), num_nodes, native.ptr(nodes), n, native.ptr(n_dev), int(k),
         int(seed) & 0xFFFFFFFFFFFFFFFF, int(tag), native.ptr(nbr), native.ptr(cnt), native.ptr(any_nonempty),
         frontier.c if frontier is not None else None, 1 if insert_self else 0, native.ptr(nbr_slot),
         native.ptr(self_slot), native.stream_handle())
@@ -158,9 +236,8 @@ def sample_neighbors_any(rowptr, col, nodes, k, seed, tag=TAG_OUTER, n_dev=None,
 
 def frontier_insert(nbr, cnt, frontier, self_nodes=None, n_dev=None):
     _need_gpu()
-    _chk(nbr, torch.int32, "nbr", 2)
-    _chk(cnt, torch.int32, "cnt", 1)
-    n, k = nbr.shape
+    n, k = _sets("frontier_insert", nbr, cnt, n_dev)
+    _opt_i32(self_nodes, "self_nodes", 1, n)
     nbr_slot = torch.empty_like(nbr)
     self_slot = torch.empty(n, dtype=torch.int32, device=nbr.device) if self_nodes is not None else None
     rc = native.lib().sage_frontier_insert(native.ptr(nbr), native.ptr(cnt), k, native.ptr(self_nodes), n,
@@ -174,13 +251,9 @@ def gather_mean(table, nbr, cnt, slot_rows=None, self_row=None, any_nonempty=Non
     """aggregators.py:54-74 -> [n, dim] mean of the gathered rows."""
     _need_gpu()
     table, ld = _row_major(table, "table")
-    _chk(nbr, torch.int32, "nbr", 2)
-    _chk(cnt, torch.int32, "cnt", 1)
-    n, k = nbr.shape
+    n, k = _sets("gather_mean", nbr, cnt, n_dev, slot_rows, self_row, any_nonempty)
     dim = table.shape[1]
-    if out is None:
-        out = torch.empty((n, dim), dtype=torch.float32, device=table.device)
-    out, ldo = _row_major(out, "out")
+    out, ldo = _out_rows("gather_mean", out, n, dim, table.device)
     rc = native.lib().sage_gather_mean(native.ptr(table), table.shape[0], ld, dim, native.ptr(nbr), native.ptr(cnt), k, n,
                                        native.ptr(n_dev), native.ptr(slot_rows), native.ptr(self_row),
                                        native.ptr(any_nonempty), native.ptr(out), ldo, native.stream_handle())
@@ -188,23 +261,50 @@ def gather_mean(table, nbr, cnt, slot_rows=None, self_row=None, any_nonempty=Non
     return out
 
 
+def gather_mean_backward(grad_out, nbr, cnt, table_rows, slot_rows=None, self_row=None, n_dev=None, out=None):
+    """The adjoint of gather_mean with respect to its table, [table_rows, dim], by fp32 atomic scatter (sage_gather_mean_backward:
+    the order of additions is not fixed; the engine's reproducible form is sage_gather_mean_backward_ws).  grad_out [n, dim] = d loss /
+    d gather_mean's result; nbr, cnt, slot_rows, self_row as the forward took them.  ACCUMULATES into out (zeros when absent)."""
+    _need_gpu()
+    grad_out, ldg = _row_major(grad_out, "grad_out")
+    n, k = _sets("gather_mean_backward", nbr, cnt, n_dev, slot_rows, self_row)
+    rows, dim = int(table_rows), grad_out.shape[1]
+    if grad_out.shape[0] < n:
+        raise native.SageError(f"gather_mean_backward: grad_out has {grad_out.shape[0]} rows for {n} sets")
+    if out is None:
+        out = torch.zeros((rows, dim), dtype=torch.float32, device=grad_out.device)
+    out, ld = _out_rows("gather_mean_backward", out, rows, dim, grad_out.device)
+    rc = native.lib().sage_gather_mean_backward(native.ptr(grad_out), ldg, dim, native.ptr(nbr), native.ptr(cnt), k, n, native.ptr(n_dev),
+                                                native.ptr(slot_rows), native.ptr(self_row), native.ptr(out), rows, ld,
+                                                native.stream_handle())
+    native.check(rc, "gather_mean_backward")
+    return out
+
+
+def _linear_inputs(who, agg, weight, self_tab, self_index, n_dev):
+    """What linear_act and its backward read: agg [n, dim], weight [out_dim, dim | 2 dim] over [self | agg], self_tab [*, dim] and the
+    int32 arrays; returns the leading dimensions (agg, weight, self_tab or 0)."""
+    _, ld_agg = _row_major(agg, "agg")
+    _, ldw = _row_major(weight, "weight")
+    n, dim = agg.shape
+    ld_self = 0
+    if self_tab is not None:
+        _, ld_self = _row_major(self_tab, "self_tab")
+        if self_tab.shape[1] != dim:
+            raise native.SageError(f"{who}: self_tab width != agg width")
+    if weight.shape[1] != dim * (2 if self_tab is not None else 1):
+        raise native.SageError(f"{who}: weight is {tuple(weight.shape)}, inputs are {dim} wide")
+    _opt_i32(self_index, "self_index", 1, n)
+    _opt_i32(n_dev, "n_dev", min_len=1)
+    return ld_agg, ldw, ld_self
+
+
 def linear_act(agg, weight, act=ACT_RELU, self_tab=None, self_index=None, n_dev=None, out=None):
     """encoders.py:49-62 -> [n, out_dim] (the module hands out the transpose view)."""
     _need_gpu()
-    agg, ld_agg = _row_major(agg, "agg")
-    weight, ldw = _row_major(weight, "weight")
-    n, dim = agg.shape
-    out_dim = weight.shape[0]
-    ld_self = 0
-    if self_tab is not None:
-        self_tab, ld_self = _row_major(self_tab, "self_tab")
-        if self_tab.shape[1] != dim:
-            raise native.SageError("linear_act: self_tab width != agg width")
-    if weight.shape[1] != dim * (2 if self_tab is not None else 1):
-        raise native.SageError(f"linear_act: weight is {tuple(weight.shape)}, inputs are {dim} wide")
-    if out is None:
-        out = torch.empty((n, out_dim), dtype=torch.float32, device=agg.device)
-    out, ldo = _row_major(out, "out")
+    ld_agg, ldw, ld_self = _linear_inputs("linear_act", agg, weight, self_tab, self_index, n_dev)
+    (n, dim), out_dim = agg.shape, weight.shape[0]
+    out, ldo = _out_rows("linear_act", out, n, out_dim, agg.device)
     rc = native.lib().sage_linear_act(native.ptr(self_tab), ld_self, native.ptr(self_index), native.ptr(agg), ld_agg, dim,
                                       native.ptr(weight), ldw, out_dim, int(act), n, native.ptr(n_dev), native.ptr(out),
                                       ldo, native.stream_handle())
@@ -224,19 +324,24 @@ def linear_act_backward(agg, weight, act, out, grad_out, self_tab=None, self_ind
     d loss / d [self | agg].  The reproducible entry point (sage_linear_act_backward_ws): the partial tiles of grad_w go through a
     workspace and are added in a fixed order, no float atomics.  workspace: a uint8 device tensor to use when it is large enough."""
     _need_gpu()
+    ld_agg, ldw, ld_self = _linear_inputs("linear_act_backward", agg, weight, self_tab, self_index, n_dev)
     n, dim = agg.shape
     out_dim, kw = weight.shape
+    lds = []
+    for t, name in ((out, "out"), (grad_out, "grad_out")):
+        lds.append(_row_major(t, name)[1])
+        if t.shape[0] < n or t.shape[1] < out_dim:
+            raise native.SageError(f"linear_act_backward: {name} is {tuple(t.shape)}, expected at least ({n}, {out_dim})")
     grad_w = torch.zeros_like(weight) if need_w else None
     grad_x = torch.empty((n, kw), dtype=torch.float32, device=agg.device) if need_x else None
     ws = None
     if need_w:
         need = max(256, linear_act_backward_workspace_bytes(n, dim, self_tab is not None, out_dim))
-        ws = workspace if workspace is not None and workspace.numel() >= need else torch.empty(need, dtype=torch.uint8, device=agg.device)
+        ws = _workspace("linear_act_backward", need, workspace, agg.device, "")
     P = native.ptr
     rc = native.lib().sage_linear_act_backward_ws(
-        P(self_tab), self_tab.stride(0) if self_tab is not None else 0, P(self_index), P(agg), agg.stride(0), dim,
-        P(weight), weight.stride(0), out_dim, int(act), P(out), out.stride(0), P(grad_out), grad_out.stride(0), n, P(n_dev),
-        P(grad_w), grad_w.stride(0) if need_w else 0, P(grad_x), kw if need_x else 0, None,
+        P(self_tab), ld_self, P(self_index), P(agg), ld_agg, dim, P(weight), ldw, out_dim, int(act), P(out), lds[0], P(grad_out), lds[1],
+        n, P(n_dev), P(grad_w), grad_w.stride(0) if need_w else 0, P(grad_x), kw if need_x else 0, None,
         P(ws), ws.numel() if need_w else 0, native.stream_handle())
     native.check(rc, "linear_act_backward")
     return grad_w, grad_x
@@ -266,16 +371,13 @@ def layer_forward(table, nbr, cnt, weight, act=ACT_RELU, concat=False, self_inde
     _need_gpu()
     table, ld = _row_major(table, "table")
     weight, ldw = _row_major(weight, "weight")
-    _chk(nbr, torch.int32, "nbr", 2)
-    _chk(cnt, torch.int32, "cnt", 1)
-    n, k = nbr.shape
+    n, k = _sets("layer_forward", nbr, cnt, n_dev, slot_rows, self_row, any_nonempty)
+    _opt_i32(self_index, "self_index", 1, n)
     dim = table.shape[1]
     out_dim = weight.shape[0]
     if weight.shape[1] != dim * (2 if concat else 1):
         raise native.SageError(f"layer_forward: weight is {tuple(weight.shape)}, table is {dim} wide")
-    if out is None:
-        out = torch.empty((n, out_dim), dtype=torch.float32, device=table.device)
-    out, ldo = _row_major(out, "out")
+    out, ldo = _out_rows("layer_forward", out, n, out_dim, table.device)
     rc = native.lib().sage_layer_forward(native.ptr(table), table.shape[0], ld, dim, native.ptr(nbr), native.ptr(cnt), k, n,
                                          native.ptr(n_dev), native.ptr(slot_rows), native.ptr(self_row),
                                          native.ptr(any_nonempty), 1 if concat else 0, native.ptr(self_index),
@@ -314,21 +416,20 @@ def layer1_fused_supported(dim, out_dim, k):
 def layer1_fused(table_sliced, nbr, cnt, weight, act=ACT_RELU, self_row=None, any_nonempty=None, n_dev=None, out=None, prepared=None):
     """The gcn encoder's layer 1 in one phase-sliced launch on a slice-major table float[D / 32][N][32] (sage_layer1_fused)."""
     _need_gpu()
-    if not (table_sliced.dim() == 3 and table_sliced.shape[2] == 32 and table_sliced.is_contiguous() and table_sliced.dtype == torch.float32):
-        raise native.SageError("layer1_fused: table_sliced must be a contiguous fp32 [D / 32, N, 32] tensor")
+    if not (isinstance(table_sliced, torch.Tensor) and table_sliced.is_cuda and table_sliced.dim() == 3 and table_sliced.shape[2] == 32
+            and table_sliced.is_contiguous() and table_sliced.dtype == torch.float32):
+        raise native.SageError("layer1_fused: table_sliced must be a contiguous fp32 [D / 32, N, 32] device tensor")
     weight, ldw = _row_major(weight, "weight")
-    _chk(nbr, torch.int32, "nbr", 2)
-    _chk(cnt, torch.int32, "cnt", 1)
-    n, k = nbr.shape
+    n, k = _sets("layer1_fused", nbr, cnt, n_dev, None, self_row, any_nonempty)
     dim, rows = table_sliced.shape[0] * 32, table_sliced.shape[1]
     out_dim = weight.shape[0]
     if weight.shape[1] != dim:
         raise native.SageError(f"layer1_fused: weight is {tuple(weight.shape)}, table is {dim} wide")
     if prepared is None:
         prepared = prepare_weights(weight)
-    if out is None:
-        out = torch.empty((n, out_dim), dtype=torch.float32, device=table_sliced.device)
-    out, ldo = _row_major(out, "out")
+    elif not _is_workspace(prepared, weight.device):
+        raise native.SageError("layer1_fused: prepared must be what prepare_weights returns for this weight")
+    out, ldo = _out_rows("layer1_fused", out, n, out_dim, table_sliced.device)
     rc = native.lib().sage_layer1_fused(native.ptr(table_sliced), rows, dim, native.ptr(nbr), native.ptr(cnt), k, n, native.ptr(n_dev),
                                         native.ptr(self_row), native.ptr(any_nonempty), native.ptr(weight), ldw, native.ptr(prepared),
                                         out_dim, int(act), native.ptr(out), ldo, native.stream_handle())
@@ -351,14 +452,10 @@ def csr_mean(rowptr, col, table, nodes=None, self_loop=False, any_nonempty=None,
     table may be torch.bfloat16 (sage_csr_mean_bf16; not with index=): the caller rounded it once, the kernel widens each element
     exactly and sums in fp32, so the result is csr_mean(table.float()) bit for bit at half the table bytes; out stays fp32."""
     _need_gpu()
-    _chk(rowptr, torch.int64, "rowptr", 1)
-    _chk(col, torch.int32, "col", 1)
+    num_nodes = _graph("csr_mean", rowptr, col)
     if index is not None:
         refuse_bf16(table, "csr_mean(index=): the embedding is trained and stays fp32")
     table, ld = _feature_table(table, "table")
-    num_nodes = rowptr.shape[0] - 1
-    if num_nodes < 0:
-        raise native.SageError("csr_mean: rowptr is empty")
     if index is not None:
         _chk(index, torch.int32, "index", 1)
         if index.shape[0] != num_nodes or table.shape[0] < 1:
@@ -369,38 +466,24 @@ def csr_mean(rowptr, col, table, nodes=None, self_loop=False, any_nonempty=None,
         _chk(nodes, torch.int32, "nodes", 1)
     n = num_nodes if nodes is None else nodes.shape[0]
     dim = table.shape[1]
-    if out is None:
-        out = torch.empty((n, dim), dtype=torch.float32, device=table.device)
-    out, ldo = _row_major(out, "out")
-    if out.shape[0] < n or out.shape[1] != dim:
-        raise native.SageError(f"csr_mean: out is {tuple(out.shape)}, expected ({n}, {dim})")
-    if any_nonempty is not None:
-        _chk(any_nonempty, torch.int32, "any_nonempty")
+    out, ldo = _out_rows("csr_mean", out, n, dim, table.device)
+    _opt_i32(any_nonempty, "any_nonempty", min_len=1)
     if n == 0:
         return out
-    if col.numel() == 0:                                  # an empty tensor may have no storage address: the kernels read none of it
-        col = torch.zeros(1, dtype=torch.int32, device=table.device)
+    col, index = _nonempty(col), _nonempty(index)
     max_edges = col.numel() if max_edges is None else int(max_edges)
-    need = csr_mean_workspace_bytes(n, max_edges, dim)
-    if need == 0:
-        raise native.SageError(f"csr_mean: n = {n}, max_edges = {max_edges}, dim = {dim} out of range")
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=table.device)
+    workspace = _workspace("csr_mean", csr_mean_workspace_bytes(n, max_edges, dim), workspace, table.device,
+                           f"n = {n}, max_edges = {max_edges}, dim = {dim}")
+    lib, P = native.lib(), native.ptr
+    graph = (P(rowptr), P(col), num_nodes, P(nodes), n, max_edges)
+    rest = (P(table), table.shape[0], ld, dim, 1 if self_loop else 0, P(any_nonempty), P(out), ldo, P(workspace), workspace.numel(),
+            native.stream_handle())
     if index is not None:
-        if index.numel() == 0:
-            index = torch.zeros(1, dtype=torch.int32, device=table.device)
-        rc = native.lib().sage_csr_mean_indexed(native.ptr(rowptr), native.ptr(col), num_nodes, native.ptr(nodes), n, max_edges,
-                                                native.ptr(index), native.ptr(table), table.shape[0], ld, dim, 1 if self_loop else 0,
-                                                native.ptr(any_nonempty), native.ptr(out), ldo, native.ptr(workspace), workspace.numel(),
-                                                native.stream_handle())
-        native.check(rc, "csr_mean_indexed")
-        return out
-    bf16 = table.dtype == torch.bfloat16
-    entry = native.lib().sage_csr_mean_bf16 if bf16 else native.lib().sage_csr_mean
-    rc = entry(native.ptr(rowptr), native.ptr(col), num_nodes, native.ptr(nodes), n, max_edges,
-               native.ptr(table), table.shape[0], ld, dim, 1 if self_loop else 0, native.ptr(any_nonempty),
-               native.ptr(out), ldo, native.ptr(workspace), workspace.numel(), native.stream_handle())
-    native.check(rc, "csr_mean_bf16" if bf16 else "csr_mean")
+        native.check(lib.sage_csr_mean_indexed(*graph, P(index), *rest), "csr_mean_indexed")
+    elif table.dtype == torch.bfloat16:
+        native.check(lib.sage_csr_mean_bf16(*graph, *rest), "csr_mean_bf16")
+    else:
+        native.check(lib.sage_csr_mean(*graph, *rest), "csr_mean")
     return out
 
 
@@ -462,26 +545,20 @@ def csr_frontier(rowptr, col, seeds, frontier, max_edges=None):
     frontier.pos[id] = its row.  max_edges: upper bound on the edges of the seeds' rows, default len(col) (a smaller bound only costs
     speed).  Nothing is read back: frontier.size() is the host read, and a size above frontier.max_nodes means the set did not fit."""
     _need_gpu()
-    _chk(rowptr, torch.int64, "rowptr", 1)
-    _chk(col, torch.int32, "col", 1)
+    num_nodes = _graph("csr_frontier", rowptr, col)
     _chk(seeds, torch.int32, "seeds", 1)
     if not isinstance(frontier, CsrFrontier):
         raise native.SageError("csr_frontier: frontier must be a CsrFrontier")
-    num_nodes = rowptr.shape[0] - 1
     if num_nodes != frontier.num_nodes:
         raise native.SageError(f"csr_frontier: the frontier maps {frontier.num_nodes} nodes, the CSR has {num_nodes}")
     n = seeds.shape[0]
     if n == 0:
         return frontier
     dev = frontier.pos.device
-    if col.numel() == 0:                                  # an empty tensor may have no storage address: the kernel reads none of it
-        col = torch.zeros(1, dtype=torch.int32, device=dev)
+    col = _nonempty(col)
     max_edges = col.numel() if max_edges is None else int(max_edges)
-    need = csr_frontier_workspace_bytes(n, max_edges)
-    if need == 0:
-        raise native.SageError(f"csr_frontier: n = {n}, max_edges = {max_edges} out of range")
-    if frontier.workspace is None or frontier.workspace.numel() < need:
-        frontier.workspace = torch.empty(need, dtype=torch.uint8, device=dev)
+    frontier.workspace = _workspace("csr_frontier", csr_frontier_workspace_bytes(n, max_edges), frontier.workspace, dev,
+                                    f"n = {n}, max_edges = {max_edges}")
     rc = native.lib().sage_csr_frontier(native.ptr(rowptr), native.ptr(col), num_nodes, native.ptr(seeds), n, max_edges,
                                         native.ptr(frontier.pos), native.ptr(frontier.nodes), min(frontier.max_nodes, frontier.nodes.numel()),
                                         native.ptr(frontier.count), native.ptr(frontier.workspace), frontier.workspace.numel(),
@@ -505,17 +582,10 @@ def csr_transpose(rowptr, col):
     if e < 0 or e > col.numel() or int(rp[0]) != 0 or (n > 0 and bool((rp[1:] < rp[:-1]).any())):
         raise native.SageError("csr_transpose: rowptr is not a row pointer array of col")
     dst = col[:e].to(torch.int64)
-    if e > 0:
-        lo, hi = int(dst.min()), int(dst.max())
-        if lo < 0 or hi >= n:
-            raise native.SageError(f"csr_transpose: id {lo if lo < 0 else hi} outside [0, {n})")
+    _in_range("csr_transpose", "id", dst, n)
     src = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=col.device), rp[1:] - rp[:-1])
     order = torch.sort(dst, stable=True).indices                 # sources are ascending already: stable keeps them so inside a row
-    col_t = src[order].to(torch.int32)
-    rowptr_t = torch.zeros(n + 1, dtype=torch.int64, device=col.device)
-    if n > 0:
-        rowptr_t[1:] = torch.cumsum(torch.bincount(dst, minlength=n), 0)
-    return rowptr_t, col_t
+    return _group_rowptr(dst, n), src[order].to(torch.int32)
 
 
 def csr_mean_backward_workspace_bytes(num_nodes, n, max_edges, dim):
@@ -529,14 +599,9 @@ def csr_mean_backward(rowptr, col, rowptr_t, col_t, grad_out, nodes=None, self_l
     The result is stored, not accumulated.  max_edges: upper bound on the entries of the selected transposed rows, default
     len(col_t) (exact for distinct rows; a smaller bound only costs speed).  workspace: a uint8 device tensor to reuse."""
     _need_gpu()
-    _chk(rowptr, torch.int64, "rowptr", 1)
-    _chk(col, torch.int32, "col", 1)
-    _chk(rowptr_t, torch.int64, "rowptr_t", 1)
-    _chk(col_t, torch.int32, "col_t", 1)
+    num_nodes = _graph("csr_mean_backward", rowptr, col)
+    _graph("csr_mean_backward", rowptr_t, col_t, "rowptr_t", "col_t")
     grad_out, ldg = _row_major(grad_out, "grad_out")
-    num_nodes = rowptr.shape[0] - 1
-    if num_nodes < 0:
-        raise native.SageError("csr_mean_backward: rowptr is empty")
     if rowptr_t.shape[0] != rowptr.shape[0] or col_t.numel() != col.numel():
         raise native.SageError("csr_mean_backward: the transpose does not have the graph's shape")
     if grad_out.shape[0] < num_nodes:
@@ -545,21 +610,13 @@ def csr_mean_backward(rowptr, col, rowptr_t, col_t, grad_out, nodes=None, self_l
         _chk(nodes, torch.int32, "nodes", 1)
     n = num_nodes if nodes is None else nodes.shape[0]
     dim = grad_out.shape[1]
-    if out is None:
-        out = torch.empty((n, dim), dtype=torch.float32, device=grad_out.device)
-    out, ldgt = _row_major(out, "out")
-    if out.shape[0] < n or out.shape[1] != dim:
-        raise native.SageError(f"csr_mean_backward: out is {tuple(out.shape)}, expected ({n}, {dim})")
+    out, ldgt = _out_rows("csr_mean_backward", out, n, dim, grad_out.device)
     if n == 0:
         return out
-    if col.numel() == 0:                                  # an empty tensor may have no storage address: the kernels read none of it
-        col = col_t = torch.zeros(1, dtype=torch.int32, device=grad_out.device)
+    col, col_t = _nonempty(col), _nonempty(col_t)
     max_edges = col_t.numel() if max_edges is None else int(max_edges)
-    need = csr_mean_backward_workspace_bytes(num_nodes, n, max_edges, dim)
-    if need == 0:
-        raise native.SageError(f"csr_mean_backward: n = {n}, max_edges = {max_edges}, dim = {dim} out of range")
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=grad_out.device)
+    workspace = _workspace("csr_mean_backward", csr_mean_backward_workspace_bytes(num_nodes, n, max_edges, dim), workspace, grad_out.device,
+                           f"n = {n}, max_edges = {max_edges}, dim = {dim}")
     rc = native.lib().sage_csr_mean_backward(native.ptr(rowptr), native.ptr(col), native.ptr(rowptr_t), native.ptr(col_t), num_nodes,
                                              native.ptr(nodes), n, max_edges, native.ptr(grad_out), ldg, dim, 1 if self_loop else 0,
                                              native.ptr(out), ldgt, native.ptr(workspace), workspace.numel(), native.stream_handle())
@@ -588,10 +645,7 @@ def csr_transpose_grouped(rowptr, col, index, num_groups, self_loop=False):
     if k < 0 or k >= (1 << 31):
         raise native.SageError(f"csr_transpose_grouped: num_groups = {k}")
     idx = index.to(torch.int64)
-    if n > 0:
-        lo, hi = int(idx.min()), int(idx.max())
-        if lo < 0 or hi >= k:
-            raise native.SageError(f"csr_transpose_grouped: index {lo if lo < 0 else hi} outside [0, {k})")
+    _in_range("csr_transpose_grouped", "index", idx, k)
     nodes = torch.arange(n, dtype=torch.int64, device=dev)
     owner = torch.repeat_interleave(nodes, rowptr_t[1:] - rowptr_t[:-1])           # col_t's rows: ascending already
     entry = col_t.to(torch.int64)
@@ -601,11 +655,7 @@ def csr_transpose_grouped(rowptr, col, index, num_groups, self_loop=False):
         selfs = nodes[~own]
         owner, entry = torch.cat([owner, selfs]), torch.cat([entry, selfs])         # appended: stable keeps them last in their node
     order = torch.sort(idx[owner] * max(n, 1) + owner, stable=True).indices
-    col_gt = entry[order].to(torch.int32)
-    rowptr_gt = torch.zeros(k + 1, dtype=torch.int64, device=dev)
-    if k > 0 and owner.numel() > 0:
-        rowptr_gt[1:] = torch.cumsum(torch.bincount(idx[owner], minlength=k), 0)
-    return GroupedTranspose(rowptr_gt, col_gt, bool(self_loop))
+    return GroupedTranspose(_group_rowptr(idx[owner], k), entry[order].to(torch.int32), bool(self_loop))
 
 
 def csr_mean_backward_grouped_workspace_bytes(num_nodes, num_groups, max_edges, dim):
@@ -622,44 +672,112 @@ def csr_mean_backward_grouped(rowptr, col, grouped, grad_out, out=None, max_edge
     _need_gpu()
     if not isinstance(grouped, GroupedTranspose):
         raise native.SageError("csr_mean_backward_grouped: grouped must be what csr_transpose_grouped returns")
-    _chk(rowptr, torch.int64, "rowptr", 1)
-    _chk(col, torch.int32, "col", 1)
-    rowptr_gt, col_gt = _chk(grouped.rowptr, torch.int64, "grouped.rowptr", 1), _chk(grouped.col, torch.int32, "grouped.col", 1)
+    num_nodes = _graph("csr_mean_backward_grouped", rowptr, col)
+    rowptr_gt, col_gt = grouped.rowptr, grouped.col
+    k = _graph("csr_mean_backward_grouped", rowptr_gt, col_gt, "grouped.rowptr", "grouped.col")
     grad_out, ldg = _row_major(grad_out, "grad_out")
-    num_nodes, k = rowptr.shape[0] - 1, rowptr_gt.shape[0] - 1
-    if num_nodes < 0 or k < 0:
-        raise native.SageError("csr_mean_backward_grouped: a row pointer array is empty")
     if not col.numel() <= col_gt.numel() <= col.numel() + num_nodes:
         raise native.SageError("csr_mean_backward_grouped: the grouped list does not have the graph's shape")
     if grad_out.shape[0] < num_nodes:
         raise native.SageError(f"csr_mean_backward_grouped: grad_out has {grad_out.shape[0]} rows for {num_nodes} nodes")
     dim = grad_out.shape[1]
-    if out is None:
-        out = torch.empty((k, dim), dtype=torch.float32, device=grad_out.device)
-    out, ldge = _row_major(out, "out")
-    if out.shape[0] < k or out.shape[1] != dim:
-        raise native.SageError(f"csr_mean_backward_grouped: out is {tuple(out.shape)}, expected ({k}, {dim})")
+    out, ldge = _out_rows("csr_mean_backward_grouped", out, k, dim, grad_out.device)
     if k == 0:
         return out
     if num_nodes == 0:                                    # no node reads any row
         out[:k].zero_()
         return out
-    if col.numel() == 0:                                  # an empty tensor may have no storage address: the kernels read none of it
-        col = torch.zeros(1, dtype=torch.int32, device=grad_out.device)
-    if col_gt.numel() == 0:
-        col_gt = torch.zeros(1, dtype=torch.int32, device=grad_out.device)
+    col, col_gt = _nonempty(col), _nonempty(col_gt)
     max_edges = grouped.col.numel() if max_edges is None else int(max_edges)
-    need = csr_mean_backward_grouped_workspace_bytes(num_nodes, k, max_edges, dim)
-    if need == 0:
-        raise native.SageError(f"csr_mean_backward_grouped: K = {k}, max_edges = {max_edges}, dim = {dim} out of range")
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=grad_out.device)
+    workspace = _workspace("csr_mean_backward_grouped", csr_mean_backward_grouped_workspace_bytes(num_nodes, k, max_edges, dim), workspace,
+                           grad_out.device, f"K = {k}, max_edges = {max_edges}, dim = {dim}")
     rc = native.lib().sage_csr_mean_backward_grouped(native.ptr(rowptr), native.ptr(col), native.ptr(rowptr_gt), native.ptr(col_gt),
                                                      num_nodes, k, max_edges, native.ptr(grad_out), ldg, dim, 1 if grouped.self_loop else 0,
                                                      native.ptr(out), ldge, native.ptr(workspace), workspace.numel(),
                                                      native.stream_handle())
     native.check(rc, "csr_mean_backward_grouped")
     return out
+
+
+_SeedBatch = collections.namedtuple("_SeedBatch", "n dim rows max_edges device shape args keep")   # keep: the tensors `args` points into
+
+
+def _seed_batch(who, rowptr, col, nodes, grad_out, index, num_rows, max_edges, total_terms):
+    """The prologue of the two seed-batch adjoints (csr_mean_backward_rows / _touched): the checks of the graph, the seed rows, their
+    gradient, the index with num_rows and total_terms; the ONE host read of the wrappers (max_edges=None: the entries of the seeds'
+    rows); the stand-ins of empty arrays.  `args` are the leading arguments of both C entries (rowptr .. dim), `shape` the sizes in
+    words for a refusal."""
+    _need_gpu()
+    num_nodes = _graph(who, rowptr, col)
+    _chk(nodes, torch.int32, "nodes", 1)
+    grad_out, ldg = _row_major(grad_out, "grad_out")
+    n, dim = nodes.shape[0], grad_out.shape[1]
+    if grad_out.shape[0] < n:
+        raise native.SageError(f"{who}: grad_out has {grad_out.shape[0]} rows for {n} seed rows")
+    if index is not None:
+        _chk(index, torch.int32, "index", 1)
+        if index.shape[0] != num_nodes:
+            raise native.SageError(f"{who}: index has {index.shape[0]} entries for {num_nodes} nodes")
+        if num_rows is None:
+            raise native.SageError(f"{who}: num_rows is required with an index")
+    rows = num_nodes if num_rows is None else int(num_rows)
+    if rows < 0 or (rows == 0 and n > 0):
+        raise native.SageError(f"{who}: num_rows = {rows} with {n} seed rows")
+    if total_terms is not None:
+        _chk(total_terms, torch.int64, "total_terms", 1)
+    if max_edges is None:                                 # the host read: the entries of the seeds' rows (ids clamped into the graph)
+        v = nodes.long().clamp_(0, max(num_nodes - 1, 0))
+        max_edges = int((rowptr[v + 1] - rowptr[v]).clamp_(min=0).sum()) if n > 0 and num_nodes > 0 else 0
+    max_edges = int(max_edges)
+    P = native.ptr
+    keep = col, nodes, index, grad_out = _nonempty(col), _nonempty(nodes), _nonempty(index), _nonempty(grad_out)
+    args = (P(rowptr), P(col), num_nodes, P(nodes), n, max_edges, P(index), rows, P(grad_out), ldg, dim)
+    return _SeedBatch(n, dim, rows, max_edges, grad_out.device, f"n = {n}, max_edges = {max_edges}, num_rows = {rows}, dim = {dim}", args, keep)
+
+
+_TouchedOut = collections.namedtuple("_TouchedOut", "result args")
+
+
+def _touched_out(who, n, dim, rows, cap, table, table_name, lr, want_grad, out, device, total_terms=None):
+    """The output block of the two touched-rows entries (csr_mean_backward_touched / embed_grad_rows) over a table of `rows` rows:
+    `table` (named table_name) and lr go together or the gradient is wanted; (rows, num_rows, grad_rows) of `cap` rows are the
+    caller's `out` or fresh; without terms (n == 0) the library launches nothing, so the counts are zeroed here.  result = the
+    triple to return, args = the C entries' arguments num_rows_out .. lr."""
+    if not want_grad and table is None:
+        raise native.SageError(f"{who}: nothing to do: want_grad=False and no {table_name} to update")
+    if (table is None) != (lr is None):
+        raise native.SageError(f"{who}: {table_name} and lr go together")
+    ldt = 0
+    if table is not None:
+        table, ldt = _row_major(table, table_name)
+        if table.shape[0] < rows or table.shape[1] != dim:
+            raise native.SageError(f"{who}: {table_name} is {tuple(table.shape)}, expected ({rows}, {dim})")
+    if want_grad and cap < 1 and n > 0:
+        raise native.SageError(f"{who}: max_rows = {cap}")
+    cap = max(cap, 1)
+    rows_t, num_t, grad_t = out if out is not None else (None, None, None)
+    if num_t is None:
+        num_t = torch.empty(1, dtype=torch.int32, device=device)
+    _chk(num_t, torch.int32, "num_rows", 1)
+    ldr = 0
+    if want_grad:
+        if rows_t is None:
+            rows_t = torch.empty(cap, dtype=torch.int32, device=device)
+        if grad_t is None:
+            grad_t = torch.empty((cap, dim), dtype=torch.float32, device=device)
+        _chk(rows_t, torch.int32, "rows", 1)
+        grad_t, ldr = _row_major(grad_t, "grad_rows")
+        if rows_t.shape[0] < cap or grad_t.shape[0] < cap or grad_t.shape[1] != dim:
+            raise native.SageError(f"{who}: out is rows {tuple(rows_t.shape)}, grad_rows {tuple(grad_t.shape)}, expected ({cap},) and "
+                                   f"({cap}, {dim})")
+    else:
+        rows_t = grad_t = None
+    if n == 0:
+        num_t.zero_()
+        if total_terms is not None:
+            total_terms.zero_()
+    P = native.ptr
+    return _TouchedOut((rows_t, num_t, grad_t), (P(num_t), P(rows_t), P(grad_t), cap, ldr, P(table), ldt, 0.0 if lr is None else float(lr)))
 
 
 def csr_mean_backward_rows_workspace_bytes(n, max_edges, num_rows, dim):
@@ -677,57 +795,15 @@ def csr_mean_backward_rows(rowptr, col, nodes, grad_out, index=None, num_rows=No
     max_edges: upper bound on the entries of the seeds' rows; None costs one host read of their count.  A bound below the truth
     DROPS the terms past it: total_terms (int64 [1] on the device) receives the true term count (entries + self terms).
     workspace: a uint8 device tensor to reuse."""
-    _need_gpu()
-    _chk(rowptr, torch.int64, "rowptr", 1)
-    _chk(col, torch.int32, "col", 1)
-    _chk(nodes, torch.int32, "nodes", 1)
-    grad_out, ldg = _row_major(grad_out, "grad_out")
-    num_nodes = rowptr.shape[0] - 1
-    if num_nodes < 0:
-        raise native.SageError("csr_mean_backward_rows: rowptr is empty")
-    n, dim = nodes.shape[0], grad_out.shape[1]
-    if grad_out.shape[0] < n:
-        raise native.SageError(f"csr_mean_backward_rows: grad_out has {grad_out.shape[0]} rows for {n} seed rows")
-    if index is not None:
-        _chk(index, torch.int32, "index", 1)
-        if index.shape[0] != num_nodes:
-            raise native.SageError(f"csr_mean_backward_rows: index has {index.shape[0]} entries for {num_nodes} nodes")
-        if num_rows is None:
-            raise native.SageError("csr_mean_backward_rows: num_rows is required with an index")
-    rows = num_nodes if num_rows is None else int(num_rows)
-    if rows < 0 or (rows == 0 and n > 0):
-        raise native.SageError(f"csr_mean_backward_rows: num_rows = {rows} with {n} seed rows")
-    dev = grad_out.device
-    if out is None:
-        out = torch.empty((rows, dim), dtype=torch.float32, device=dev)
-    out, ldgt = _row_major(out, "out")
-    if out.shape[0] < rows or out.shape[1] != dim:
-        raise native.SageError(f"csr_mean_backward_rows: out is {tuple(out.shape)}, expected ({rows}, {dim})")
-    if total_terms is not None:
-        _chk(total_terms, torch.int64, "total_terms", 1)
-    if rows == 0:
+    who = "csr_mean_backward_rows"
+    b = _seed_batch(who, rowptr, col, nodes, grad_out, index, num_rows, max_edges, total_terms)
+    out, ldgt = _out_rows(who, out, b.rows, b.dim, b.device)
+    if b.rows == 0:
         return out
-    if max_edges is None:                                 # the host read: the entries of the seeds' rows (ids clamped into the graph)
-        v = nodes.long().clamp_(0, max(num_nodes - 1, 0))
-        max_edges = int((rowptr[v + 1] - rowptr[v]).clamp_(min=0).sum()) if n > 0 and num_nodes > 0 else 0
-    max_edges = int(max_edges)
-    # an empty tensor may have no storage address: the kernels read none of it
-    if col.numel() == 0:
-        col = torch.zeros(1, dtype=torch.int32, device=dev)
-    if n == 0:
-        nodes, grad_out, ldg = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros((1, dim), dtype=torch.float32, device=dev), dim
-    if index is not None and index.numel() == 0:
-        index = torch.zeros(1, dtype=torch.int32, device=dev)
-    need = csr_mean_backward_rows_workspace_bytes(n, max_edges, rows, dim)
-    if need == 0:
-        raise native.SageError(f"csr_mean_backward_rows: n = {n}, max_edges = {max_edges}, num_rows = {rows}, dim = {dim} out of range")
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    rc = native.lib().sage_csr_mean_backward_rows(native.ptr(rowptr), native.ptr(col), num_nodes, native.ptr(nodes), n, max_edges,
-                                                  native.ptr(index), rows, native.ptr(grad_out), ldg, dim, 1 if self_loop else 0,
-                                                  native.ptr(out), ldgt, native.ptr(total_terms), native.ptr(workspace), workspace.numel(),
-                                                  native.stream_handle())
-    native.check(rc, "csr_mean_backward_rows")
+    workspace = _workspace(who, csr_mean_backward_rows_workspace_bytes(b.n, b.max_edges, b.rows, b.dim), workspace, b.device, b.shape)
+    rc = native.lib().sage_csr_mean_backward_rows(*b.args, 1 if self_loop else 0, native.ptr(out), ldgt, native.ptr(total_terms),
+                                                  native.ptr(workspace), workspace.numel(), native.stream_handle())
+    native.check(rc, who)
     return out
 
 
@@ -748,85 +824,17 @@ def csr_mean_backward_touched(rowptr, col, nodes, grad_out, index=None, num_rows
     for ALL U rows, in place, other rows untouched (torch's version counter of `table` does not move: the caller's business).
     out: (rows, num_rows, grad_rows) to write into (rows / grad_rows may be None there with want_grad=False); workspace: a uint8
     device tensor to reuse."""
-    _need_gpu()
-    _chk(rowptr, torch.int64, "rowptr", 1)
-    _chk(col, torch.int32, "col", 1)
-    _chk(nodes, torch.int32, "nodes", 1)
-    grad_out, ldg = _row_major(grad_out, "grad_out")
-    num_nodes = rowptr.shape[0] - 1
-    if num_nodes < 0:
-        raise native.SageError("csr_mean_backward_touched: rowptr is empty")
-    n, dim = nodes.shape[0], grad_out.shape[1]
-    if grad_out.shape[0] < n:
-        raise native.SageError(f"csr_mean_backward_touched: grad_out has {grad_out.shape[0]} rows for {n} seed rows")
-    if index is not None:
-        _chk(index, torch.int32, "index", 1)
-        if index.shape[0] != num_nodes:
-            raise native.SageError(f"csr_mean_backward_touched: index has {index.shape[0]} entries for {num_nodes} nodes")
-        if num_rows is None:
-            raise native.SageError("csr_mean_backward_touched: num_rows is required with an index")
-    rows = num_nodes if num_rows is None else int(num_rows)
-    if rows < 0 or (rows == 0 and n > 0):
-        raise native.SageError(f"csr_mean_backward_touched: num_rows = {rows} with {n} seed rows")
-    if not want_grad and table is None:
-        raise native.SageError("csr_mean_backward_touched: nothing to do: want_grad=False and no table to update")
-    if (table is None) != (lr is None):
-        raise native.SageError("csr_mean_backward_touched: table and lr go together")
-    dev = grad_out.device
-    ldt = 0
-    if table is not None:
-        table, ldt = _row_major(table, "table")
-        if table.shape[0] < rows or table.shape[1] != dim:
-            raise native.SageError(f"csr_mean_backward_touched: table is {tuple(table.shape)}, expected ({rows}, {dim})")
-    if total_terms is not None:
-        _chk(total_terms, torch.int64, "total_terms", 1)
-    if max_edges is None:                                 # the host read: the entries of the seeds' rows (ids clamped into the graph)
-        v = nodes.long().clamp_(0, max(num_nodes - 1, 0))
-        max_edges = int((rowptr[v + 1] - rowptr[v]).clamp_(min=0).sum()) if n > 0 and num_nodes > 0 else 0
-    max_edges = int(max_edges)
-    cap = min(max_edges + n, rows) if max_rows is None else int(max_rows)
-    if want_grad and cap < 1 and n > 0:
-        raise native.SageError(f"csr_mean_backward_touched: max_rows = {cap}")
-    cap = max(cap, 1)
-    rows_t, num_t, grad_t = out if out is not None else (None, None, None)
-    if num_t is None:
-        num_t = torch.empty(1, dtype=torch.int32, device=dev)
-    _chk(num_t, torch.int32, "num_rows", 1)
-    ldr = 0
-    if want_grad:
-        if rows_t is None:
-            rows_t = torch.empty(cap, dtype=torch.int32, device=dev)
-        if grad_t is None:
-            grad_t = torch.empty((cap, dim), dtype=torch.float32, device=dev)
-        _chk(rows_t, torch.int32, "rows", 1)
-        grad_t, ldr = _row_major(grad_t, "grad_rows")
-        if rows_t.shape[0] < cap or grad_t.shape[0] < cap or grad_t.shape[1] != dim:
-            raise native.SageError(f"csr_mean_backward_touched: out is rows {tuple(rows_t.shape)}, grad_rows {tuple(grad_t.shape)}, "
-                                   f"expected ({cap},) and ({cap}, {dim})")
-    else:
-        rows_t = grad_t = None
-    if n == 0:                                             # the library launches nothing then: the counts are written here
-        num_t.zero_()
-        if total_terms is not None:
-            total_terms.zero_()
-        return rows_t, num_t, grad_t
-    # an empty tensor may have no storage address: the kernels read none of it
-    if col.numel() == 0:
-        col = torch.zeros(1, dtype=torch.int32, device=dev)
-    if index is not None and index.numel() == 0:
-        index = torch.zeros(1, dtype=torch.int32, device=dev)
-    need = csr_mean_backward_touched_workspace_bytes(n, max_edges, rows, dim)
-    if need == 0:
-        raise native.SageError(f"csr_mean_backward_touched: n = {n}, max_edges = {max_edges}, num_rows = {rows}, dim = {dim} out of range")
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    rc = native.lib().sage_csr_mean_backward_touched(native.ptr(rowptr), native.ptr(col), num_nodes, native.ptr(nodes), n, max_edges,
-                                                     native.ptr(index), rows, native.ptr(grad_out), ldg, dim, 1 if self_loop else 0,
-                                                     native.ptr(num_t), native.ptr(rows_t), native.ptr(grad_t), cap, ldr, native.ptr(table),
-                                                     ldt, 0.0 if lr is None else float(lr), native.ptr(total_terms), native.ptr(workspace),
-                                                     workspace.numel(), native.stream_handle())
-    native.check(rc, "csr_mean_backward_touched")
-    return rows_t, num_t, grad_t
+    who, P = "csr_mean_backward_touched", native.ptr
+    b = _seed_batch(who, rowptr, col, nodes, grad_out, index, num_rows, max_edges, total_terms)
+    t = _touched_out(who, b.n, b.dim, b.rows, min(b.max_edges + b.n, b.rows) if max_rows is None else int(max_rows), table, "table", lr,
+                     want_grad, out, b.device, total_terms)
+    if b.n == 0:
+        return t.result
+    workspace = _workspace(who, csr_mean_backward_touched_workspace_bytes(b.n, b.max_edges, b.rows, b.dim), workspace, b.device, b.shape)
+    rc = native.lib().sage_csr_mean_backward_touched(*b.args, 1 if self_loop else 0, *t.args, P(total_terms), P(workspace), workspace.numel(),
+                                                     native.stream_handle())
+    native.check(rc, who)
+    return t.result
 
 
 def group_rows(index, num_groups):
@@ -840,15 +848,9 @@ def group_rows(index, num_groups):
     if k < 0 or index.numel() >= (1 << 31):
         raise native.SageError(f"group_rows: num_groups = {k}, {index.numel()} positions")
     idx = index.to(torch.int64)
-    if idx.numel() > 0:
-        lo, hi = int(idx.min()), int(idx.max())
-        if lo < 0 or hi >= k:
-            raise native.SageError(f"group_rows: index {lo if lo < 0 else hi} outside [0, {k})")
+    _in_range("group_rows", "index", idx, k)
     col_g = torch.sort(idx, stable=True).indices.to(torch.int32)      # positions are ascending already: stable keeps them so inside a group
-    rowptr_g = torch.zeros(k + 1, dtype=torch.int64, device=index.device)
-    if k > 0:
-        rowptr_g[1:] = torch.cumsum(torch.bincount(idx, minlength=k), 0)
-    return rowptr_g, col_g
+    return _group_rowptr(idx, k), col_g
 
 
 def csr_sum_workspace_bytes(num_rows, max_edges, dim):
@@ -862,34 +864,27 @@ def csr_sum(rowptr, col, table, out=None, max_edges=None, workspace=None):
     not accumulated; an empty row is zeros.  max_edges: upper bound on rowptr[-1], default len(col) (a smaller bound only costs
     speed).  workspace: a uint8 device tensor to reuse."""
     _need_gpu()
-    _chk(rowptr, torch.int64, "rowptr", 1)
-    _chk(col, torch.int32, "col", 1)
+    num_rows = _graph("csr_sum", rowptr, col)
     table, ld = _row_major(table, "table")
-    num_rows = rowptr.shape[0] - 1
-    if num_rows < 0:
-        raise native.SageError("csr_sum: rowptr is empty")
     if table.shape[0] < 1:
         raise native.SageError("csr_sum: table has no rows")
     dim = table.shape[1]
-    if out is None:
-        out = torch.empty((num_rows, dim), dtype=torch.float32, device=table.device)
-    out, ldo = _row_major(out, "out")
-    if out.shape[0] < num_rows or out.shape[1] != dim:
-        raise native.SageError(f"csr_sum: out is {tuple(out.shape)}, expected ({num_rows}, {dim})")
+    out, ldo = _out_rows("csr_sum", out, num_rows, dim, table.device)
     if num_rows == 0:
         return out
-    if col.numel() == 0:                                  # an empty tensor may have no storage address: the kernels read none of it
-        col = torch.zeros(1, dtype=torch.int32, device=table.device)
+    col = _nonempty(col)
     max_edges = col.numel() if max_edges is None else int(max_edges)
-    need = csr_sum_workspace_bytes(num_rows, max_edges, dim)
-    if need == 0:
-        raise native.SageError(f"csr_sum: num_rows = {num_rows}, max_edges = {max_edges}, dim = {dim} out of range")
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=table.device)
+    workspace = _workspace("csr_sum", csr_sum_workspace_bytes(num_rows, max_edges, dim), workspace, table.device,
+                           f"num_rows = {num_rows}, max_edges = {max_edges}, dim = {dim}")
     rc = native.lib().sage_csr_sum(native.ptr(rowptr), native.ptr(col), num_rows, max_edges, native.ptr(table), table.shape[0], ld, dim,
                                    native.ptr(out), ldo, native.ptr(workspace), workspace.numel(), native.stream_handle())
     native.check(rc, "csr_sum")
     return out
+
+
+def row_order_workspace_bytes(n):
+    """Bytes of the workspace sage_row_order needs (host arithmetic; 0 = n out of range)."""
+    return int(native.lib().sage_row_order_workspace_bytes(int(n)))
 
 
 def row_order(nodes, n_dev=None, first_row=0, out=None, workspace=None):
@@ -901,16 +896,13 @@ def row_order(nodes, n_dev=None, first_row=0, out=None, workspace=None):
     n = nodes.shape[0]
     if n < 1:
         raise native.SageError("row_order: no rows")
-    if n_dev is not None:
-        _chk(n_dev, torch.int32, "n_dev")
+    _opt_i32(n_dev, "n_dev", min_len=1)
     if out is None:
         out = torch.empty(n, dtype=torch.int32, device=nodes.device)
     _chk(out, torch.int32, "out", 1)
     if out.shape[0] < n:
         raise native.SageError(f"row_order: out has {out.shape[0]} entries for {n} rows")
-    need = int(native.lib().sage_row_order_workspace_bytes(n))
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=nodes.device)
+    workspace = _workspace("row_order", row_order_workspace_bytes(n), workspace, nodes.device, f"n = {n}")
     native.check(native.lib().sage_row_order(native.ptr(nodes), n, native.ptr(n_dev), int(first_row), native.ptr(out), native.ptr(workspace),
                                              workspace.numel(), native.stream_handle()), "row_order")
     return out
@@ -921,39 +913,31 @@ def embed_grad_workspace_bytes(n, k, embed_rows, dim):
     return int(native.lib().sage_embed_grad_workspace_bytes(int(n), int(k), int(embed_rows), int(dim)))
 
 
+def _embed_terms(who, grad_agg, nbr, cnt, n_dev, row_order):
+    """What embed_grad and embed_grad_rows read: grad_agg [n, dim] over the sets (nbr, cnt), n_dev and row_order; returns (ldg, n, k, dim)."""
+    _need_gpu()
+    grad_agg, ldg = _row_major(grad_agg, "grad_agg")
+    n, k = _sets(who, nbr, cnt, n_dev)
+    if grad_agg.shape[0] < n:
+        raise native.SageError(f"{who}: {n} sets, grad_agg has {grad_agg.shape[0]} rows, cnt {cnt.shape[0]} entries")
+    _opt_i32(row_order, "row_order", 1, n)
+    return ldg, n, k, grad_agg.shape[1]
+
+
 def embed_grad(grad_agg, nbr, cnt, embed_rows, n_dev=None, row_order=None, out=None, workspace=None):
     """[embed_rows, dim]: the gradient of an embedding whose rows the sampled sets (nbr [n, k], cnt [n]) name, from the gradient of the
     sets' means grad_agg [n, dim]: row e is the sum of grad_agg[t] / c_t over the slots (t, j < c_t) with nbr[t, j] == e, the terms in
     `row_order` position (sage_embed_grad: 512-term chunks, fixed order, no atomics).  Stored, not accumulated: a row nobody names is
     zeros.  n_dev: int32 [1] live row count; row_order: int32 [n] from ops.row_order (None: rows as they lie); workspace: a uint8
     device tensor to reuse."""
-    _need_gpu()
-    grad_agg, ldg = _row_major(grad_agg, "grad_agg")
-    _chk(nbr, torch.int32, "nbr", 2)
-    _chk(cnt, torch.int32, "cnt", 1)
-    n, k = nbr.shape
-    dim, rows = grad_agg.shape[1], int(embed_rows)
-    if grad_agg.shape[0] < n or cnt.shape[0] < n:
-        raise native.SageError(f"embed_grad: {n} sets, grad_agg has {grad_agg.shape[0]} rows, cnt {cnt.shape[0]} entries")
-    if n_dev is not None:
-        _chk(n_dev, torch.int32, "n_dev")
-    if row_order is not None:
-        _chk(row_order, torch.int32, "row_order", 1)
-        if row_order.shape[0] < n:
-            raise native.SageError(f"embed_grad: row_order has {row_order.shape[0]} entries for {n} rows")
-    if out is None:
-        out = torch.empty((rows, dim), dtype=torch.float32, device=grad_agg.device)
-    out, ld = _row_major(out, "out")
-    if out.shape[0] < rows or out.shape[1] != dim:
-        raise native.SageError(f"embed_grad: out is {tuple(out.shape)}, expected ({rows}, {dim})")
+    ldg, n, k, dim = _embed_terms("embed_grad", grad_agg, nbr, cnt, n_dev, row_order)
+    rows = int(embed_rows)
+    out, ld = _out_rows("embed_grad", out, rows, dim, grad_agg.device)
     if n == 0:                                             # the library launches nothing then: the zeros are written here
         out[:rows].zero_()
         return out
-    need = embed_grad_workspace_bytes(n, k, rows, dim)
-    if need == 0:
-        raise native.SageError(f"embed_grad: n = {n}, k = {k}, embed_rows = {rows}, dim = {dim} out of range")
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=grad_agg.device)
+    workspace = _workspace("embed_grad", embed_grad_workspace_bytes(n, k, rows, dim), workspace, grad_agg.device,
+                           f"n = {n}, k = {k}, embed_rows = {rows}, dim = {dim}")
     rc = native.lib().sage_embed_grad(native.ptr(grad_agg), ldg, dim, native.ptr(nbr), native.ptr(cnt), k, n, native.ptr(n_dev),
                                       native.ptr(row_order), native.ptr(out), rows, ld, native.ptr(workspace), workspace.numel(),
                                       native.stream_handle())
@@ -976,65 +960,18 @@ def embed_grad_rows(grad_agg, nbr, cnt, embed_rows, n_dev=None, row_order=None, 
     embed_rows), which always holds every row.  embed [embed_rows, dim] with lr: embed[e] = fma(-lr, sum, embed[e]) for ALL U rows, in
     place, other rows untouched (torch's version counter of `embed` does not move: the caller's business).  out: (rows, num_rows,
     grad_rows) to write into (rows / grad_rows may be None there with want_grad=False); workspace: a uint8 device tensor to reuse."""
-    _need_gpu()
-    grad_agg, ldg = _row_major(grad_agg, "grad_agg")
-    _chk(nbr, torch.int32, "nbr", 2)
-    _chk(cnt, torch.int32, "cnt", 1)
-    n, k = nbr.shape
-    dim, rows = grad_agg.shape[1], int(embed_rows)
-    dev = grad_agg.device
-    if grad_agg.shape[0] < n or cnt.shape[0] < n:
-        raise native.SageError(f"embed_grad_rows: {n} sets, grad_agg has {grad_agg.shape[0]} rows, cnt {cnt.shape[0]} entries")
-    if n_dev is not None:
-        _chk(n_dev, torch.int32, "n_dev")
-    if row_order is not None:
-        _chk(row_order, torch.int32, "row_order", 1)
-        if row_order.shape[0] < n:
-            raise native.SageError(f"embed_grad_rows: row_order has {row_order.shape[0]} entries for {n} rows")
-    if not want_grad and embed is None:
-        raise native.SageError("embed_grad_rows: nothing to do: want_grad=False and no embed to update")
-    if (embed is None) != (lr is None):
-        raise native.SageError("embed_grad_rows: embed and lr go together")
-    lde = 0
-    if embed is not None:
-        embed, lde = _row_major(embed, "embed")
-        if embed.shape[0] < rows or embed.shape[1] != dim:
-            raise native.SageError(f"embed_grad_rows: embed is {tuple(embed.shape)}, expected ({rows}, {dim})")
-    cap = min(n * k, rows) if max_rows is None else int(max_rows)
-    if want_grad and cap < 1 and n > 0:
-        raise native.SageError(f"embed_grad_rows: max_rows = {cap}")
-    cap = max(cap, 1)
-    rows_t, num_t, grad_t = out if out is not None else (None, None, None)
-    if num_t is None:
-        num_t = torch.empty(1, dtype=torch.int32, device=dev)
-    _chk(num_t, torch.int32, "num_rows", 1)
-    ldr = 0
-    if want_grad:
-        if rows_t is None:
-            rows_t = torch.empty(cap, dtype=torch.int32, device=dev)
-        if grad_t is None:
-            grad_t = torch.empty((cap, dim), dtype=torch.float32, device=dev)
-        _chk(rows_t, torch.int32, "rows", 1)
-        grad_t, ldr = _row_major(grad_t, "grad_rows")
-        if rows_t.shape[0] < cap or grad_t.shape[0] < cap or grad_t.shape[1] != dim:
-            raise native.SageError(f"embed_grad_rows: out is rows {tuple(rows_t.shape)}, grad_rows {tuple(grad_t.shape)}, expected "
-                                   f"({cap},) and ({cap}, {dim})")
-    else:
-        rows_t = grad_t = None
-    if n == 0:                                             # the library launches nothing then: the count is written here
-        num_t.zero_()
-        return rows_t, num_t, grad_t
-    need = embed_grad_rows_workspace_bytes(n, k, rows, dim)
-    if need == 0:
-        raise native.SageError(f"embed_grad_rows: n = {n}, k = {k}, embed_rows = {rows}, dim = {dim} out of range")
-    if workspace is None or workspace.numel() < need:
-        workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    rc = native.lib().sage_embed_grad_rows(native.ptr(grad_agg), ldg, dim, native.ptr(nbr), native.ptr(cnt), k, n, native.ptr(n_dev),
-                                           native.ptr(row_order), rows, native.ptr(num_t), native.ptr(rows_t), native.ptr(grad_t), cap, ldr,
-                                           native.ptr(embed), lde, 0.0 if lr is None else float(lr), native.ptr(workspace),
+    who, P = "embed_grad_rows", native.ptr
+    ldg, n, k, dim = _embed_terms(who, grad_agg, nbr, cnt, n_dev, row_order)
+    rows, dev = int(embed_rows), grad_agg.device
+    t = _touched_out(who, n, dim, rows, min(n * k, rows) if max_rows is None else int(max_rows), embed, "embed", lr, want_grad, out, dev)
+    if n == 0:
+        return t.result
+    workspace = _workspace(who, embed_grad_rows_workspace_bytes(n, k, rows, dim), workspace, dev,
+                           f"n = {n}, k = {k}, embed_rows = {rows}, dim = {dim}")
+    rc = native.lib().sage_embed_grad_rows(P(grad_agg), ldg, dim, P(nbr), P(cnt), k, n, P(n_dev), P(row_order), rows, *t.args, P(workspace),
                                            workspace.numel(), native.stream_handle())
-    native.check(rc, "embed_grad_rows")
-    return rows_t, num_t, grad_t
+    native.check(rc, who)
+    return t.result
 
 
 def xent_head_supported(dim, num_classes):
@@ -1102,7 +1039,7 @@ def xent_head(emb, w_cls, labels=None, scale=None, scores=False, pred=False, gra
     need = xent_head_workspace_bytes(n, dim, c)
     if workspace is None:
         workspace = torch.empty(need, dtype=torch.uint8, device=dev)
-    elif not workspace.is_cuda or workspace.dtype != torch.uint8 or workspace.numel() < need:
+    elif not _is_workspace(workspace, dev) or workspace.numel() < need:          # stricter than _workspace: a short one is refused
         raise native.SageError(f"xent_head: workspace must be a uint8 device tensor of >= {need} bytes")
     rc = native.lib().sage_xent_head(native.ptr(emb), lde, dim, native.ptr(w_cls), ldw, c, native.ptr(labels), n,
                                      float(1.0 / n if scale is None else scale), native.ptr(t_scores), lds, native.ptr(t_pred),
