@@ -19,7 +19,7 @@ edge = int(sys.argv[2]) if len(sys.argv) > 2 else 40
 def kind(n):
     if "sample_kernel" in n:
         return "So" if "true, true>" in n else "Si"
-    if "layer1_phase_kernel" in n:
+    if "layer1_phase_kernel" in n or "layer1_pair_kernel" in n:
         return "G"
     if "layer_tile16" in n or "layer_fused" in n:
         return "L"

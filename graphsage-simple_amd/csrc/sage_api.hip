@@ -33,6 +33,11 @@ static int env_int(const char* name, int dflt, int lo, int hi) {
 #define SAGE_LAYER1_FUSED_DEFAULT 1
 #endif
 
+// Tiles per block of the phase-sliced layer 1 (the same-box A/B that decides it)
+#ifndef SAGE_L1P_TILES_DEFAULT
+#define SAGE_L1P_TILES_DEFAULT 2
+#endif
+
 const sage_tunables_t& sage_tunables() {
     static const sage_tunables_t t = [] {
         sage_tunables_t x;
@@ -57,7 +62,8 @@ const sage_tunables_t& sage_tunables() {
         { const int tw = env_int("SAGE_T16_WAVES", 0, 0, 16); x.tile16_waves = tw == 0 ? 0 : tw >= 16 ? 16 : 8; }
         { const int ti = env_int("SAGE_T16_INFLIGHT", 0, 0, 13); x.tile16_inflight = ti == 0 ? 0 : ti >= 13 ? 13 : 7; }
         x.layer1_fused = env_int("SAGE_LAYER1_FUSED", SAGE_LAYER1_FUSED_DEFAULT, 0, 1);
-        x.layer1_phase_per_cu = env_int("SAGE_L1P_PER_CU", 3, 1, 3);
+        x.layer1_phase_tiles = env_int("SAGE_L1P_TILES", SAGE_L1P_TILES_DEFAULT, 1, 2);
+        { const int most = x.layer1_phase_tiles == 2 ? 2 : 3; x.layer1_phase_per_cu = env_int("SAGE_L1P_PER_CU", most, 1, most); }
         return x;
     }();
     return t;

@@ -235,6 +235,33 @@ __device__ __forceinline__ void gather_sliced_block_pipelined(
 // rows of all 64/SL destinations are in flight together.  (A predicated form compiled to one exec branch and one
 // s_waitcnt vmcnt(0) PER LOAD: 54 us at 4 blocks per CU.)
 using gather_v4 = __attribute__((ext_vector_type(4))) float;
+// One trip of a unit in its two halves: request the TRIP rows from list position j0 on, and add them in list order once they are
+// here.  A caller that has other work between the two (the pair form of the phase-sliced layer 1) keeps the trip in flight over it.
+template <int TRIP, bool SLOT>
+__device__ __forceinline__ void gather_rows_unit_issue(const float* __restrict__ tcol, const int64_t ld, const int32_t* __restrict__ myn,
+                                                       const int j0, const int c, const int k, const int s, const int last_row,
+                                                       const int32_t* __restrict__ slot_rows, bool& extra, gather_v4 (&t)[TRIP]) {
+    int id[TRIP];
+#pragma unroll
+    for (int u = 0; u < TRIP; ++u) id[u] = myn[min(min(j0 + u, c - 1), k - 1) < 0 ? 0 : min(min(j0 + u, c - 1), k - 1)];
+#pragma unroll
+    for (int u = 0; u < TRIP; ++u) {
+        int x = id[u];
+        if (SLOT) x = slot_rows[max(x, 0)];
+        extra = extra && !(j0 + u < c && x == s);               // aggregators.py:50-51: set union
+        x = min(max(x, 0), last_row);
+        t[u] = *reinterpret_cast<const gather_v4*>(tcol + (int64_t)x * ld);
+    }
+}
+template <int TRIP>
+__device__ __forceinline__ void gather_rows_unit_add(gather_v4& acc, const gather_v4 (&t)[TRIP], const int j0, const int c) {
+#pragma unroll
+    for (int u = 0; u < TRIP; ++u) {
+        // select, not multiply: a slot past the end may hold Inf / NaN of a row that is not in the set
+        acc[0] += (j0 + u < c) ? t[u][0] : 0.f; acc[1] += (j0 + u < c) ? t[u][1] : 0.f;
+        acc[2] += (j0 + u < c) ? t[u][2] : 0.f; acc[3] += (j0 + u < c) ? t[u][3] : 0.f;
+    }
+}
 template <int TRIP, bool SLOT>
 __device__ __forceinline__ gather_v4 gather_rows_unit_sum(const float* __restrict__ tcol, const int64_t ld, const int32_t* __restrict__ myn,
                                                           const int c, const int k, const int s, const int last_row,
@@ -242,24 +269,9 @@ __device__ __forceinline__ gather_v4 gather_rows_unit_sum(const float* __restric
     using V = gather_v4;
     V acc = {0.f, 0.f, 0.f, 0.f};
     for (int j0 = 0; j0 < k; j0 += TRIP) {                      // wave-uniform bounds; one trip when k <= TRIP
-        int id[TRIP];
-#pragma unroll
-        for (int u = 0; u < TRIP; ++u) id[u] = myn[min(min(j0 + u, c - 1), k - 1) < 0 ? 0 : min(min(j0 + u, c - 1), k - 1)];
         V t[TRIP];
-#pragma unroll
-        for (int u = 0; u < TRIP; ++u) {
-            int x = id[u];
-            if (SLOT) x = slot_rows[max(x, 0)];
-            extra = extra && !(j0 + u < c && x == s);           // aggregators.py:50-51: set union
-            x = min(max(x, 0), last_row);
-            t[u] = *reinterpret_cast<const V*>(tcol + (int64_t)x * ld);
-        }
-#pragma unroll
-        for (int u = 0; u < TRIP; ++u) {
-            // select, not multiply: a slot past the end may hold Inf / NaN of a row that is not in the set
-            acc[0] += (j0 + u < c) ? t[u][0] : 0.f; acc[1] += (j0 + u < c) ? t[u][1] : 0.f;
-            acc[2] += (j0 + u < c) ? t[u][2] : 0.f; acc[3] += (j0 + u < c) ? t[u][3] : 0.f;
-        }
+        gather_rows_unit_issue<TRIP, SLOT>(tcol, ld, myn, j0, c, k, s, last_row, slot_rows, extra, t);
+        gather_rows_unit_add<TRIP>(acc, t, j0, c);
     }
     if (extra) {
         const V sv = *reinterpret_cast<const V*>(tcol + (int64_t)min(s, last_row) * ld);
@@ -267,7 +279,18 @@ __device__ __forceinline__ gather_v4 gather_rows_unit_sum(const float* __restric
     }
     return acc;
 }
-// the mean of a unit, with the empty-set rule (NaN inside a batch that has non-empty sets, zeros otherwise)
+// the mean of a unit, with the empty-set rule (NaN inside a batch that has non-empty sets, zeros otherwise).  In two steps for the
+// caller that means many slices of one row (the pair form of the phase-sliced layer 1): the row's scale 1 / |set| once -- below zero
+// for the empty set -- and then one multiply per slice with nothing but a select beside it.  (With the division beside it the select
+// becomes a branch, and a sum that is used on one side of a branch only is moved there, behind whatever stands between sum and mean.)
+__device__ __forceinline__ float gather_rows_unit_scale(const int c, const bool extra) {
+    const int ceff = c + (extra ? 1 : 0);
+    return ceff > 0 ? 1.0f / (float)ceff : -1.0f;
+}
+__device__ __forceinline__ gather_v4 gather_rows_unit_mean(const gather_v4 acc, const float scale, const bool nan_rule) {
+    const float fill = nan_rule ? __builtin_nanf("") : 0.f;
+    return scale >= 0.f ? acc * scale : gather_v4{fill, fill, fill, fill};
+}
 __device__ __forceinline__ gather_v4 gather_rows_unit_mean(const gather_v4 acc, const int c, const bool extra, const bool nan_rule) {
     const int ceff = c + (extra ? 1 : 0);
     if (ceff > 0) return acc * (1.0f / (float)ceff);

@@ -197,7 +197,9 @@ struct sage_tunables_t {
                                   //                      13 beside the one-launch layer 1, 7 otherwise.  Every other form has 7
     int layer1_fused;             // SAGE_LAYER1_FUSED    1: layer 1 as ONE phase-sliced launch where its conditions hold and nobody needs the means
                                   //                      (sage_layer1_phase.hip); 0: always gather + contraction.  Default: see sage_api.hip
-    int layer1_phase_per_cu;      // SAGE_L1P_PER_CU      phase-sliced layer 1: persistent 256-thread blocks per CU (1..3), default 3
+    int layer1_phase_tiles;       // SAGE_L1P_TILES       phase-sliced layer 1: 32-row tiles a block walks in ping-pong, 2 (default) or 1
+    int layer1_phase_per_cu;      // SAGE_L1P_PER_CU      phase-sliced layer 1: persistent 256-thread blocks per CU: 1..2 with two tiles per
+                                  //                      block (default 2), 1..3 with one (default 3)
 };
 // n_words 32-bit words := v, as a kernel (hipMemsetAsync misbehaves inside replayed hipGraphs on ROCm 7.2: sage_api.hip)
 int sage_fill_u32(void* p, uint32_t v, size_t n_words, hipStream_t st);
