@@ -30,6 +30,16 @@ def graph_voronoi_labels(graph, num_classes, rng):
     return labels
 
 
+def pagerank_table(graph, device, **kw):
+    """float32 [N, 1] on `device`: the frozen feature table of --initializer pagerank (model.py:159-162: nx.pagerank(G) as the
+    single feature column), computed on the device by ops.pagerank; **kw are its keywords (alpha, tol, max_iter, symmetric).  Layer 1
+    of this initializer goes through a sigmoid (encoders.py:58): the trainers and run drivers take it as act1=ACT_SIGMOID."""
+    from . import ops
+    rowptr, col = graph.to(device)
+    x, _ = ops.pagerank(rowptr, col, **kw)
+    return x.reshape(-1, 1)
+
+
 def standin_citation(graph, num_classes=7, feat_dim=1433, words_per_node=18, topic_words=60, purity=0.7, seed=0):
     """-> (feat_data float32 [N, feat_dim] 0/1, labels int64 [N, 1]) in the reference loaders' layout
     (model.py:267-269: feat_data, labels [N,1])."""

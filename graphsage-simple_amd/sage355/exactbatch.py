@@ -19,7 +19,7 @@ import torch
 
 from . import dist, ops
 from .head import head_grads, head_predict
-from .fullgraph import check_table_dtype, embed_arguments
+from .fullgraph import check_table_dtype, embed_arguments, frozen_arguments
 from .inference import _check_index, _seed_frontier
 from .native import ACT_RELU, SageError
 from .train import _batches, _split, _validation_result, check_trainer_args, csr_pair, init_parameters
@@ -246,17 +246,18 @@ class ExactBatchEmbedTrainer(ExactBatchTrainer):
 
 
 def run_exact_batch_training(graph, feat_data, labels, num_classes, seed=1, epochs=1, batch_size=128, ref_batching=False, lr=0.7,
-                             hidden1=50, hidden2=128, gcn=True, agg_self_loop=False, head="native", table_dtype=torch.float32, initializer="None",
-                             embed_dim=100, sparse_embed=False):
+                             hidden1=50, hidden2=128, gcn=True, agg_self_loop=False, head="native", table_dtype=torch.float32, act1=None,
+                             initializer="None", embed_dim=100, sparse_embed=False):
     """run_model (model.py:184-259) with num_sample=None batches: the same split, shuffles, batching and SGD as
     train.run_engine_training, every step through ExactBatchTrainer, validation by its predict (full neighbourhoods as well).
     initializer, embed_dim: run_full_graph_training's -- "None": the frozen table feat_data; "1hot" / "node_degree": a trainable
     embedding through ExactBatchEmbedTrainer (feat_data is not read and may be None), with its sparse_embed.
     table_dtype: torch.float32, or torch.bfloat16 = the frozen table is rounded to bf16 once and stored so (half its bytes; exact for
     0/1 features); refused with a trainable embedding, which stays fp32.
+    act1: run_full_graph_training's (a frozen table's layer-1 activation; refused with an initializer).
     -> dict(f1_micro, f1_macro, mean_step_time, losses, trainer), as train.run_engine_training."""
     dev = torch.device("cuda")
-    embed = embed_arguments("run_exact_batch_training", initializer, ("None",), graph, embed_dim, dev)
+    embed = embed_arguments("run_exact_batch_training", initializer, ("None",), graph, embed_dim, dev, act1)
     table_dtype = check_table_dtype("run_exact_batch_training", table_dtype, embed is not None)
     if sparse_embed and embed is None:
         raise SageError("run_exact_batch_training: sparse_embed needs initializer '1hot' or 'node_degree': a frozen table has no update")
@@ -264,7 +265,8 @@ def run_exact_batch_training(graph, feat_data, labels, num_classes, seed=1, epoc
     _, val, train = _split(graph.num_nodes, seed)
     common = dict(hidden1=hidden1, hidden2=hidden2, gcn=gcn, lr=lr, agg_self_loop=agg_self_loop, head=head)
     if embed is None:
-        tr = ExactBatchTrainer(rowptr, col, torch.as_tensor(feat_data, dtype=torch.float32).to(dev).to(table_dtype), num_classes, **common)
+        tr = ExactBatchTrainer(rowptr, col, torch.as_tensor(feat_data, dtype=torch.float32).to(dev).to(table_dtype), num_classes, **common,
+                               **frozen_arguments(act1))
     else:
         tr = ExactBatchEmbedTrainer(rowptr, col, num_classes, sparse_embed=sparse_embed, **embed, **common)
     labels_dev = torch.as_tensor(np.asarray(labels).reshape(-1), dtype=torch.int64).to(dev)

@@ -231,14 +231,19 @@ def check_table_dtype(who, table_dtype, trainable_embedding):
     return table_dtype
 
 
-def embed_arguments(who, initializer, frozen, graph, embed_dim, dev):
+def embed_arguments(who, initializer, frozen, graph, embed_dim, dev, act1=None):
     """What a run driver `who` hands its trainer for --initializer (model.py:153-157, 209-212): None for a spelling in `frozen` (the
     frozen feature table), else dict(embed_index, embed_rows, embed_dim, act1) -- "1hot": a row per node, ReLU; "node_degree": a row
-    per degree, SIGMOID at layer 1 (encoders.py:58-59).  Anything else is refused, before the graph is read."""
+    per degree, SIGMOID at layer 1 (encoders.py:58-59).  Anything else is refused, before the graph is read.
+    act1: the driver's own act1 argument, which belongs to a frozen table (frozen_arguments); with an initializer that sets layer
+    1's activation itself it is refused."""
     if initializer not in (*frozen, "1hot", "node_degree"):
         raise SageError(f"{who}: initializer = {initializer!r}, expected {frozen[0]!r}, '1hot' or 'node_degree'")
     if initializer in frozen:
         return None
+    if act1 is not None:
+        raise SageError(f"{who}: act1 = {act1!r} with initializer = {initializer!r}, which sets layer 1's activation itself; act1 goes "
+                        "with a frozen table (datasets.pagerank_table with ACT_SIGMOID)")
     if initializer == "1hot":
         index, rows = one_hot_index(graph.num_nodes, dev)
     else:
@@ -246,9 +251,15 @@ def embed_arguments(who, initializer, frozen, graph, embed_dim, dev):
     return dict(embed_index=index.to(dev), embed_rows=rows, embed_dim=embed_dim, act1=ACT_SIGMOID if initializer == "node_degree" else ACT_RELU)
 
 
+def frozen_arguments(act1):
+    """What a run driver hands the trainer of a frozen table for its act1 argument: None is the trainer's own default (ReLU); a
+    table that wants another layer-1 activation names it -- datasets.pagerank_table goes with ACT_SIGMOID (encoders.py:58)."""
+    return {} if act1 is None else dict(act1=act1)
+
+
 def run_full_graph_training(graph, feat_data, labels, num_classes, seed=1, steps=100, lr=0.7, hidden1=50, hidden2=128, gcn=True,
                             agg_self_loop=False, head="native", initializer="None", embed_dim=100, fused_embed=False,
-                            table_dtype=torch.float32):
+                            table_dtype=torch.float32, act1=None):
     """run_model (model.py:184-259) with full neighbourhoods: the same 10 / 10 / 80 split of a seeded numpy permutation
     (model.py:229-235), ONE step per epoch over the whole training set, `steps` epochs.
     initializer: "None" -- the frozen table feat_data, ReLU at both layers; "1hot" -- a trainable embedding row per node, ReLU;
@@ -259,15 +270,16 @@ def run_full_graph_training(graph, feat_data, labels, num_classes, seed=1, steps
     fused_embed: FullGraphTrainer's flag (it changes something for "node_degree" only: the 1hot index is the identity).
     table_dtype: torch.float32, or torch.bfloat16 = the frozen table is rounded to bf16 once and stored so (gcn=True only; refused
     with a trainable embedding).
+    act1: layer 1's activation over a frozen table (None: ReLU), ACT_SIGMOID for datasets.pagerank_table; refused with an initializer.
     -> dict(f1_micro, f1_macro, mean_step_time, losses, trainer), as train.run_engine_training."""
     dev = torch.device("cuda")
-    embed = embed_arguments("run_full_graph_training", initializer, ("None",), graph, embed_dim, dev)
+    embed = embed_arguments("run_full_graph_training", initializer, ("None",), graph, embed_dim, dev, act1)
     table_dtype = check_table_dtype("run_full_graph_training", table_dtype, embed is not None)
     rowptr, col = graph.to(dev)
     _, val, train = _split(graph.num_nodes, seed)
     table = torch.as_tensor(feat_data, dtype=torch.float32).to(dev).to(table_dtype) if embed is None else None
     tr = FullGraphTrainer(rowptr, col, table, num_classes, hidden1, hidden2, gcn=gcn, lr=lr, agg_self_loop=agg_self_loop, head=head,
-                          fused_embed=fused_embed, **(embed or {}))
+                          fused_embed=fused_embed, **(embed or frozen_arguments(act1)))
     labels_dev = torch.as_tensor(np.asarray(labels).reshape(-1), dtype=torch.int64).to(dev)
     ids = torch.as_tensor(train.astype(np.int32)).to(dev)
     tgt = labels_dev[ids.long()]

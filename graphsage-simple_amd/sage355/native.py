@@ -45,6 +45,7 @@ SYMBOLS = [
     "sage_csr_mean_backward_rows_workspace_bytes", "sage_csr_mean_backward_rows",
     "sage_csr_mean_backward_touched_workspace_bytes", "sage_csr_mean_backward_touched",
     "sage_csr_mean_bf16",
+    "sage_pagerank_workspace_bytes", "sage_pagerank_init", "sage_pagerank_load", "sage_pagerank_step",
 ]
 PIPE_MAX_DEPTH = 8
 
@@ -184,6 +185,10 @@ def lib():
     L.sage_csr_mean_backward_touched.argtypes = [P, P, I64, P, I32, I64, P, I64, P, I64, I32, I32, P, P, P, I64, I64, P, I64, c_float, P,
                                                  P, c_size_t, P]
     L.sage_csr_mean_bf16.argtypes = L.sage_csr_mean.argtypes
+    L.sage_pagerank_workspace_bytes.argtypes = [I64, I64]
+    L.sage_pagerank_init.argtypes = [P, I64, I64, P, P, P, P, P, P, c_size_t, P]
+    L.sage_pagerank_load.argtypes = [P, I64, I64, P, P, P, P, P, c_size_t, P]
+    L.sage_pagerank_step.argtypes = [P, P, I64, I64, P, c_float, P, P, P, P, P, P, c_size_t, P]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name == "sage_prepared_weight_bytes" or name.endswith("_workspace_bytes"):

@@ -882,6 +882,87 @@ def csr_sum(rowptr, col, table, out=None, max_edges=None, workspace=None):
     return out
 
 
+def pagerank_workspace_bytes(num_nodes, num_edges):
+    """Bytes of the workspace the sage_pagerank_* entries need (host arithmetic; 0 = shape out of range)."""
+    return int(native.lib().sage_pagerank_workspace_bytes(int(num_nodes), int(num_edges)))
+
+
+def _pagerank_graph(who, rowptr, col, alpha):
+    """The pull CSR of a PageRank call and its alpha; returns (N, col with an address, number of edges the workspace is sized for)."""
+    _need_gpu()
+    n = _graph(who, rowptr, col)
+    if n < 1:
+        raise native.SageError(f"{who}: the graph has no nodes")
+    if not 0.0 < float(alpha) < 1.0:
+        raise native.SageError(f"{who}: alpha = {alpha!r}, expected inside (0, 1)")
+    return n, _nonempty(col), col.numel()
+
+
+def pagerank_step(rowptr, col, x, inv_out, alpha=0.85, workspace=None):
+    """One PageRank power-iteration step from any x: (x_next float32 [N], err float32 [1] on the device) with
+    x_next = alpha * (pull of x * inv_out over the CSR + mass / N) + (1 - alpha) / N, mass = the sum of x over the dangling nodes
+    (inv_out == 0), err = sum |x_next - x|, N = len(x) (include/sage355.h: sage_pagerank_load, sage_pagerank_step).  Row i of
+    (rowptr, col) lists the nodes that link to i; inv_out is 1 / out-degree, 0 for a dangling node."""
+    n, col, e = _pagerank_graph("pagerank_step", rowptr, col, alpha)
+    _chk(x, torch.float32, "x", 1)
+    _chk(inv_out, torch.float32, "inv_out", 1)
+    if x.shape[0] != n or inv_out.shape[0] != n:
+        raise native.SageError(f"pagerank_step: x has {x.shape[0]} and inv_out {inv_out.shape[0]} entries for {n} nodes")
+    dev = x.device
+    workspace = _workspace("pagerank_step", pagerank_workspace_bytes(n, e), workspace, dev, f"num_nodes = {n}, num_edges = {e}")
+    y, x_next, y_next = (torch.empty(n, dtype=torch.float32, device=dev) for _ in range(3))
+    state = torch.empty(2, dtype=torch.float32, device=dev)
+    L, st = native.lib(), native.stream_handle()
+    native.check(L.sage_pagerank_load(native.ptr(rowptr), n, e, native.ptr(x), native.ptr(inv_out), native.ptr(y), native.ptr(state),
+                                      native.ptr(workspace), workspace.numel(), st), "pagerank_load")
+    native.check(L.sage_pagerank_step(native.ptr(rowptr), native.ptr(col), n, e, native.ptr(inv_out), float(alpha), native.ptr(x), native.ptr(y),
+                                      native.ptr(x_next), native.ptr(y_next), native.ptr(state), native.ptr(workspace), workspace.numel(), st),
+                 "pagerank_step")
+    return x_next, state[:1]
+
+
+def pagerank(rowptr, col, alpha=0.85, tol=1e-6, max_iter=100, symmetric=True, err_history=None):
+    """(x float32 [N], iterations): nx.pagerank of the CSR graph with networkx's defaults (model.py:158-162 calls it so) -- uniform
+    start, personalization and dangling weights, the power iteration stopped after the first step with err < N * tol; SageError
+    naming "converge" after max_iter steps, where networkx raises PowerIterationFailedConvergence.  symmetric=True: the graph's
+    own CSR is its pull CSR (every stored entry one link, a self loop too).  symmetric=False: rows are out-edge lists, as of an
+    nx.DiGraph; the pull runs over csr_transpose(rowptr, col) with the out-degrees of the original rows.  Ids are checked once, on
+    the host; per iteration the host reads the 4 bytes of err.  err_history: a list that receives every step's err."""
+    n, col, _ = _pagerank_graph("pagerank", rowptr, col, alpha)
+    if int(max_iter) < 1:
+        raise native.SageError(f"pagerank: max_iter = {max_iter!r}")
+    e = int(rowptr[-1])
+    if e < 0 or e > col.numel() or int(rowptr[0]) != 0:
+        raise native.SageError("pagerank: rowptr is not a row pointer array of col")
+    dev = col.device
+    out_degree = None
+    if symmetric:
+        _in_range("pagerank", "id", col[:e], n)
+    else:
+        out_degree = (rowptr[1:] - rowptr[:-1]).to(torch.int32).contiguous()
+        rowptr, col = csr_transpose(rowptr, col)                      # checks the ids itself
+        col = _nonempty(col)
+    workspace = _workspace("pagerank", pagerank_workspace_bytes(n, e), None, dev, f"num_nodes = {n}, num_edges = {e}")
+    xs, ys = torch.empty(2, n, dtype=torch.float32, device=dev), torch.empty(2, n, dtype=torch.float32, device=dev)
+    inv_out = torch.empty(n, dtype=torch.float32, device=dev)
+    state = torch.empty(2, dtype=torch.float32, device=dev)
+    L, st = native.lib(), native.stream_handle()
+    native.check(L.sage_pagerank_init(native.ptr(rowptr), n, e, native.ptr(out_degree), native.ptr(xs[0]), native.ptr(ys[0]), native.ptr(inv_out),
+                                      native.ptr(state), native.ptr(workspace), workspace.numel(), st), "pagerank_init")
+    for it in range(1, int(max_iter) + 1):
+        cur, nxt = (it - 1) & 1, it & 1
+        native.check(L.sage_pagerank_step(native.ptr(rowptr), native.ptr(col), n, e, native.ptr(inv_out), float(alpha), native.ptr(xs[cur]),
+                                          native.ptr(ys[cur]), native.ptr(xs[nxt]), native.ptr(ys[nxt]), native.ptr(state), native.ptr(workspace),
+                                          workspace.numel(), st), "pagerank_step")
+        err = float(state[0])
+        if err_history is not None:
+            err_history.append(err)
+        if err < n * tol:
+            return xs[nxt].clone(), it
+    raise native.SageError(f"pagerank: power iteration failed to converge within {int(max_iter)} iterations (err = {err:.3e}, "
+                           f"N * tol = {n * tol:.3e})")
+
+
 def row_order_workspace_bytes(n):
     """Bytes of the workspace sage_row_order needs (host arithmetic; 0 = n out of range)."""
     return int(native.lib().sage_row_order_workspace_bytes(int(n)))

@@ -435,24 +435,25 @@ class EngineTrainer:
 
 def run_engine_training(graph, feat_data, labels, num_classes, seed=1, epochs=1, batch_size=128, ref_batching=False, lr=0.7,
                         sample_seed=0, hidden1=50, hidden2=128, num_sample1=10, num_sample2=10, gcn=True, head="torch", initializer=None,
-                        embed_dim=100, sparse_embed=False, exact_eval=False):
+                        embed_dim=100, sparse_embed=False, exact_eval=False, act1=None):
     """run_model (model.py:184-259) on the engine path: same split, shuffles, batching and optimiser as run_training above, every
     step through EngineTrainer.  -> dict(f1_micro, f1_macro, mean_step_time, losses, trainer).
     initializer: None (or "None") -- the frozen table feat_data; "1hot" -- a trainable embedding row per node, ReLU; "node_degree" -- a
     row per degree, SIGMOID at layer 1 (encoders.py:58-59).  feat_data is not read for the last two and may be None; embed_dim is
     the embedding's width (the reference's --feature_dim default), a multiple of 4.  sparse_embed: EngineTrainer's (an initializer
     only): update the touched embedding rows alone.  exact_eval: the validation predictions come from predict_exact (full
-    neighbourhoods, no sampler key) instead of one sampled forward; training is the same either way."""
-    from .fullgraph import embed_arguments
+    neighbourhoods, no sampler key) instead of one sampled forward; training is the same either way.  act1: layer 1's activation over
+    the frozen table (None: ReLU), ACT_SIGMOID for datasets.pagerank_table; refused with an initializer, which sets its own."""
+    from .fullgraph import embed_arguments, frozen_arguments
     dev = torch.device("cuda")
-    embed = embed_arguments("run_engine_training", initializer, (None, "None"), graph, embed_dim, dev)
+    embed = embed_arguments("run_engine_training", initializer, (None, "None"), graph, embed_dim, dev, act1)
     rowptr, col = graph.to(dev)
     table = torch.as_tensor(feat_data, dtype=torch.float32).to(dev) if embed is None else None
     _, val, train = _split(graph.num_nodes, seed)
     train = list(train)
     top = len(train) if ref_batching else batch_size
     tr = EngineTrainer(rowptr, col, table, num_classes, hidden1, hidden2, num_sample1, num_sample2, gcn=gcn, lr=lr, max_batch=max(top, len(val)),
-                       head=head, sparse_embed=sparse_embed, **(embed or {}))
+                       head=head, sparse_embed=sparse_embed, **(embed or frozen_arguments(act1)))
     labels_dev = torch.as_tensor(np.asarray(labels).reshape(-1), dtype=torch.int64).to(dev)
     losses, key = [], int(sample_seed) << 20
     torch.cuda.synchronize()

@@ -1003,6 +1003,64 @@ int    sage_xent_head(const float* emb, int64_t lde, int32_t dim,            /* 
                       float* grad_w   /* [C, dim] nullable, STORED */, int64_t ldgw,
                       void* workspace, size_t workspace_bytes, sage_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * sage_pagerank_* (additive, ABI 9) -- the `pagerank` initializer.
+ * model.py:158-162 (and its copies at 322-326 and 470-474) calls nx.pagerank(G)
+ * with its defaults and uses the result as the single feature column, layer 1
+ * through a sigmoid (encoders.py:58).  These entries are that power iteration on
+ * the device, one step per call, as a PULL over a CSR whose row i lists the
+ * nodes that link to i -- for a symmetric graph its own CSR, for out-edge lists
+ * their transpose with out_degree taken from the original rows:
+ *     s_i      = sum of y[col[e]] over e in [rowptr[i], rowptr[i+1])
+ *     x_next_i = alpha * (s_i + mass / N) + (1 - alpha) / N
+ *     y_next_i = x_next_i * inv_out[i]
+ *     err      = sum over i of |x_next_i - x_i|
+ * with y = x * inv_out, inv_out[j] = 1 / out-degree of j (0 for a dangling
+ * node) and mass = the sum of x_j over the dangling nodes: uniform start 1 / N,
+ * uniform personalization and dangling weights, every stored entry (a self loop
+ * too) one link of weight 1.  The caller stops after the first step whose
+ * err < N * tol (nx: tol = 1e-6, max_iter = 100, alpha = 0.85).
+ * state is float[2] on the device: {err of the last step, mass of the current
+ * x}; a step reads state[1] and stores both.  All arrays are fp32 [N] except
+ * rowptr (int64 [N + 1]), col (int32, at least rowptr[N] entries) and
+ * out_degree (int32 [N]).
+ * Order of the sums (csrc/sage_pagerank.hip states it in full): the bits of
+ * x_next[i] depend on row i's stored entries, y, alpha, mass and N alone; rows
+ * longer than SAGE_CSR_MEAN_CHUNK entries are cut into chunks summed apart
+ * and added in chunk order; err and mass are per-tile partials added in a fixed
+ * order.  No float atomics: two calls on the same inputs give the same bits.
+ * Wrong ids give wrong numbers, never an access out of range: ids from col are
+ * clamped into [0, N), row pointers into [0, rowptr[N]] and made non-decreasing.
+ *
+ * sage_pagerank_init   replaces x = 1 / N (nx.pagerank's start): stores x,
+ *                      inv_out (from out_degree, or from the row lengths when
+ *                      it is NULL), y, state = {0, mass}, and plans the chunk
+ *                      split of the rows into the workspace.
+ * sage_pagerank_load   the same start from the caller's x and inv_out (neither
+ *                      is written): y, state = {0, mass} and the plan.
+ * sage_pagerank_step   one iteration; the workspace is the one init / load
+ *                      filled for this rowptr (any other gives wrong numbers).
+ *                      x_next and y_next are arrays of their own.
+ * num_edges bounds rowptr[N] and sizes the workspace, as sage_csr_sum's
+ * max_edges does; a step must pass what init passed.
+ * Host validation, before any launch: num_nodes outside [1, 2^31), num_edges
+ * < 0, alpha outside (0, 1), a NULL array, aliased outputs: SAGE_EINVAL; a
+ * short workspace: SAGE_ENOSPACE.  The size query is host arithmetic and
+ * returns 0 for a shape out of range.  Workspace 256-byte aligned.
+ * ------------------------------------------------------------------------- */
+size_t sage_pagerank_workspace_bytes(int64_t num_nodes, int64_t num_edges);
+int sage_pagerank_init(const int64_t* rowptr, int64_t num_nodes, int64_t num_edges,
+                       const int32_t* out_degree /* [N], nullable = row lengths */,
+                       float* x, float* y, float* inv_out, float* state /* [2]: err, mass */,
+                       void* workspace, size_t workspace_bytes, sage_stream_t stream);
+int sage_pagerank_load(const int64_t* rowptr, int64_t num_nodes, int64_t num_edges,
+                       const float* x, const float* inv_out, float* y, float* state,
+                       void* workspace, size_t workspace_bytes, sage_stream_t stream);
+int sage_pagerank_step(const int64_t* rowptr, const int32_t* col, int64_t num_nodes, int64_t num_edges,
+                       const float* inv_out, float alpha, const float* x, const float* y,
+                       float* x_next, float* y_next, float* state,
+                       void* workspace, size_t workspace_bytes, sage_stream_t stream);
+
 /* (ABI 5: sage_set_option is gone with the only option it carried -- the producer / consumer contraction kernel of round 3 was measured
  * slower inside the pipeline and deleted in round 4.) */
 
