@@ -40,6 +40,18 @@ def pagerank_table(graph, device, **kw):
     return x.reshape(-1, 1)
 
 
+def eigen_table(graph, device, feature_dim=100, **kw):
+    """float32 [N, feature_dim] on `device`: the frozen feature table of --initializer eigen_decomposition (model.py:163-180: column
+    j is the eigenvector of the j-th largest eigenvalue of the adjacency matrix, a dense LA.eig there), computed on the device by
+    ops.eigen_top; **kw are its keywords (tol, max_iter, degree, guard, seed, check_symmetric, history).  A column's sign is
+    LAPACK's in the reference and ops.eigen_top's rule here (largest entry positive).  Layer 1 keeps the default ReLU: this
+    initializer is not in encoders.py:58's sigmoid list."""
+    from . import ops
+    rowptr, col = graph.to(device)
+    _, vectors, _ = ops.eigen_top(rowptr, col, feature_dim, **kw)
+    return vectors
+
+
 def standin_citation(graph, num_classes=7, feat_dim=1433, words_per_node=18, topic_words=60, purity=0.7, seed=0):
     """-> (feat_data float32 [N, feat_dim] 0/1, labels int64 [N, 1]) in the reference loaders' layout
     (model.py:267-269: feat_data, labels [N,1])."""

@@ -46,6 +46,7 @@ SYMBOLS = [
     "sage_csr_mean_backward_touched_workspace_bytes", "sage_csr_mean_backward_touched",
     "sage_csr_mean_bf16",
     "sage_pagerank_workspace_bytes", "sage_pagerank_init", "sage_pagerank_load", "sage_pagerank_step",
+    "sage_csr_cheb_workspace_bytes", "sage_csr_cheb_plan", "sage_csr_cheb_step",
 ]
 PIPE_MAX_DEPTH = 8
 
@@ -189,6 +190,9 @@ def lib():
     L.sage_pagerank_init.argtypes = [P, I64, I64, P, P, P, P, P, P, c_size_t, P]
     L.sage_pagerank_load.argtypes = [P, I64, I64, P, P, P, P, P, c_size_t, P]
     L.sage_pagerank_step.argtypes = [P, P, I64, I64, P, c_float, P, P, P, P, P, P, c_size_t, P]
+    L.sage_csr_cheb_workspace_bytes.argtypes = [I64, I64, I32]
+    L.sage_csr_cheb_plan.argtypes = [P, I64, I64, I32, P, c_size_t, P]
+    L.sage_csr_cheb_step.argtypes = [P, P, I64, I64, P, I64, P, I64, I32, c_float, c_float, c_float, P, I64, P, c_size_t, P]
     for name in SYMBOLS:
         fn = getattr(L, name)
         if name == "sage_prepared_weight_bytes" or name.endswith("_workspace_bytes"):

@@ -963,6 +963,193 @@ def pagerank(rowptr, col, alpha=0.85, tol=1e-6, max_iter=100, symmetric=True, er
                            f"N * tol = {n * tol:.3e})")
 
 
+def csr_cheb_workspace_bytes(num_nodes, num_edges, dim):
+    """Bytes of the workspace the sage_csr_cheb_* entries need (host arithmetic; 0 = shape out of range)."""
+    return int(native.lib().sage_csr_cheb_workspace_bytes(int(num_nodes), int(num_edges), int(dim)))
+
+
+class CsrChebPlan:
+    """A square CSR graph planned for csr_cheb_step at one width: the chunk split of its long rows sits in `workspace`, made once by
+    csr_cheb_plan and read by every step."""
+
+    def __init__(self, rowptr, col, dim, num_nodes, num_edges, workspace):
+        self.rowptr, self.col, self.dim, self.num_nodes, self.num_edges, self.workspace = rowptr, col, dim, num_nodes, num_edges, workspace
+
+
+def csr_cheb_plan(rowptr, col, dim):
+    """CsrChebPlan of the square CSR (rowptr int64 [N + 1], col int32) for blocks of `dim` columns (include/sage355.h:
+    sage_csr_cheb_plan).  Once per graph and width; the steps on it re-plan nothing."""
+    _need_gpu()
+    n = _graph("csr_cheb_plan", rowptr, col)
+    if n < 1:
+        raise native.SageError("csr_cheb_plan: the graph has no nodes")
+    dim = int(dim)
+    col = _nonempty(col)
+    e = col.numel()
+    workspace = _workspace("csr_cheb_plan", csr_cheb_workspace_bytes(n, e, dim), None, col.device, f"num_nodes = {n}, num_edges = {e}, dim = {dim}")
+    native.check(native.lib().sage_csr_cheb_plan(native.ptr(rowptr), n, e, dim, native.ptr(workspace), workspace.numel(), native.stream_handle()),
+                 "csr_cheb_plan")
+    return CsrChebPlan(rowptr, col, dim, n, e, workspace)
+
+
+def csr_cheb_step(plan, y, x=None, a=1.0, b=0.0, g=0.0, out=None):
+    """[N, dim]: out[i] = a * S_i + b * y[i] + g * x[i] with S_i the sum of y[col[e]] over row i's entries in stored order (the bits of
+    csr_sum) -- one step of a Chebyshev three-term recurrence, or with the defaults the product A.y (include/sage355.h:
+    sage_csr_cheb_step).  x=None drops the last term.  y, x and out are fp32 row-major with any leading dimension; out may be x
+    (in place), never y."""
+    _need_gpu()
+    if not isinstance(plan, CsrChebPlan):
+        raise native.SageError("csr_cheb_step: plan must come from csr_cheb_plan")
+    n, dim = plan.num_nodes, plan.dim
+    y, ldy = _row_major(y, "y")
+    if tuple(y.shape) != (n, dim):
+        raise native.SageError(f"csr_cheb_step: y is {tuple(y.shape)}, expected ({n}, {dim})")
+    ldx = dim
+    if x is not None:
+        x, ldx = _row_major(x, "x")
+        if tuple(x.shape) != (n, dim):
+            raise native.SageError(f"csr_cheb_step: x is {tuple(x.shape)}, expected ({n}, {dim})")
+    out, ldo = _out_rows("csr_cheb_step", out, n, dim, y.device)
+    ws = plan.workspace
+    rc = native.lib().sage_csr_cheb_step(native.ptr(plan.rowptr), native.ptr(plan.col), n, plan.num_edges, native.ptr(y), ldy, native.ptr(x), ldx,
+                                         dim, float(a), float(b), float(g), native.ptr(out), ldo, native.ptr(ws), ws.numel(),
+                                         native.stream_handle())
+    native.check(rc, "csr_cheb_step")
+    return out
+
+
+EIGEN_MAX_K = 1000                                               # the reference's assert on feature_dim (model.py:165)
+
+
+def _cholesky_qr(x, spare):
+    """x [N, m] with orthonormal columns to about the square of its condition number times fp32 rounding: the Gram matrix by torch.mm
+    on the device, its m x m Cholesky factor in fp64 on the host, x . R^-1 into `spare`.  A Gram matrix that is not positive definite
+    in fp64 (columns dependent to rounding) goes through its eigen-decomposition instead, small eigenvalues raised to rounding level.
+    Returns (the orthonormalised block, the buffer that is free now)."""
+    import numpy as np
+    gram = torch.mm(x.t(), x).double().cpu().numpy()
+    gram = (gram + gram.T) / 2
+    try:
+        rinv = np.linalg.inv(np.linalg.cholesky(gram)).T
+    except np.linalg.LinAlgError:
+        w, q = np.linalg.eigh(gram)
+        rinv = q / np.sqrt(np.maximum(w, w.max() * 2.0 ** -40))
+    torch.mm(x, torch.from_numpy(np.ascontiguousarray(rinv)).to(device=x.device, dtype=torch.float32), out=spare)
+    return spare, x
+
+
+def _round_once(v):
+    """v [N, k] fp32, orthonormal to the rounding of the fp32 products that made it (about sqrt(m) * 2^-24), orthonormalised once more
+    in fp64 -- Gram matrix and product on the device, the k x k Cholesky factor on the host -- and rounded to fp32: what is returned
+    is an orthonormal block rounded once, |V^T V - I| <= 2^-23 per element."""
+    import numpy as np
+    v64 = v.double()
+    gram = torch.mm(v64.t(), v64).cpu().numpy()
+    rinv = np.linalg.inv(np.linalg.cholesky((gram + gram.T) / 2)).T
+    return torch.mm(v64, torch.from_numpy(np.ascontiguousarray(rinv)).to(v.device)).float()
+
+
+def _fix_signs(v):
+    """Each column's entry of largest magnitude made positive, the lowest index on a tie (in place)."""
+    n, k = v.shape
+    rows = torch.arange(n, dtype=torch.int32, device=v.device).unsqueeze(1)
+    for c0 in range(0, k, 16):
+        blk = v[:, c0:c0 + 16]
+        mag = blk.abs()
+        first = torch.where(mag == mag.amax(0, keepdim=True), rows, n).amin(0).long()
+        lead = blk.gather(0, first.unsqueeze(0))
+        blk.mul_(torch.where(lead < 0, -1.0, 1.0).to(v.dtype))
+    return v
+
+
+def eigen_top(rowptr, col, k, tol=1e-4, max_iter=200, degree=10, guard=None, seed=0, check_symmetric=True, history=None):
+    """(values float64 [k] on the host, descending; vectors float32 [N, k] on the device; iterations): the k largest eigenvalues of the
+    symmetric CSR graph's adjacency matrix (every stored entry a 1) and their eigenvectors -- what model.py:163-180 takes from a dense
+    LA.eig -- by Chebyshev-filtered subspace iteration on a block of m = k + guard columns.  Every A.X is one csr_cheb_step on a
+    graph planned once; the dense algebra (Gram matrices, rotations) is torch.mm on the device, the m x m Cholesky and eigh fp64
+    on the host.  Every returned pair has ||A v - theta v||_2 <= tol * theta_1 as evaluated here in fp32; columns are orthonormal
+    to one fp32 rounding (a last fp64 pass, _round_once) and their entry of largest magnitude is positive (lowest index on a tie); the same arguments give the same bits.
+    SageError: k outside [1, min(N, 1000)], no entries, a CSR that is not symmetric (check_symmetric: one comparison with
+    csr_transpose), no convergence within max_iter outer iterations ("converge").  history: a list that receives each iteration's
+    largest residual norm of the first k pairs."""
+    import math
+
+    import numpy as np
+    k = int(k)
+    if k < 1 or k > EIGEN_MAX_K:
+        raise native.SageError(f"eigen_top: k = {k}, expected inside [1, {EIGEN_MAX_K}]")
+    if int(max_iter) < 1 or int(degree) < 1 or not float(tol) > 0.0:
+        raise native.SageError(f"eigen_top: max_iter = {max_iter!r}, degree = {degree!r}, tol = {tol!r}")
+    if guard is not None and int(guard) < 0:
+        raise native.SageError(f"eigen_top: guard = {guard!r}")
+    _need_gpu()
+    n = _graph("eigen_top", rowptr, col)
+    if k > n:
+        raise native.SageError(f"eigen_top: k = {k} for a graph of {n} nodes")
+    e = int(rowptr[-1])
+    if e < 0 or e > col.numel() or int(rowptr[0]) != 0:
+        raise native.SageError("eigen_top: rowptr is not a row pointer array of col")
+    if e == 0:
+        raise native.SageError("eigen_top: the graph has no entries (every eigenvalue is 0)")
+    dev = col.device
+    lens = rowptr[1:] - rowptr[:-1]
+    if bool((lens < 0).any()):
+        raise native.SageError("eigen_top: rowptr is not a row pointer array of col")
+    _in_range("eigen_top", "id", col[:e], n)
+    src = torch.repeat_interleave(torch.arange(n, dtype=torch.int64, device=dev), lens)
+    dst = col[:e].to(torch.int64)
+    if check_symmetric:
+        rowptr_t, col_t = csr_transpose(rowptr, col[:e])          # row u: its sources, ascending
+        own = torch.sort(src * n + dst).values % n                 # row u: its stored ids, ascending
+        if not torch.equal(rowptr_t, rowptr) or not torch.equal(own.to(torch.int32), col_t):
+            raise native.SageError("eigen_top: the CSR is not symmetric (row u must hold v as often as row v holds u)")
+    # rho(A)^2 <= the largest row sum of A^2 = max_i sum over row i's entries of len(col[e]): a proven lower bound of the spectrum
+    lo = -math.sqrt(float(torch.zeros(n, dtype=torch.int64, device=dev).index_add_(0, src, lens[dst]).max()))
+    del src, dst
+    m = k + (max(8, k // 5) if guard is None else int(guard))
+    m = min(n, (m + 3) // 4 * 4)
+    plan = csr_cheb_plan(rowptr, col, m)
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(int(seed))
+    x = torch.randn(n, m, generator=gen, device=dev, dtype=torch.float32)
+    b1, b2, b3 = (torch.empty_like(x) for _ in range(3))
+    theta = None
+    for it in range(1, int(max_iter) + 1):
+        if theta is not None:                                    # 1. filter: damp [lo, cut], the smallest Ritz value of the block
+            cut, top = float(theta[-1]), float(theta[0])
+            half, mid = max((cut - lo) / 2, 1e-30 * top), (cut + lo) / 2
+            s1 = half / (top - mid)
+            s = s1
+            csr_cheb_step(plan, x, a=s / half, b=-mid * s / half, out=b1)
+            old, cur = x, b1
+            for _ in range(2, int(degree) + 1):
+                s_next = 1.0 / (2.0 / s1 - s)
+                csr_cheb_step(plan, cur, x=old, a=2 * s_next / half, b=-2 * s_next * mid / half, g=-s * s_next, out=old)
+                old, cur, s = cur, old, s_next
+            x, b1 = cur, old
+        x.div_(torch.linalg.vector_norm(x, dim=0).clamp_min(1e-30))      # 2. orthonormalise: columns to unit norm, Cholesky-QR twice
+        x, b1 = _cholesky_qr(x, b1)
+        x, b1 = _cholesky_qr(x, b1)
+        ax = csr_cheb_step(plan, x, out=b2)                       # 3. Rayleigh-Ritz
+        h = torch.mm(x.t(), ax).double().cpu().numpy()
+        w, q = np.linalg.eigh((h + h.T) / 2)
+        theta, q = w[::-1].copy(), np.ascontiguousarray(q[:, ::-1])
+        if not theta[0] > 0.0:
+            raise native.SageError(f"eigen_top: largest Ritz value {theta[0]!r} is not positive")
+        qf = torch.from_numpy(q).to(device=dev, dtype=torch.float32)
+        xr = torch.mm(x, qf, out=b3)
+        res = torch.mm(ax, qf, out=b1)                            # 4. residual columns A X - X theta
+        res.addcmul_(xr, torch.from_numpy(theta).to(device=dev, dtype=torch.float32).unsqueeze(0), value=-1.0)
+        worst = float(torch.linalg.vector_norm(res[:, :k], dim=0).max())
+        if history is not None:
+            history.append(worst)
+        x, b1, b2, b3 = xr, x, ax, res
+        if worst <= tol * theta[0]:
+            return torch.from_numpy(theta[:k].copy()), _fix_signs(_round_once(x[:, :k])), it
+    raise native.SageError(f"eigen_top: subspace iteration failed to converge within {int(max_iter)} iterations (largest residual "
+                           f"{worst:.3e}, tol * theta_1 = {tol * theta[0]:.3e})")
+
+
 def row_order_workspace_bytes(n):
     """Bytes of the workspace sage_row_order needs (host arithmetic; 0 = n out of range)."""
     return int(native.lib().sage_row_order_workspace_bytes(int(n)))

@@ -1061,6 +1061,56 @@ int sage_pagerank_step(const int64_t* rowptr, const int32_t* col, int64_t num_no
                        float* x_next, float* y_next, float* state,
                        void* workspace, size_t workspace_bytes, sage_stream_t stream);
 
+/* ---------------------------------------------------------------------------
+ * sage_csr_cheb_* (additive, ABI 9) -- the A.X product of the
+ * `eigen_decomposition` initializer.
+ * model.py:163-180 (and its two copies) takes LA.eig of the dense adjacency
+ * matrix and uses the eigenvectors of the feature_dim largest eigenvalues as
+ * the feature table.  ops.eigen_top computes those vectors by Chebyshev-
+ * filtered subspace iteration, whose only sparse operation is one step of a
+ * three-term recurrence on a block of dim columns, in one pass:
+ *     S_i       = sum of y[col[e], :] over e in [rowptr[i], rowptr[i+1])
+ *     out[i, :] = fma(a, S_i, fma(b, y[i, :], g * x[i, :]))
+ *     out[i, :] = fma(a, S_i, b * y[i, :])                   when x is NULL
+ * (a = 1, b = g = 0: the plain product A.y.)  rowptr is int64 [N + 1], col
+ * int32 with at least rowptr[N] entries, y, x and out fp32 [N, dim] row-major
+ * with leading dimensions ldy, ldx, ldo >= dim.
+ * Order of the sums: S_i has the bits of sage_csr_sum -- each column is summed
+ * in stored order, rows longer than SAGE_CSR_MEAN_CHUNK entries are cut into
+ * chunks summed apart and added in chunk order.  out[i, :] depends on row i's
+ * stored entries, y, x[i, :] and the three scalars alone, not on the rows
+ * beside it, on dim's cut into lanes or on the grid.  No float atomics: two
+ * calls on the same inputs give the same bits.
+ * A row is walked by a group of 16, 32 or 64 lanes, the smallest that holds
+ * its columns at four per lane (one per lane when dim, a leading dimension or
+ * a pointer does not allow 16-byte accesses); wider rows loop over column
+ * blocks.
+ * Wrong ids give wrong numbers, never an access out of range: ids from col are
+ * clamped into [0, N), row pointers into [0, rowptr[N]] and made non-decreasing.
+ *
+ * sage_csr_cheb_plan   plans the chunk split of the rows into the workspace,
+ *                      once per graph.
+ * sage_csr_cheb_step   one step; the workspace is the one plan filled for this
+ *                      rowptr, num_nodes, num_edges and dim (any other gives
+ *                      wrong numbers).  out may be x (with ldo == ldx): a row
+ *                      reads only its own row of x before it is stored.  out
+ *                      must not overlap y.
+ * num_edges bounds rowptr[N] and sizes the workspace, as sage_csr_sum's
+ * max_edges does; a step must pass what plan passed.
+ * Host validation, before any launch: num_nodes outside [1, 2^31), num_edges
+ * < 0, dim outside [1, 2^20], a leading dimension below dim, a NULL array, out
+ * overlapping y: SAGE_EINVAL; a short workspace: SAGE_ENOSPACE.  The size query
+ * is host arithmetic and returns 0 for a shape out of range.  Workspace
+ * 256-byte aligned.
+ * ------------------------------------------------------------------------- */
+size_t sage_csr_cheb_workspace_bytes(int64_t num_nodes, int64_t num_edges, int32_t dim);
+int sage_csr_cheb_plan(const int64_t* rowptr, int64_t num_nodes, int64_t num_edges, int32_t dim,
+                       void* workspace, size_t workspace_bytes, sage_stream_t stream);
+int sage_csr_cheb_step(const int64_t* rowptr, const int32_t* col, int64_t num_nodes, int64_t num_edges,
+                       const float* y, int64_t ldy, const float* x /* nullable */, int64_t ldx, int32_t dim,
+                       float a, float b, float g, float* out, int64_t ldo,
+                       void* workspace, size_t workspace_bytes, sage_stream_t stream);
+
 /* (ABI 5: sage_set_option is gone with the only option it carried -- the producer / consumer contraction kernel of round 3 was measured
  * slower inside the pipeline and deleted in round 4.) */
 
