@@ -211,13 +211,27 @@ def check(rc, what=""):
         raise SageError(f"{what or 'libsage355'} failed (rc={rc}): {msg}")
 
 
+def on_current_device(t):
+    """The device rule: a device tensor lives on torch's CURRENT device, or SageError naming both.  Every launch goes to the current
+    device's stream (stream_handle), so a pointer into another GPU's memory would be walked by a kernel of the wrong device -- the
+    sibling of the host pointer.  Arguments on mixed devices fall under it too: at most one device is the current one."""
+    import torch
+    cur = torch.cuda.current_device()
+    idx = t.device.index
+    if idx is not None and idx != cur:
+        raise SageError(f"native.ptr: a tensor on cuda:{idx} while cuda:{cur} is the current device: every launch goes to the current "
+                        f"device's stream (run the call under torch.cuda.device({idx}))")
+
+
 def ptr(t):
     """Device pointer of a tensor (None -> NULL).  The only way a tensor becomes a pointer of a library call: host memory is refused
-    here, whatever the wrapper checked -- a kernel that walks a host address can take the whole GPU node down."""
+    here, whatever the wrapper checked -- a kernel that walks a host address can take the whole GPU node down -- and so is memory of
+    a GPU that is not the current device (on_current_device)."""
     if t is None:
         return None
     if not t.is_cuda:
         raise SageError(f"native.ptr: a {tuple(t.shape)} {t.dtype} tensor on {t.device}, not on a GPU")
+    on_current_device(t)
     return c_void_p(t.data_ptr())
 
 

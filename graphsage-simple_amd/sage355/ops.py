@@ -164,6 +164,13 @@ def next_pow2(x):
     return p
 
 
+def _frontier_struct(frontier):
+    """The sage_frontier_t (`.c`) of a frontier -- a Frontier, or any object with its `keys` tensor and `c` -- for one call: its pointers
+    were taken once, so the device rule (native.on_current_device) is checked again at every call that passes it."""
+    native.on_current_device(frontier.keys)
+    return frontier.c
+
+
 class Frontier:
     """Device hash set of distinct ids + id -> row map (aggregators.py:52-53)."""
 
@@ -175,12 +182,12 @@ class Frontier:
         self.rows = torch.empty(self.capacity, dtype=torch.int32, device=device)
         self.nodes = torch.empty(self.max_nodes, dtype=torch.int32, device=device)
         self.count = torch.zeros(1, dtype=torch.int32, device=device)
-        self.c = native.Frontier(self.keys.data_ptr(), self.rows.data_ptr(), self.capacity, self.nodes.data_ptr(),
-                                 self.count.data_ptr(), self.max_nodes)
+        P = native.ptr                                     # the struct's pointers pass the one check too
+        self.c = native.Frontier(P(self.keys).value, P(self.rows).value, self.capacity, P(self.nodes).value, P(self.count).value, self.max_nodes)
         self.reset(first_row)
 
     def reset(self, first_row=0):
-        native.check(native.lib().sage_frontier_reset(self.c, int(first_row), native.stream_handle()), "frontier_reset")
+        native.check(native.lib().sage_frontier_reset(_frontier_struct(self), int(first_row), native.stream_handle()), "frontier_reset")
 
     def size(self):
         return int(self.count.item())   # host sync: tests / generic path only
@@ -207,7 +214,7 @@ def _sample(entry, rowptr, col, nodes, k, seed, tag, n_dev, frontier, insert_sel
     rc = getattr(native.lib(), "sage_" + entry)(
         native.ptr(rowptr), native.ptr(col), num_nodes, native.ptr(nodes), n, native.ptr(n_dev), int(k),
         int(seed) & 0xFFFFFFFFFFFFFFFF, int(tag), native.ptr(nbr), native.ptr(cnt), native.ptr(any_nonempty),
-        frontier.c if frontier is not None else None, 1 if insert_self else 0, native.ptr(nbr_slot),
+        _frontier_struct(frontier) if frontier is not None else None, 1 if insert_self else 0, native.ptr(nbr_slot),
         native.ptr(self_slot), native.stream_handle())
     native.check(rc, entry)
     return nbr, cnt, nbr_slot, self_slot
@@ -241,7 +248,7 @@ def frontier_insert(nbr, cnt, frontier, self_nodes=None, n_dev=None):
     nbr_slot = torch.empty_like(nbr)
     self_slot = torch.empty(n, dtype=torch.int32, device=nbr.device) if self_nodes is not None else None
     rc = native.lib().sage_frontier_insert(native.ptr(nbr), native.ptr(cnt), k, native.ptr(self_nodes), n,
-                                           native.ptr(n_dev), frontier.c, native.ptr(nbr_slot), native.ptr(self_slot),
+                                           native.ptr(n_dev), _frontier_struct(frontier), native.ptr(nbr_slot), native.ptr(self_slot),
                                            native.stream_handle())
     native.check(rc, "frontier_insert")
     return nbr_slot, self_slot
